@@ -7,10 +7,14 @@ resident in HBM.  Default workload = BASELINE.json configs[1]: Talos pos-tracker
 
 The timed steps are a STREAM, not a replay: instance i at step t solves tick (i + t) of the squat reference stream
 (etc/talos/squat.yaml through move_com.cpp:22-45, BASELINE config 4's own definition), so the launch order the library
-derives from earlier launches never comes from the batch it schedules.  The replayed-batch figure (perfect foresight),
-the index-order figure (no schedule) and a run over unrelated batches stand beside `value`.
+derives from earlier launches never comes from the batch it schedules.  With --full, the replayed-batch figure (perfect
+foresight), the index-order figure (no schedule), a run over unrelated batches and the rest of the comparisons, the CPU
+baseline and the parity sample against the oracle stand beside `value`; without it the run times the K steps and nothing else.
+--dump-outputs DIR writes what the last timed step computed, as DIR/<name>.npy (the inputs are the same in every run; at N > 1
+rank 0's shard).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python bench.py --robot icub --batch 4096 --dtype f32          (BASELINE config 3)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -36,6 +40,7 @@ HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 
 ALGORITHMIC_BYTES = {"talos": 35152, "icub": 23872, "franka": 1152}
 N_TICKS = 128  # distinct consecutive ticks of the reference stream kept resident (the timed steps cycle through them)
 SWEEP = (1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096, 8192)
+DUMP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -54,11 +59,18 @@ def parse():
                         "exchange; the path itself has none -- the QPs of a batch are independent)")
     p.add_argument("--no-exchange", action="store_true", help="N > 1: skip the all-gather leg that is timed apart from the solve")
     p.add_argument("--exchange-timeout", type=float, default=120.0, help="seconds after which the all-gather leg is abandoned")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-compare", action="store_true", help="skip the extra runs reported beside `value`")
-    p.add_argument("--no-sweep", action="store_true", help="skip the batch 1..8192 table")
-    p.add_argument("--headline-only", action="store_true", help="the warm-up and the K timed steps and nothing else on the device (no comparison lines, no\n"
-                   "before/after-path sections, no CPU baseline): the command the rocprofv3 passes of tools/profile_round.sh trace, so that\n"
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything beside the headline (comparison runs, before/after-path sections, the batch sweep,\n"
+                        "BASELINE configs 3 and 5, the single-robot seams, the CPU baseline, the parity sample against the oracle, the\n"
+                        "all-gather leg at N > 1); without it a run sets up, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (x, tau, status, iters, objective, n_active, active_mask) as DIR/<name>.npy\n"
+                        "(at N > 1: rank 0's shard of --batch QPs only)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity samples")
+    p.add_argument("--no-compare", action="store_true", help="with --full: skip the extra runs reported beside `value`")
+    p.add_argument("--no-sweep", action="store_true", help="with --full: skip the batch 1..8192 table")
+    p.add_argument("--headline-only", action="store_true", help="the warm-up and the K timed steps and nothing else on the device, even with --full\n"
+                   "(what a run without --full does): the command the rocprofv3 passes of tools/profile_round.sh trace, so that\n"
                    "the kernel's average duration in the trace is the duration of the timed launches")
     p.add_argument("--index-order", action="store_true",
                    help="launch the QPs in index order instead of longest-first (WBCQP_FLAG_INDEX_ORDER)")
@@ -66,11 +78,14 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="bound on the CPU-baseline sample")
     p.add_argument("--traffic", type=float, default=None,
                    help="HBM bytes per launch from rocprofv3 PMC passes (default: scaled from profiles/pmc_latest.json)")
-    p.add_argument("--sweep", default=None, help="also write the batch 1..8192 table to this JSON file")
+    p.add_argument("--sweep", default=None, help="with --full: also write the batch 1..8192 table to this JSON file")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to\n"
                    "exercise the N > 1 code path where RCCL cannot run, e.g. several ranks on one GPU)")
     p.add_argument("--single-device", action="store_true", help="testing only: every rank uses cuda:0 (with --backend gloo)")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.sweep and not a.full:
+        p.error("--sweep writes the batch table that only --full measures")
+    return a
 
 
 def before_path(h, st, dev, B, torch, cpu_baseline=True):
@@ -521,6 +536,23 @@ def franka_single_tick(local_rank, torch, cpu=True):
     return res
 
 
+def dump_outputs(dirname, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: DIR/<name>.npy for every output array of the last timed step, floating ones in their own type, integer ones as float64
+    (exact).  Above `limit` bytes in all, the same seeded sample of rows of every array, their indices in DIR/rows.npy."""
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    n = len(arrays["x"])
+    total = sum(v.nbytes for v in arrays.values())
+    rows = None
+    if total > limit:
+        k = int((limit - (1 << 16)) // (total / n + 8))  # (room for rows.npy and the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = {name: v[rows] for name, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v))
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -625,6 +657,8 @@ def exchange_leg(torch, dist, h, gather, rank, world, dev, d_out, st, B, tdt, sp
 
 def main():
     args = parse()
+    if not args.full:  # a plain run: set-up, warm-up, the K timed steps, the line -- whatever else the bench measures is --full's
+        args.headline_only = True
     if args.headline_only:
         args.no_compare = args.no_sweep = args.no_cpu_baseline = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -757,9 +791,11 @@ def main():
         return el, ev0.elapsed_time(ev1) * 1e-3
 
     # ---- where in the stream the K timed steps lie.  The resident ticks are not equally heavy (the squat's later ticks ask for
-    # more), so a short window is representative only where its mean launch time equals the cycle's: one untimed pass measures
-    # every resident tick's launch (an event pair per launch), and the window starts at the phase whose mean over the K steps
-    # behind the warm-up is closest to the mean over the whole cycle.  `value / long_run` is printed beside it.
+    # more), so a short window is representative only where its mean launch time equals the cycle's.  A launch lasts about as long
+    # as its longest QP (the straggler alone 191 us, the launch 193 us), so one untimed pass records every
+    # resident tick's largest iteration count, and the window starts at the phase whose mean of it over the K steps behind the
+    # warm-up is closest to the cycle's.  Iteration counts, unlike launch times, are the same in every run: so are the ticks the
+    # K steps solve, and what --dump-outputs writes.  The pass's launch times (an event pair per launch) are printed beside it.
     t_first, window = 0, None
     if stream and args.steps < len(tick_dicts) and not args.replay:
         nt = len(tick_dicts)
@@ -767,22 +803,27 @@ def main():
             step(nt - 8 + t)
         torch.cuda.synchronize()
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nt)]
+        longest = torch.zeros(nt, dtype=torch.int32, device=dev)
         for t in range(nt):
             evs[t][0].record()
             step(t)
             evs[t][1].record()
+            longest[t] = d_out["iters"].max()
         torch.cuda.synchronize()
         per = np.array([a.elapsed_time(b) for a, b in evs])
-        means = np.array([per[[(s0 + args.warmup + j) % nt for j in range(args.steps)]].mean() for s0 in range(nt)])
-        t_first = int(np.argmin(np.abs(means - per.mean())))
+        lng = longest.cpu().numpy().astype(np.float64)
+        phase = [[(s0 + args.warmup + j) % nt for j in range(args.steps)] for s0 in range(nt)]
+        means = np.array([lng[ix].mean() for ix in phase])
+        t_first = int(np.argmin(np.abs(means - lng.mean())))
         if distributed:  # every rank times the same stretch
             tf = torch.tensor([t_first], dtype=torch.int64, device=dev)
             dist.broadcast(tf, src=0)
             t_first = int(tf.item())
-        window = {"first_tick": t_first, "ms_window_mean_prepass": float(means[t_first]), "ms_cycle_mean_prepass": float(per.mean()),
+        window = {"first_tick": t_first, "iters_max_window_mean": float(means[t_first]), "iters_max_cycle_mean": float(lng.mean()),
+                  "ms_window_mean_prepass": float(per[phase[t_first]].mean()), "ms_cycle_mean_prepass": float(per.mean()),
                   "ms_cycle_min": float(per.min()), "ms_cycle_max": float(per.max()),
-                  "note": "the timed steps start at the phase of the %d-tick cycle whose %d-step mean launch time is closest to the cycle's mean "
-                          "(untimed pre-pass, one event pair per launch)" % (nt, args.steps)}
+                  "note": "the timed steps start at the phase of the %d-tick cycle whose %d-step mean of the largest iteration count per launch is "
+                          "closest to the cycle's mean (untimed pre-pass; its launch times, one event pair per launch, beside it)" % (nt, args.steps)}
     elapsed, ev_s = timed(args.steps, args.warmup, t_first=t_first)
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -800,12 +841,15 @@ def main():
     mask_gpu = d_out["active_mask"].cpu().numpy().view(np.uint32)
     nact_gpu = d_out["n_active"].cpu().numpy()
     obj_gpu = d_out["objective"].cpu().numpy().astype(np.float64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x": x_gpu.astype(ndt), "tau": tau_gpu.astype(ndt), "objective": obj_gpu.astype(ndt), "status": status,
+                                         "iters": iters, "n_active": nact_gpu, "active_mask": mask_gpu})
 
     # ---- the optional exchange step of BASELINE config 4, timed APART from the solve (the path itself has no collective): the
     # library's own wbcqp_allgather_tau on a communicator of this job's ranks.  It has never run on more than one rank before the
     # driver's 8-GPU run, so it runs under a watchdog: a hang costs the exchange figures, never the line.
     exchange = None
-    if distributed and args.backend == "nccl" and not args.no_exchange:
+    if distributed and args.backend == "nccl" and not args.no_exchange and args.full:
         exchange = exchange_leg(torch, dist, h, gather, rank, world, dev, d_out, st, B, tdt, sp, step, fence, args.exchange_timeout)
 
 
@@ -895,7 +939,8 @@ def main():
         if window is not None:
             result["window"] = window
         if exchange is None and distributed:
-            result["allgather_tau"] = {"skipped_reason": exchange_skipped or gather["err"] or "not requested"}
+            result["allgather_tau"] = {"skipped_reason": exchange_skipped or gather["err"] or
+                                       ("not requested" if args.full else "the all-gather leg timed apart from the solve runs with --full")}
         if exchange is not None:
             result["allgather_tau"] = {k: v for k, v in exchange.items() if k != "hung"}
             if "rccl_nranks" in exchange:

@@ -174,10 +174,38 @@ def test_bench_accepts_the_drivers_command_line_and_counts_usable_cores(monkeypa
     monkeypatch.setattr(_sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
     a = bench.parse()
     assert (a.gpus, a.steps, a.warmup, a.batch, a.robot, a.dtype) == (1, 20, 5, 1024, "talos", "f64")
-    assert not a.replay and not a.headline_only and a.backend == "nccl"
+    assert not a.replay and not a.headline_only and a.backend == "nccl" and not a.full and a.dump_outputs is None
     n, note = bench.usable_cores()
     assert 1 <= n <= (os.cpu_count() or 1) and "os.cpu_count()" in note
     assert bench.ALGORITHMIC_BYTES["talos"] == 35152
+
+
+def test_bench_dump_outputs_writes_every_array_and_samples_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: one .npy per output array, floating arrays in their own type and integer ones as float64; above the byte cap the
+    same seeded rows of every array (indices in rows.npy), within the cap, and the same rows from call to call."""
+    import importlib
+    import sys as _sys
+    _sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    rng = np.random.default_rng(3)
+    B = 4096
+    arrays = {"x": rng.standard_normal((B, 74)), "tau": rng.standard_normal((B, 44)).astype(np.float32), "status": np.zeros(B, np.int32),
+              "active_mask": rng.integers(0, 2 ** 32, (B, 8), dtype=np.uint64).astype(np.uint32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    got = {f.stem: np.load(f) for f in (tmp_path / "all").glob("*.npy")}
+    assert sorted(got) == ["active_mask", "status", "tau", "x"]
+    assert got["tau"].dtype == np.float32 and got["status"].dtype == np.float64 and got["active_mask"].dtype == np.float64
+    assert np.array_equal(got["x"], arrays["x"]) and np.array_equal(got["active_mask"], arrays["active_mask"])
+    cap = 1 << 20
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays, limit=cap)
+    s1 = {f.stem: np.load(f) for f in (tmp_path / "s1").glob("*.npy")}
+    s2 = {f.stem: np.load(f) for f in (tmp_path / "s2").glob("*.npy")}
+    assert sum(f.stat().st_size for f in (tmp_path / "s1").glob("*.npy")) <= cap
+    rows = s1["rows"].astype(np.int64)
+    assert 0 < len(rows) < B and np.all(np.diff(rows) > 0)
+    assert np.array_equal(s1["x"], arrays["x"][rows]) and np.array_equal(s1["tau"], arrays["tau"][rows])
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)
 
 
 def test_the_build_refuses_a_barrier_without_the_lds_wait(tmp_path):
