@@ -47,7 +47,9 @@ extern "C" {
  *   151  no declaration changed.  wbcqp_tick_host fills wbcqp_outputs.active_mask when given; the numbering of active_mask's bits is documented (below);
  *        a slot's FIRST solve on the compact layout makes the force blocks' factor for the force-regularisation weights of its first QP (one small kernel
  *        and one synchronisation of the launch's stream, once per wbcqp_set_structure; never inside a stream capture) -- later QPs that carry those weights
- *        take the factor from there, others compute it as before: the same bits either way (env WBCQP_DEBUG_NO_FFCACHE=1, read at wbcqp_create, turns it off)
+ *        take the factor from there, others compute it as before: the same bits either way (env WBCQP_DEBUG_NO_FFCACHE=1, read at wbcqp_create, turns it off).
+ *        Added without a change of version: wbcqp_mix, wbcqp_mixed_io, wbcqp_tick_mixed and wbcqp_rollout_mixed (instances of one robot model in
+ *        different contact sets, one call)
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -491,6 +493,54 @@ typedef struct {
  * synchronises the device to do it); WBCQP_ROLLOUT_STREAMS in the environment fixes the number of sub-batches (1 .. 8; 1: a plain tick loop)
  * instead of the measured choice. */
 int wbcqp_rollout(wbcqp_handle* handle, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, void* stream);
+
+/* ---- A fleet: instances of ONE robot model in DIFFERENT contact sets, one call ----
+ * Under a walk, the QP changes size at every lift-off and touchdown (remove_contact / add_contact, pos_tracker.cpp:246-263): one library
+ * slot per contact set (a structure and a model each).  wbcqp_tick and wbcqp_rollout take one slot, so every instance of a call is in the
+ * same set.  The two calls below take a MIX of slots and, per instance, which of them it uses this tick: the rows kernel runs once per
+ * non-empty set and tick on that set's instances (read where they lie, written as a contiguous record), the QPs of all sets go out as ONE
+ * launch (wbcqp_solve_ragged: the generic compact kernel when several sets are present), and one kernel puts the outputs back in instance
+ * order and integrates each instance from its own set's x.  Bit for bit, instance i's results are those of wbcqp_tick on its slot.
+ *
+ * Everything is in INSTANCE order: q, v, ref ([batch][nref]), momentum, q_next, v_next, q_solver, and the outputs tau, status, iters,
+ * objective, n_active, active_mask.  x is [batch][ldx] with ldx = the largest n over the mix's slots: instance i's row is in the layout of
+ * ITS slot ([dv; the forces of that slot's contacts]), zero past its n; active_mask numbers the rows of its own slot's CI.
+ * Every slot of a mix holds a structure and a model (wbcqp_set_model), all with the same tree (nq, nv, na, floating base, bodies), the same
+ * nref and the same dt: ONE reference row serves every contact set (a single-support task map points its remaining contact's contact_ref at
+ * the offset the double-support map uses).  Refused with WBCQP_ERR_INVALID, before anything is launched: a mix that breaks that rule,
+ * n_slots outside 1 .. 8, a `which` / `schedule` entry outside [0, n_slots), a NULL w for a slot some instance uses, tlb / tub NULL
+ * where a slot in use has actuation bounds.  A handle with WBCQP_FLAG_WARM_START gets WBCQP_ERR_UNSUPPORTED (a hint does not carry across
+ * a change of contact set).  The force blocks' factor cache of every slot of the mix is made before the first tick is enqueued (from the
+ * weights of instance 0 of that slot's w; the same bits whichever QP it comes from).  The library owns the per-set records (about the
+ * size of the instances' own records) and the plan (the per-tick permutation, 4 bytes per instance and tick, copied up once per call);
+ * the first call of a larger shape allocates them after a device synchronisation.  DEVICE pointers, asynchronous on `stream`; a call
+ * waits on the device for the previous mixed call of the handle (on whatever stream) before it reuses the handle's buffers. */
+typedef struct {
+    int32_t n_slots;          /* 1 .. 8: one slot per contact set of the same robot model */
+    const int32_t* slots;     /* [n_slots] HOST */
+    const void* const* w;     /* [n_slots] HOST array of DEVICE pointers, w[k]: [batch][n_tasks of slots[k]], indexed by INSTANCE; may be
+                                 NULL for a slot no instance uses */
+    const void* tlb;          /* [batch][na] torque bounds by instance (NULL when no slot has actuation bounds) */
+    const void* tub;
+} wbcqp_mix;
+
+typedef struct {              /* wbcqp_tick_io without the record: the library keeps the per-set records */
+    wbcqp_state state;        /* q [batch][nq], v [batch][nv], ref [batch][nref], momentum [batch][6] or NULL */
+    wbcqp_outputs out;        /* x [batch][ldx], tau [batch][na], status, iters (objective, n_active, active_mask) by instance */
+    void* q_next;             /* [batch][nq] */
+    void* v_next;             /* [batch][nv] */
+    void* q_solver;           /* [batch][nv] or NULL */
+    double dt;
+} wbcqp_mixed_io;
+
+/* One tick; which: HOST [batch], instance i uses mix->slots[which[i]]. */
+int wbcqp_tick_mixed(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, const int32_t* which, const wbcqp_mixed_io* io, void* stream);
+/* n_ticks ticks enqueued up front (the host waits for nothing; one stream of ticks); schedule: HOST [n_ticks][batch] index into mix->slots.
+ * io->state.ref is [n_ticks][batch][nref]; io->w, io->tlb, io->tub are not read (the mix's are); out holds the LAST tick's outputs,
+ * iters_sum / ticks_ok the per-instance totals; an instance whose QP fails keeps its state for that tick, as wbcqp_integrate does.
+ * Bit for bit n_ticks calls of wbcqp_tick_mixed with q_next / v_next fed back. */
+int wbcqp_rollout_mixed(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule, const wbcqp_rollout_io* io,
+                        void* stream);
 
 /* The same sequence captured once into a HIP graph and replayed: one graph launch per tick instead of four kernel
  * launches (what matters when the batch is small -- one robot at 1 kHz is the reference's own use case).  The graph is

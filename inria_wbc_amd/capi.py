@@ -28,7 +28,8 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_layout_of", "wbcqp_solve_batch", "wbcqp_solve_batch_host", "wbcqp_solve_ragged",
            "wbcqp_allgather_tau", "wbcqp_integrate", "wbcqp_integrate_host", "wbcqp_set_model", "wbcqp_check_model", "wbcqp_problem_data",
            "wbcqp_problem_data_host", "wbcqp_tick", "wbcqp_tick_host", "wbcqp_tick_graph_create", "wbcqp_tick_graph_launch", "wbcqp_tick_graph_destroy",
-           "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout")
+           "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout",
+           "wbcqp_tick_mixed", "wbcqp_rollout_mixed")
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
 
 c_i32_p = C.POINTER(C.c_int32)
@@ -121,6 +122,14 @@ class CTickIO(C.Structure):
 CTickIO._fields_ = [("state", CState), ("rows", CInputs), ("out", COutputs), ("q_next", C.c_void_p), ("v_next", C.c_void_p),
                     ("q_solver", C.c_void_p), ("dt", C.c_double)]
 
+class CMix(C.Structure):
+    _fields_ = [("n_slots", C.c_int32), ("slots", c_i32_p), ("w", C.POINTER(C.c_void_p)), ("tlb", C.c_void_p), ("tub", C.c_void_p)]
+
+
+class CMixedIO(C.Structure):
+    _fields_ = [("state", CState), ("out", COutputs), ("q_next", C.c_void_p), ("v_next", C.c_void_p), ("q_solver", C.c_void_p), ("dt", C.c_double)]
+
+
 _lib = None
 
 
@@ -166,6 +175,8 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_tick_graph_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CTickIO), C.POINTER(C.c_void_p)]
     lib.wbcqp_tick_graph_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.wbcqp_tick_graph_destroy.argtypes = [C.c_void_p, C.c_void_p]
+    lib.wbcqp_tick_mixed.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, c_i32_p, C.POINTER(CMixedIO), C.c_void_p]
+    lib.wbcqp_rollout_mixed.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, c_i32_p, C.POINTER(CRolloutIO), C.c_void_p]
     _lib = lib
     return lib
 
@@ -447,6 +458,56 @@ class Handle:
         io.iters_sum = iters_sum.data_ptr() if iters_sum is not None else None
         io.ticks_ok = ticks_ok.data_ptr() if ticks_ok is not None else None
         self._check(self.lib.wbcqp_rollout(self._h, slot, batch, n_ticks, C.byref(io), C.c_void_p(stream)))
+
+    @staticmethod
+    def _ptr(t):
+        return t.data_ptr() if t is not None and t.numel() else None
+
+    def _mix(self, slots: Sequence[int], w: Sequence, tlb=None, tub=None):
+        """wbcqp_mix: slots (one per contact set of one robot model), w[k] = device tensor [B, n_tasks of slots[k]] by instance (or None)."""
+        slots_arr = np.ascontiguousarray(slots, dtype=np.int32)
+        w_arr = (C.c_void_p * max(len(slots_arr), 1))(*[self._ptr(t) for t in w])
+        mix = CMix(len(slots_arr), slots_arr.ctypes.data_as(c_i32_p), C.cast(w_arr, C.POINTER(C.c_void_p)), self._ptr(tlb), self._ptr(tub))
+        return mix, (slots_arr, w_arr)  # (the second item keeps the arrays alive for the call)
+
+    def _outs(self, out) -> COutputs:
+        cout = COutputs()
+        for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask"):
+            setattr(cout, k, self._ptr(out.get(k)))
+        return cout
+
+    def tick_mixed(self, slots: Sequence[int], which, state, w: Sequence, out, q_next, v_next, dt: float, tlb=None, tub=None, q_solver=None,
+                   stream: int = 0):
+        """One tick of B instances of one robot model, instance i in the contact set of slots[which[i]] (wbcqp_tick_mixed).  which: host
+        int array [B]; state: q, v, ref [B, nref] (+ momentum [B, 6]) by instance; w[k]: [B, n_tasks of slots[k]] by instance; tlb / tub
+        [B, na]; out: x [B, ldx = max n], tau, status, iters (objective, n_active, active_mask) by instance."""
+        which = np.ascontiguousarray(which, dtype=np.int32)
+        mix, keep = self._mix(slots, w, tlb, tub)
+        io = CMixedIO()
+        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), self._ptr(state.get("ref")), self._ptr(state.get("momentum")))
+        io.out = self._outs(out)
+        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
+        io.dt = float(dt)
+        self._check(self.lib.wbcqp_tick_mixed(self._h, C.byref(mix), int(which.size), which.ctypes.data_as(c_i32_p), C.byref(io),
+                                              C.c_void_p(stream)))
+        del keep
+
+    def rollout_mixed(self, slots: Sequence[int], schedule, state, w: Sequence, out, q_next, v_next, dt: float, tlb=None, tub=None,
+                      q_solver=None, iters_sum=None, ticks_ok=None, stream: int = 0):
+        """K ticks of a fleet in mixed contact sets, enqueued up front (wbcqp_rollout_mixed).  schedule: host int array [K, B] of indices
+        into slots; state: q [B, nq], v [B, nv], ref [K, B, nref] (+ momentum [B, 6] of the last tick's state); out: the last tick's."""
+        schedule = np.ascontiguousarray(schedule, dtype=np.int32)
+        K, B = schedule.shape
+        mix, keep = self._mix(slots, w, tlb, tub)
+        io = CRolloutIO()
+        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), self._ptr(state.get("ref")), self._ptr(state.get("momentum")))
+        io.out = self._outs(out)
+        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
+        io.dt = float(dt)
+        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
+        self._check(self.lib.wbcqp_rollout_mixed(self._h, C.byref(mix), int(B), int(K), schedule.ctypes.data_as(c_i32_p), C.byref(io),
+                                                 C.c_void_p(stream)))
+        del keep
 
     def tick_host(self, slot: int, q: np.ndarray, v: np.ndarray, ref: np.ndarray, tlb, tub, w, dt: float, want_rows: bool = False):
         """One whole tick with host arrays (wbcqp_tick_host): returns dict(x, tau, status, iters, objective, n_active, active_mask, q_next, v_next,

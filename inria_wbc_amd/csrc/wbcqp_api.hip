@@ -43,6 +43,7 @@ struct Slot {
     double* ffc_dev = nullptr;  // the force blocks' factor for one weight (DevStruct::ffc; owned through `allocs`), null: none (no contacts, not compact, disabled)
     bool ffc_built = false;     // ... made from the first QP of the slot's first compact launch (solve_ragged)
     bool has_model = false;     // wbcqp_set_model: tree + task bindings for wbcqp_problem_data
+    std::vector<double> tree;   // ... the tree as numbers (sizes, parents, joint types, placements, inertias, gravity): the slots of a mix must agree on it
     TermsDev terms{};
     std::vector<void*> model_allocs;
 };
@@ -146,6 +147,20 @@ struct wbcqp_handle {
     };
     RollMeas roll_meas[4];
     Staging roll_rec, roll_state;
+    // wbcqp_tick_mixed / wbcqp_rollout_mixed: the per-tick permutations go up through a ring of page-locked buffers (an entry is reused
+    // once the call that last used it is done on the device: four calls ago), the per-set records, gathered weights and outputs, and the
+    // state ping-pong of a roll-out
+    struct MixPlan {
+        Pinned pin;
+        int* dev = nullptr;
+        size_t cap = 0; // ints
+        hipEvent_t done = nullptr;
+        bool used = false;
+    };
+    MixPlan mix_plan[4];
+    int mix_next = 0;
+    Staging mix_rec, mix_state;
+    hipEvent_t mix_done = nullptr; // end of the previous mixed call: the next one (on whatever stream) waits for it before it reuses the buffers
 };
 
 namespace {
@@ -378,6 +393,7 @@ void release_model(Slot& s)
     for (void* p : s.model_allocs) (void)hipFree(p);
     s.model_allocs.clear();
     s.has_model = false;
+    s.tree.clear();
 }
 
 void release(Slot& s)
@@ -746,6 +762,14 @@ int wbcqp_destroy(wbcqp_handle* h)
         if (ss.ord.order) (void)hipFree(ss.ord.order);
         if (ss.ord.queue) (void)hipFree(ss.ord.queue);
     }
+    for (auto& mp : h->mix_plan) {
+        if (mp.pin.host) (void)hipHostFree(mp.pin.host);
+        if (mp.dev) (void)hipFree(mp.dev);
+        if (mp.done) (void)hipEventDestroy(mp.done);
+    }
+    if (h->mix_rec.dev) (void)hipFree(h->mix_rec.dev);
+    if (h->mix_state.dev) (void)hipFree(h->mix_state.dev);
+    if (h->mix_done) (void)hipEventDestroy(h->mix_done);
     delete h;
     return WBCQP_OK;
 }
@@ -859,6 +883,18 @@ int wbcqp_set_structure(wbcqp_handle* h, int slot, const wbcqp_structure* st)
     return WBCQP_OK;
 }
 
+// the force blocks' factor for the weights w (one QP's row), by the kernels' own code, ahead of the solve on its stream; waited for once, so that a
+// launch on another stream never meets a half-written entry
+static int build_ffcache(wbcqp_handle* h, Slot& s, const void* w, hipStream_t stream)
+{
+    if (h->dtype == WBCQP_F64) hipLaunchKernelGGL(ffcache_kernel<double>, dim3(1), dim3(128), 0, stream, s.host_cp, static_cast<const double*>(w), s.ffc_dev);
+    else hipLaunchKernelGGL(ffcache_kernel<float>, dim3(1), dim3(128), 0, stream, s.host_cp, static_cast<const float*>(w), s.ffc_dev);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(stream));
+    s.ffc_built = true;
+    return WBCQP_OK;
+}
+
 int wbcqp_solve_ragged(wbcqp_handle* h, int n_groups, const wbcqp_group* groups, void* stream)
 {
     if (!h) return WBCQP_ERR_INVALID;
@@ -890,13 +926,9 @@ int wbcqp_solve_ragged(wbcqp_handle* h, int n_groups, const wbcqp_group* groups,
             user_capture = cst != hipStreamCaptureStatusNone;
         }
         if (compact && s.ffc_dev && !s.ffc_built && !h->capturing && !user_capture && !(wave_per_qp && s.small)) {
-            // the slot's first compact launch: the force blocks' factor for the weights of its first QP, by the kernels' own code, ahead of the solve on its
-            // stream; waited for once, so that a launch on another stream never meets a half-written entry
-            if (h->dtype == WBCQP_F64) hipLaunchKernelGGL(ffcache_kernel<double>, dim3(1), dim3(128), 0, static_cast<hipStream_t>(stream), s.host_cp, static_cast<const double*>(G.in.w), s.ffc_dev);
-            else hipLaunchKernelGGL(ffcache_kernel<float>, dim3(1), dim3(128), 0, static_cast<hipStream_t>(stream), s.host_cp, static_cast<const float*>(G.in.w), s.ffc_dev);
-            HIP_TRY(h, hipGetLastError());
-            HIP_TRY(h, hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-            s.ffc_built = true;
+            // the slot's first compact launch: the force blocks' factor for the weights of its first QP
+            rc = build_ffcache(h, s, G.in.w, static_cast<hipStream_t>(stream));
+            if (rc != WBCQP_OK) return rc;
         }
         if (wave_per_qp && s.small) { // one wavefront per QP: a launch of their own (wbcqp_small.hpp)
             if (h->dtype == WBCQP_F64) fill_group(s64.g[used_small], s, false, G.batch, &G.in, &G.out);
@@ -1529,9 +1561,19 @@ int wbcqp_set_model(wbcqp_handle* h, int slot, const wbcqp_model* md, const wbcq
     if (o * 8 > 64 * 1024) {
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&terms_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, o * 8));
         HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&terms_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, o * 8));
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&terms_kernel<double, true>), hipFuncAttributeMaxDynamicSharedMemorySize, o * 8));
+        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&terms_kernel<float, true>), hipFuncAttributeMaxDynamicSharedMemorySize, o * 8));
     }
     s.terms = T;
     s.has_model = true;
+    const int nb = md->nbody;
+    s.tree.assign({(double)nb, (double)(md->floating_base ? 1 : 0), md->gravity[0], md->gravity[1], md->gravity[2]});
+    for (int i = 0; i < nb; ++i) {
+        s.tree.push_back((double)md->parent[i]);
+        s.tree.push_back((double)md->jtype[i]);
+    }
+    s.tree.insert(s.tree.end(), md->placement, md->placement + 12 * nb);
+    s.tree.insert(s.tree.end(), md->inertia, md->inertia + 10 * nb);
     return WBCQP_OK;
 }
 
@@ -1827,6 +1869,253 @@ int wbcqp_rollout(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp
         meas->stat = stat_i; meas->S = S; meas->ticks = n_ticks; meas->pending = true;
     }
     return rc_all;
+}
+
+} // extern "C"
+
+// ---- wbcqp_tick_mixed / wbcqp_rollout_mixed: one robot model, its instances in different contact sets ----------------------------------------
+// Per tick: the rows kernel once per non-empty set (terms_kernel<., true>: instances gathered through the tick's permutation, the record of
+// the set written contiguously), ONE solve launch over the sets (wbcqp_solve_ragged), one kernel that scatters the outputs back to instance
+// order and integrates every instance from its set's x (mixed_integrate_kernel).  The host makes the plan: which instances each set holds
+// on each tick.
+namespace {
+
+struct MixCall { // the checked arguments of a mixed call
+    const wbcqp_mix* mix;
+    int batch, n_ticks;
+    const int32_t* which;  // [n_ticks][batch]
+    wbcqp_state state;     // ref: [n_ticks][batch][nref]
+    wbcqp_outputs out;
+    void *q_next, *v_next, *q_solver;
+    double dt;
+    int32_t *iters_sum, *ticks_ok;
+};
+
+int check_mix(wbcqp_handle* h, const MixCall& c)
+{
+    if (h->flags & WBCQP_FLAG_WARM_START) return fail(h, WBCQP_ERR_UNSUPPORTED, "mixed contact sets: no warm start (a hint does not carry across a change of contact set)");
+    const wbcqp_mix* mix = c.mix;
+    if (!mix) return fail(h, WBCQP_ERR_INVALID, "mix is NULL");
+    if (mix->n_slots < 1 || mix->n_slots > kMaxGroups) return fail(h, WBCQP_ERR_INVALID, "mix: n_slots must be in [1, 8]");
+    if (!mix->slots || !mix->w) return fail(h, WBCQP_ERR_INVALID, "mix: slots / w is NULL");
+    const Slot* s0 = nullptr;
+    for (int k = 0; k < mix->n_slots; ++k) {
+        const int sl = mix->slots[k];
+        if (sl < 0 || sl >= WBCQP_MAX_STRUCTURES || !h->slots[sl].set || !h->slots[sl].has_model)
+            return fail(h, WBCQP_ERR_INVALID, "mix: slot " + std::to_string(sl) + " has no structure and model (wbcqp_set_model)");
+        const Slot& s = h->slots[sl];
+        if (!s0) { s0 = &s; continue; }
+        if (s.tree != s0->tree || s.terms.nq != s0->terms.nq || s.terms.nv != s0->terms.nv || s.terms.na != s0->terms.na)
+            return fail(h, WBCQP_ERR_INVALID, "mix: slot " + std::to_string(sl) + " has another robot model than slot " + std::to_string(mix->slots[0]));
+        if (s.terms.nref != s0->terms.nref || s.terms.dt != s0->terms.dt)
+            return fail(h, WBCQP_ERR_INVALID, "mix: slot " + std::to_string(sl) + " has another reference length (nref) or dt than slot " + std::to_string(mix->slots[0]));
+    }
+    if (c.batch < 0 || c.n_ticks < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch / n_ticks");
+    if (c.batch == 0 || c.n_ticks == 0) return WBCQP_OK;
+    if (!c.which) return fail(h, WBCQP_ERR_INVALID, "which / schedule is NULL");
+    bool used[kMaxGroups] = {};
+    const size_t N = (size_t)c.batch * c.n_ticks;
+    for (size_t e = 0; e < N; ++e) {
+        const int k = c.which[e];
+        if (k < 0 || k >= mix->n_slots)
+            return fail(h, WBCQP_ERR_INVALID, "which / schedule entry " + std::to_string(e) + " = " + std::to_string(k) + " is outside [0, n_slots)");
+        used[k] = true;
+    }
+    for (int k = 0; k < mix->n_slots; ++k) {
+        if (!used[k]) continue;
+        const Slot& s = h->slots[mix->slots[k]];
+        if (s.layout.len_w > 0 && !mix->w[k]) return fail(h, WBCQP_ERR_INVALID, "mix: w of slot " + std::to_string(mix->slots[k]) + " is NULL and instances use it");
+        if (s.layout.len_tlb > 0 && (!mix->tlb || !mix->tub)) return fail(h, WBCQP_ERR_INVALID, "mix: tlb / tub are required (a slot in use has actuation bounds)");
+    }
+    if (!c.state.q || !c.state.v || (s0->terms.nref > 0 && !c.state.ref)) return fail(h, WBCQP_ERR_INVALID, "state arrays q / v / ref are required");
+    if (!c.out.x || !c.out.status || !c.out.iters || (s0->terms.na > 0 && !c.out.tau) || !c.q_next || !c.v_next)
+        return fail(h, WBCQP_ERR_INVALID, "x, tau, status, iters, q_next, v_next are required");
+    return WBCQP_OK;
+}
+
+// one set's arrays in the record scratch of a tick: the rows kernel's output (9), the gathered w, tlb, tub, the solve's outputs
+enum { MR_M, MR_h, MR_A, MR_b1, MR_Ac, MR_bc, MR_blb, MR_bub, MR_Acop, MR_w, MR_tlb, MR_tub, MR_x, MR_tau, MR_obj, MR_status, MR_iters, MR_nact, MR_amask, MR_N };
+
+size_t mix_group_layout(const Slot& s, int count, size_t es, size_t off[MR_N])
+{
+    const wbcqp_layout& L = s.layout;
+    const size_t len[MR_N] = {(size_t)L.len_M * es, (size_t)L.len_h * es, (size_t)L.len_A * es, (size_t)L.len_b1 * es, (size_t)L.len_Ac * es,
+                              (size_t)L.len_bc * es, (size_t)L.len_blb * es, (size_t)L.len_bub * es, (size_t)L.len_Acop * es, (size_t)L.len_w * es,
+                              (size_t)L.len_tlb * es, (size_t)L.len_tub * es, (size_t)L.n * es, (size_t)s.host.na * es, es, 4, 4, 4, 32};
+    size_t bytes = 0;
+    for (int f = 0; f < MR_N; ++f) {
+        off[f] = bytes;
+        bytes += ((size_t)count * len[f] + 255) & ~(size_t)255;
+    }
+    return bytes;
+}
+
+template <typename TI>
+int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
+{
+    const wbcqp_mix& mix = *c.mix;
+    const int B = c.batch, K = mix.n_slots;
+    const Slot& s0 = h->slots[mix.slots[0]];
+    const TermsDev& T0 = s0.terms;
+    constexpr size_t es = sizeof(TI);
+    int ldx = 0;
+    for (int k = 0; k < K; ++k) ldx = std::max(ldx, h->slots[mix.slots[k]].layout.n);
+    // the plan: per tick, the instances of set 0, then of set 1, ... (ascending within a set), and the sets' counts
+    std::vector<int> counts((size_t)c.n_ticks * K, 0);
+    for (int t = 0; t < c.n_ticks; ++t)
+        for (int i = 0; i < B; ++i) ++counts[(size_t)t * K + c.which[(size_t)t * B + i]];
+    size_t rec_bytes = 0;
+    for (int t = 0; t < c.n_ticks; ++t) {
+        size_t bytes = 0, off[MR_N];
+        for (int k = 0; k < K; ++k)
+            if (counts[(size_t)t * K + k]) bytes += mix_group_layout(h->slots[mix.slots[k]], counts[(size_t)t * K + k], es, off);
+        rec_bytes = std::max(rec_bytes, bytes);
+    }
+    const size_t plan_ints = (size_t)c.n_ticks * B;
+    const size_t qb = ((size_t)T0.nq * B * es + 255) & ~(size_t)255, vb = ((size_t)T0.nv * B * es + 255) & ~(size_t)255;
+    const size_t state_bytes = c.n_ticks > 1 ? 2 * (qb + vb) : 0;
+    wbcqp_handle::MixPlan& P = h->mix_plan[h->mix_next];
+    h->mix_next = (h->mix_next + 1) % 4;
+    if (P.used) HIP_TRY(h, hipEventSynchronize(P.done)); // (the call that last filled this entry: four calls ago)
+    if (!P.done) HIP_TRY(h, hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
+    const bool had_mix = h->mix_done != nullptr;
+    if (!h->mix_done) HIP_TRY(h, hipEventCreateWithFlags(&h->mix_done, hipEventDisableTiming));
+    if (P.cap < plan_ints || h->mix_rec.bytes < rec_bytes || h->mix_state.bytes < state_bytes) {
+        // first call of a larger shape: nothing of an earlier call may still be running on what is replaced
+        HIP_TRY(h, hipDeviceSynchronize());
+        if (P.cap < plan_ints) {
+            if (P.dev) (void)hipFree(P.dev);
+            P.dev = nullptr;
+            P.cap = 0;
+            HIP_TRY(h, hipMalloc(&P.dev, plan_ints * sizeof(int)));
+            P.cap = plan_ints;
+        }
+        int rc = ensure(h, h->mix_rec, rec_bytes);
+        if (rc != WBCQP_OK) return rc;
+        if (state_bytes) {
+            rc = ensure(h, h->mix_state, state_bytes);
+            if (rc != WBCQP_OK) return rc;
+        }
+    }
+    int rc = ensure_pinned(h, P.pin, plan_ints * sizeof(int));
+    if (rc != WBCQP_OK) return rc;
+    int* perm_h = static_cast<int*>(P.pin.host);
+    for (int t = 0; t < c.n_ticks; ++t) {
+        int pos[kMaxGroups];
+        for (int k = 0, o = 0; k < K; ++k) { pos[k] = o; o += counts[(size_t)t * K + k]; }
+        for (int i = 0; i < B; ++i) perm_h[(size_t)t * B + pos[c.which[(size_t)t * B + i]]++] = i;
+    }
+    // the force blocks' factor cache of every slot of the mix, before the first tick (a cache made in the middle of a roll-out would wait for it)
+    hipStreamCaptureStatus cst = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(sm, &cst) != hipSuccess) (void)hipGetLastError();
+    for (int k = 0; k < K && cst == hipStreamCaptureStatusNone; ++k) {
+        Slot& s = h->slots[mix.slots[k]];
+        const bool wave_small = !(h->flags & WBCQP_FLAG_WORKGROUP_PER_QP) && !h->dbg && s.small;
+        if (s.host_cp.compact && s.ffc_dev && !s.ffc_built && !h->capturing && !wave_small && mix.w[k]) {
+            rc = build_ffcache(h, s, mix.w[k], sm);
+            if (rc != WBCQP_OK) return rc;
+        }
+    }
+    if (had_mix) HIP_TRY(h, hipStreamWaitEvent(sm, h->mix_done, 0)); // the previous mixed call is done with the records and the ping-pong
+    HIP_TRY(h, hipMemcpyAsync(P.dev, perm_h, plan_ints * sizeof(int), hipMemcpyHostToDevice, sm));
+    P.used = true;
+    char* rec = static_cast<char*>(h->mix_rec.dev);
+    char* stt = static_cast<char*>(h->mix_state.dev);
+    const TI* q = static_cast<const TI*>(c.state.q);
+    const TI* v = static_cast<const TI*>(c.state.v);
+    for (int t = 0; t < c.n_ticks; ++t) {
+        const bool last = t + 1 == c.n_ticks;
+        TI* qn = last ? static_cast<TI*>(c.q_next) : reinterpret_cast<TI*>(stt + (t & 1) * qb);
+        TI* vn = last ? static_cast<TI*>(c.v_next) : reinterpret_cast<TI*>(stt + 2 * qb + (t & 1) * vb);
+        const int* perm = P.dev + (size_t)t * B;
+        wbcqp_group groups[kMaxGroups];
+        MixedScatterArgs<TI> sa{};
+        int ng = 0, o = 0;
+        size_t base = 0;
+        for (int k = 0; k < K; ++k) {
+            const int cnt = counts[(size_t)t * K + k];
+            if (cnt == 0) continue;
+            const Slot& s = h->slots[mix.slots[k]];
+            size_t off[MR_N];
+            const size_t bytes = mix_group_layout(s, cnt, es, off);
+            char* g0 = rec + base;
+            base += bytes;
+            auto at = [&](int f) -> TI* { return reinterpret_cast<TI*>(g0 + off[f]); };
+            const bool tl = s.layout.len_tlb > 0;
+            TermsGatherArgs<TI> a{};
+            a.T = s.terms; a.batch = cnt; a.dbg = h->dbg;
+            a.q = q; a.v = v; a.ref = static_cast<const TI*>(c.state.ref) + (size_t)t * B * T0.nref;
+            a.M = at(MR_M); a.h = at(MR_h); a.A = at(MR_A); a.b1 = at(MR_b1); a.Ac = at(MR_Ac); a.bc = at(MR_bc); a.blb = at(MR_blb); a.bub = at(MR_bub);
+            a.Acop = at(MR_Acop);
+            a.momentum = last ? static_cast<TI*>(c.state.momentum) : nullptr;
+            a.perm = perm + o;
+            a.w_src = static_cast<const TI*>(mix.w[k]); a.w_dst = at(MR_w); a.n_tasks = s.layout.len_w;
+            a.tlb_src = tl ? static_cast<const TI*>(mix.tlb) : nullptr; a.tub_src = tl ? static_cast<const TI*>(mix.tub) : nullptr;
+            a.tlb_dst = tl ? at(MR_tlb) : nullptr; a.tub_dst = tl ? at(MR_tub) : nullptr;
+            hipLaunchKernelGGL((terms_kernel<TI, true>), dim3(cnt), dim3(kTermsThreads), s.terms.lds_doubles * 8, sm, a);
+            HIP_TRY(h, hipGetLastError());
+            wbcqp_group& G = groups[ng];
+            G.slot = mix.slots[k];
+            G.batch = cnt;
+            G.in = wbcqp_inputs{a.M, a.h, a.A, a.b1, a.Ac, a.bc, a.blb, a.bub, a.tlb_dst, a.tub_dst, a.w_dst, s.layout.len_Acop ? a.Acop : nullptr};
+            G.out = wbcqp_outputs{at(MR_x), at(MR_tau), reinterpret_cast<int32_t*>(g0 + off[MR_status]), reinterpret_cast<int32_t*>(g0 + off[MR_iters]),
+                                  at(MR_obj), reinterpret_cast<int32_t*>(g0 + off[MR_nact]), reinterpret_cast<uint32_t*>(g0 + off[MR_amask])};
+            MixedGroupOut<TI>& M = sa.g[ng];
+            M.x = at(MR_x); M.tau = at(MR_tau); M.objective = at(MR_obj);
+            M.status = G.out.status; M.iters = G.out.iters; M.n_active = G.out.n_active; M.amask = G.out.active_mask;
+            M.n = s.layout.n;
+            sa.off[ng] = o;
+            o += cnt;
+            ++ng;
+        }
+        sa.off[ng] = o;
+        rc = wbcqp_solve_ragged(h, ng, groups, sm);
+        if (rc != WBCQP_OK) return rc;
+        sa.n_groups = ng; sa.total = B; sa.nv = T0.nv; sa.na = T0.na; sa.floating_base = T0.floating_base; sa.ldx = ldx;
+        sa.perm = perm; sa.dt = c.dt; sa.q = q; sa.v = v; sa.q_next = qn; sa.v_next = vn;
+        sa.q_solver = last ? static_cast<TI*>(c.q_solver) : nullptr;
+        if (last) { // (the outputs of the last tick only: what a roll-out reports)
+            sa.x = static_cast<TI*>(c.out.x); sa.tau = static_cast<TI*>(c.out.tau); sa.objective = static_cast<TI*>(c.out.objective);
+            sa.status = c.out.status; sa.iters = c.out.iters; sa.n_active = c.out.n_active; sa.amask = c.out.active_mask;
+        }
+        sa.iters_sum = c.iters_sum; sa.ticks_ok = c.ticks_ok; sa.first = t == 0 ? 1 : 0;
+        hipLaunchKernelGGL(mixed_integrate_kernel<TI>, dim3((B + 3) / 4), dim3(256), 0, sm, sa);
+        HIP_TRY(h, hipGetLastError());
+        q = qn;
+        v = vn;
+    }
+    HIP_TRY(h, hipEventRecord(P.done, sm));
+    HIP_TRY(h, hipEventRecord(h->mix_done, sm));
+    return WBCQP_OK;
+}
+
+int mixed_call(wbcqp_handle* h, const MixCall& c, void* stream)
+{
+    int rc = check_mix(h, c);
+    if (rc != WBCQP_OK || c.batch == 0 || c.n_ticks == 0) return rc;
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    return h->dtype == WBCQP_F64 ? mixed_run<double>(h, c, sm) : mixed_run<float>(h, c, sm);
+}
+
+} // namespace
+
+extern "C" {
+
+int wbcqp_tick_mixed(wbcqp_handle* h, const wbcqp_mix* mix, int batch, const int32_t* which, const wbcqp_mixed_io* io, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
+    const MixCall c{mix, batch, 1, which, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, nullptr, nullptr};
+    return mixed_call(h, c, stream);
+}
+
+int wbcqp_rollout_mixed(wbcqp_handle* h, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule, const wbcqp_rollout_io* io, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
+    const MixCall c{mix, batch, n_ticks, schedule, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, io->iters_sum, io->ticks_ok};
+    return mixed_call(h, c, stream);
 }
 
 int wbcqp_tick_host(wbcqp_handle* h, int slot, int batch, const wbcqp_tick_io* io)

@@ -181,4 +181,63 @@ __global__ __launch_bounds__(256) void integrate_kernel(int batch, int nv, int f
 }
 
 #endif // __HIPCC__
+
+// wbcqp_tick_mixed / wbcqp_rollout_mixed: the solve's outputs of every contact-set group of one tick (rows of the group, in the
+// group's own layout) back to instance order, and the integration of each instance from its group's x.  Group g holds rows
+// [off[g], off[g + 1]) of the tick's permutation: perm[j] = the instance of row j (checked on the host).
+template <typename TI>
+struct MixedGroupOut {
+    const TI *x, *tau, *objective; // [count][n], [count][na], [count]
+    const int *status, *iters, *n_active;
+    const unsigned* amask;         // [count][8]
+    int n;
+};
+
+template <typename TI>
+struct MixedScatterArgs {
+    int n_groups, total, nv, na, floating_base, ldx;
+    int off[kMaxGroups + 1];
+    MixedGroupOut<TI> g[kMaxGroups];
+    const int* perm;
+    double dt;
+    const TI *q, *v;                       // [instances][nq], [instances][nv]: the state before the tick
+    TI *q_next, *v_next, *q_solver;        // q_solver may be null
+    TI *x, *tau, *objective;               // instance order (x: [instances][ldx], zero-padded past the group's n); null: not written
+    int *status, *iters, *n_active;
+    unsigned* amask;
+    int* iters_sum;                        // the roll-out's per-instance totals, or null
+    int* ticks_ok;
+    int first;                             // first tick of a roll-out: the totals start from zero
+};
+
+#ifdef __HIPCC__
+template <typename TI>
+__global__ __launch_bounds__(256) void mixed_integrate_kernel(const MixedScatterArgs<TI> a)
+{
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= a.total) return;
+    int gi = 0;
+    for (int k = 1; k < a.n_groups; ++k) gi = (j >= a.off[k]) ? k : gi;
+    const MixedGroupOut<TI>& G = a.g[gi];
+    const int r = j - a.off[gi], inst = a.perm[j];
+    const int st = G.status[r];
+    const bool ok = st == HQP_OPTIMAL;
+    if (lane == 0) {
+        if (a.iters_sum) a.iters_sum[inst] = (a.first ? 0 : a.iters_sum[inst]) + G.iters[r];
+        if (a.ticks_ok) a.ticks_ok[inst] = (a.first ? 0 : a.ticks_ok[inst]) + (ok ? 1 : 0);
+        if (a.status) a.status[inst] = st;
+        if (a.iters) a.iters[inst] = G.iters[r];
+        if (a.objective) a.objective[inst] = G.objective[r];
+        if (a.n_active) a.n_active[inst] = G.n_active[r];
+    }
+    if (a.x)
+        for (int e = lane; e < a.ldx; e += 64) a.x[(size_t)inst * a.ldx + e] = e < G.n ? G.x[(size_t)r * G.n + e] : (TI)0;
+    if (a.tau)
+        for (int e = lane; e < a.na; e += 64) a.tau[(size_t)inst * a.na + e] = G.tau[(size_t)r * a.na + e];
+    if (a.amask && lane < 8) a.amask[(size_t)inst * 8 + lane] = G.amask[(size_t)r * 8 + lane];
+    const int nq = a.floating_base ? a.nv + 1 : a.nv;
+    integrate_one<TI>(a.nv, a.floating_base, a.dt, a.q + (size_t)inst * nq, a.v + (size_t)inst * a.nv, G.x + (size_t)r * G.n, ok,
+                      a.q_next + (size_t)inst * nq, a.v_next + (size_t)inst * a.nv, a.q_solver ? a.q_solver + (size_t)inst * a.nv : nullptr, lane);
+}
+#endif // __HIPCC__
 } // namespace wbcqp

@@ -25,6 +25,8 @@
 
 #include "wbcqp_prims.hpp"
 
+#include <type_traits>
+
 namespace wbcqp {
 
 enum { J_FREEFLYER = 0, J_RX = 1, J_RY = 2, J_RZ = 3, J_PX = 4, J_PY = 5, J_PZ = 6 };
@@ -78,6 +80,20 @@ struct TermsArgs {
     int batch;
     long long* dbg; // per-instance phase cycle counters, only written by the WBCQP_STAMPS diagnostic build
 };
+
+// the rows kernel on one contact-set group of a mixed tick (wbcqp_tick_mixed): q, v, ref and momentum are indexed by INSTANCE, the
+// record by the group's row; perm[i] = the instance of row i (checked on the host: every entry in [0, batch of the call))
+template <typename TI>
+struct TermsGatherArgs : TermsArgs<TI> {
+    const int* perm;
+    const TI* w_src; // [instances][n_tasks] the slot's weights, by instance
+    TI* w_dst;       // [group][n_tasks]
+    int n_tasks;
+    const TI *tlb_src, *tub_src; // [instances][na], or null (no actuation bounds)
+    TI *tlb_dst, *tub_dst;       // [group][na]
+};
+template <typename TI, bool GATHER>
+using TermsKernelArgs = std::conditional_t<GATHER, TermsGatherArgs<TI>, TermsArgs<TI>>;
 
 #ifdef __HIPCC__
 
@@ -869,14 +885,26 @@ __device__ __forceinline__ void terms_one(const TermsArgs<TI>& args, const TI* g
 #endif
 }
 
-template <typename TI>
-__global__ __launch_bounds__(kTermsThreads, 4) void terms_kernel(const TermsArgs<TI> args)
+template <typename TI, bool GATHER = false>
+__global__ __launch_bounds__(kTermsThreads, 4) void terms_kernel(const TermsKernelArgs<TI, GATHER> args)
 {
     extern __shared__ double lds[];
     if ((int)blockIdx.x >= args.batch) return;
-    const int inst = (int)blockIdx.x;
+    const int rinst = (int)blockIdx.x;
+    int inst = rinst;
+    if constexpr (GATHER) {
+        // one group of a mixed tick: workgroup i reads instance perm[i] (state, references, its slot's weights and the torque limits)
+        // and writes row i of the group's record; the momentum goes back to the instance
+        inst = args.perm[rinst];
+        for (int e = (int)threadIdx.x; e < args.n_tasks; e += kTermsThreads) args.w_dst[(size_t)rinst * args.n_tasks + e] = args.w_src[(size_t)inst * args.n_tasks + e];
+        if (args.tlb_dst)
+            for (int e = (int)threadIdx.x; e < args.T.na; e += kTermsThreads) {
+                args.tlb_dst[(size_t)rinst * args.T.na + e] = args.tlb_src[(size_t)inst * args.T.na + e];
+                args.tub_dst[(size_t)rinst * args.T.na + e] = args.tub_src[(size_t)inst * args.T.na + e];
+            }
+    }
     terms_one<TI>(args, args.q + (size_t)inst * args.T.nq, args.v + (size_t)inst * args.T.nv, args.ref + (size_t)inst * args.T.nref,
-                  args.momentum ? args.momentum + (size_t)inst * 6 : nullptr, inst, inst, lds, (int)threadIdx.x);
+                  args.momentum ? args.momentum + (size_t)inst * 6 : nullptr, inst, rinst, lds, (int)threadIdx.x);
 }
 
 #endif // __HIPCC__

@@ -731,3 +731,139 @@ def random_stack(model: Model, seed: int, n_contacts: int = 2) -> Tuple[Structur
     level0 = [(S.INEQ_BOUNDS, 0)] + [(S.INEQ_FORCE, c) for c in range(len(contacts))]
     st = S._mk("stack_" + model.name, model.nv, model.na, contacts, dense, None, sc, True, False, level0)
     return st, stack
+
+
+# ---- a fleet in different contact sets (wbcqp_tick_mixed / wbcqp_rollout_mixed) ---------------------------------------
+
+def contact_set_maps(model: Model, stack: Sequence[dict], sets: Dict[str, Tuple[Structure, Sequence[str]]], dt: float = 1e-3) -> Dict[str, TaskMap]:
+    """Task maps of a stack's contact subsets, all on the FULL stack's reference layout: sets = {name: (structure, contact names kept)}.
+    A subset keeps the tasks of the stack and the contacts named; its contacts' references point at the offsets they have in the map of
+    the whole stack, and its nref is the whole stack's -- so one reference row serves every set (what wbcqp_tick_mixed needs; the
+    reference's remove_contact / add_contact change the QP, not the task references, pos_tracker.cpp:246-263)."""
+    contact_names = [n["name"] for n in stack if n["type"] == "contact"]
+    maps = {}
+    for name, (st, kept) in sets.items():
+        unknown = set(kept) - set(contact_names)
+        assert not unknown, unknown
+        sub = [n for n in stack if n["type"] != "contact" or n["name"] in kept]
+        maps[name] = build_taskmap(model, st, sub, dt)
+    # the whole stack's layout: the tasks' offsets come first (they do not depend on the contacts), then 24 per contact in stack order
+    some = next(iter(maps.values()))
+    c0 = some.posture_ref + (model.na if some.sel_col.size else 0)
+    full_off = {nm: c0 + 24 * i for i, nm in enumerate(contact_names)}
+    nref = c0 + 24 * len(contact_names)
+    for name, (st, kept) in sets.items():
+        tm = maps[name]
+        kept_in_order = [nm for nm in contact_names if nm in kept]
+        tm.contact_ref = np.array([full_off[nm] for nm in kept_in_order], dtype=np.int32)
+        tm.nref = nref
+        assert [b.ref for b in tm.blocks] == [b.ref for b in some.blocks] and tm.posture_ref == some.posture_ref
+    return maps
+
+
+def talos_contact_sets(model: Model, dt: float = 1e-3) -> Dict[str, Tuple[Structure, TaskMap]]:
+    """Talos's three contact sets under a walk: both feet, no left foot, no right foot (the single-support structure keeps ONE contact;
+    the stack without the right one has the same shape)."""
+    from . import structure as S
+    sets = {"both": (S.talos_structure(), ["contact_lfoot", "contact_rfoot"]),
+            "no_l": (S.talos_structure(single_support=True), ["contact_rfoot"]),
+            "no_r": (S.talos_structure(single_support=True), ["contact_lfoot"])}
+    maps = contact_set_maps(model, talos_stack(), sets, dt)
+    return {k: (sets[k][0], maps[k]) for k in sets}
+
+
+def icub_contact_sets(model: Model, dt: float = 1e-3) -> Dict[str, Tuple[Structure, TaskMap]]:
+    """iCub's: both feet, and one foot (the right one, as structure.icub_structure(single_support=True))."""
+    from . import structure as S
+    sets = {"both": (S.icub_structure(), ["contact_lfoot", "contact_rfoot"]), "no_l": (S.icub_structure(single_support=True), ["contact_rfoot"])}
+    maps = contact_set_maps(model, icub_stack(), sets, dt)
+    return {k: (sets[k][0], maps[k]) for k in sets}
+
+
+class WalkOnSpotPlan:
+    """humanoid::walk-on-spot (/root/reference/src/behaviors/humanoid/walk_on_spot.cpp) as a table, for a fleet whose instances start it
+    at different ticks.  The behaviour plays INIT (CoM over the right foot, traj_com_duration) once, then cycles LIFT_UP_LF, LIFT_DOWN_LF
+    (traj_foot_duration each), MOVE_COM_LEFT (com), LIFT_UP_RF, LIFT_DOWN_RF (foot), MOVE_COM_RIGHT (com); a phase lasts floor(T / dt)
+    ticks (trajectory_generator.hpp:73,152).  The left contact is removed on the first tick of LIFT_UP_LF and comes back on the last tick
+    of LIFT_DOWN_LF (walk_on_spot.cpp:165-184), the right one likewise.  Feet and CoM references are pose-only min-jerk samples (trajs.py);
+    the contacts' references are the feet's.  Instance i starts the behaviour offsets[i] ticks late and stands on both feet, on INIT's
+    first sample, until then.  `maps` = {"both", "no_l", "no_r"}: task maps on one reference layout (talos_contact_sets)."""
+
+    SETS = ("both", "no_l", "no_r")
+
+    def __init__(self, model: Model, maps: Dict[str, TaskMap], traj_com_duration: float, traj_foot_duration: float, step_height: float,
+                 lf: str = "leg_left_6_joint", rf: str = "leg_right_6_joint"):
+        from . import trajs
+        full = maps["both"]
+        self.dt = dt = full.dt
+        self.n_com = int(np.floor(traj_com_duration / dt))
+        self.n_foot = int(np.floor(traj_foot_duration / dt))
+        Rf0, pf0 = model.frame_placements(model.q0)
+        Rl, Rr = Rf0[model.frame(lf)], Rf0[model.frame(rf)]
+        lf_low, rf_low = pf0[model.frame(lf)].copy(), pf0[model.frame(rf)].copy()
+        up = np.array([0.0, 0.0, step_height])
+        com_init = model.com(model.q0)
+        com_lf = np.array([lf_low[0], lf_low[1], com_init[2]])
+        com_rf = np.array([rf_low[0], rf_low[1], com_init[2]])
+        nc, nf = self.n_com, self.n_foot
+        const = lambda p, n: np.tile(p, (n, 1))
+        mj = lambda a, b, n, T: trajs.min_jerk_trajectory(a, b, dt, T, 0)
+        Tc, Tf = traj_com_duration, traj_foot_duration
+        both, no_l, no_r = (self.SETS.index(s) for s in ("both", "no_l", "no_r"))
+        # (name, lf positions, rf positions, com, contact set per tick)
+        lift = lambda n, removed, land: np.array([removed] * (n - 1) + [both if land else removed])
+        phases = [("INIT", const(lf_low, nc), const(rf_low, nc), mj(com_init, com_rf, nc, Tc), np.full(nc, both)),
+                  ("LIFT_UP_LF", mj(lf_low, lf_low + up, nf, Tf), const(rf_low, nf), const(com_rf, nf), np.full(nf, no_l)),
+                  ("LIFT_DOWN_LF", mj(lf_low + up, lf_low, nf, Tf), const(rf_low, nf), const(com_rf, nf), lift(nf, no_l, True)),
+                  ("MOVE_COM_LEFT", const(lf_low, nc), const(rf_low, nc), mj(com_rf, com_lf, nc, Tc), np.full(nc, both)),
+                  ("LIFT_UP_RF", const(lf_low, nf), mj(rf_low, rf_low + up, nf, Tf), const(com_lf, nf), np.full(nf, no_r)),
+                  ("LIFT_DOWN_RF", const(lf_low, nf), mj(rf_low + up, rf_low, nf, Tf), const(com_lf, nf), lift(nf, no_r, True)),
+                  ("MOVE_COM_RIGHT", const(lf_low, nc), const(rf_low, nc), mj(com_lf, com_rf, nc, Tc), np.full(nc, both))]
+        self.phase_names = [p[0] for p in phases]
+        self.phase_len = [len(p[4]) for p in phases]
+        self.lf_pos = np.concatenate([p[1] for p in phases])
+        self.rf_pos = np.concatenate([p[2] for p in phases])
+        self.com = np.concatenate([p[3] for p in phases])
+        self.set_of = np.concatenate([p[4] for p in phases]).astype(np.int32)
+        self.phase_of = np.concatenate([np.full(len(p[4]), i) for i, p in enumerate(phases)])
+        self.cycle = sum(self.phase_len[1:])
+        self.lf_low, self.rf_low, self.step_height = lf_low, rf_low, step_height
+        # one reference row: the references of a fresh controller, then per tick the feet, the CoM and the contacts
+        self.base = sample_states(model, full, 1, 0, q_noise=0.0, v_noise=0.0, ref_noise=0.0)["ref"][0]
+        blk = {b.name: b for b in full.blocks}
+        self.lf_ref, self.rf_ref = blk["lf"].ref, blk["rf"].ref
+        self.com_ref = next(b.ref for b in full.blocks if b.kind == T_COM)
+        self.Rl, self.Rr = Rl, Rr
+        cl = [c for c in range(full.ncontact) if full.contact_frame[c] == model.frame(lf)]
+        cr = [c for c in range(full.ncontact) if full.contact_frame[c] == model.frame(rf)]
+        self.cl_ref, self.cr_ref = int(full.contact_ref[cl[0]]), int(full.contact_ref[cr[0]])
+        self.nref = full.nref
+
+    def index(self, tau: np.ndarray) -> np.ndarray:
+        """Behaviour tick tau (< 0: not started) -> row of the table."""
+        tau = np.asarray(tau)
+        n0 = self.phase_len[0]
+        return np.where(tau < 0, 0, np.where(tau < n0, tau, n0 + (tau - n0) % max(self.cycle, 1)))
+
+    def plan(self, offsets: Sequence[int], start: int, n_ticks: int) -> Tuple[np.ndarray, np.ndarray]:
+        """Ticks [start, start + n_ticks) of the fleet: schedule [n_ticks][B] (index into SETS) and ref [n_ticks][B][nref]."""
+        offsets = np.asarray(offsets, dtype=np.int64)
+        tau = np.arange(start, start + n_ticks)[:, None] - offsets[None, :]
+        idx = self.index(tau)
+        schedule = self.set_of[idx]
+        ref = np.broadcast_to(self.base, idx.shape + (self.nref,)).copy()
+        for off, R, P in ((self.lf_ref, self.Rl, self.lf_pos), (self.rf_ref, self.Rr, self.rf_pos),
+                          (self.cl_ref, self.Rl, self.lf_pos), (self.cr_ref, self.Rr, self.rf_pos)):
+            ref[..., off:off + 24] = 0.0
+            ref[..., off:off + 12] = self._se3(R, P[idx])
+        ref[..., self.com_ref:self.com_ref + 9] = 0.0
+        ref[..., self.com_ref:self.com_ref + 3] = self.com[idx]
+        return schedule.astype(np.int32), ref
+
+    @staticmethod
+    def _se3(R: np.ndarray, p: np.ndarray) -> np.ndarray:
+        """se3_ref(R, p) for an array of positions p [..., 3] under one rotation."""
+        out = np.empty(p.shape[:-1] + (12,))
+        out[..., :3] = p
+        out[..., 3:] = se3_ref(R, np.zeros(3))[3:]
+        return out
