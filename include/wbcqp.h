@@ -49,7 +49,8 @@ extern "C" {
  *        and one synchronisation of the launch's stream, once per wbcqp_set_structure; never inside a stream capture) -- later QPs that carry those weights
  *        take the factor from there, others compute it as before: the same bits either way (env WBCQP_DEBUG_NO_FFCACHE=1, read at wbcqp_create, turns it off).
  *        Added without a change of version: wbcqp_mix, wbcqp_mixed_io, wbcqp_tick_mixed and wbcqp_rollout_mixed (instances of one robot model in
- *        different contact sets, one call)
+ *        different contact sets, one call); wbcqp_trace, wbcqp_task_costs, wbcqp_rollout_traced and wbcqp_rollout_mixed_traced (per-task costs on
+ *        the device, per-tick results of a roll-out)
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -541,6 +542,48 @@ int wbcqp_tick_mixed(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, cons
  * Bit for bit n_ticks calls of wbcqp_tick_mixed with q_next / v_next fed back. */
 int wbcqp_rollout_mixed(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule, const wbcqp_rollout_io* io,
                         void* stream);
+
+/* ---- Per-task costs and per-tick traces ----
+ * The cost of level-1 task t of an instance (the index space of wbcqp_inputs.w, n_tasks entries) is
+ *     cost[t] = || A_t x - b_t ||_2
+ * over the rows of task t exactly as they enter H = sum_t w_t A_t' A_t + hessian_reg I and g = -sum_t w_t A_t' b_t:
+ *     dense row r (dense_row_task):    A[r] . dv - b1[r]
+ *     selection row r (posture):       dv[sel_col[r]] - b1[n_dense + r]
+ *     force regularisation, contact c: F_c f_c - b1[n_dense + n_sel + 6 c ..], F = diag(w_f) T (forcereg_mat)
+ *     torque task row j:               acteq_scale[j] tau[acteq_joint[j]] - b1[..]   (the row scale_j [M_a | -J_a'] x = scale_j tau_ref_j -
+ *                                      scale_j h_a(joint_j) with the decoded tau = M_a dv + h_a - J_a' f)
+ *     cop task:                        Acop f - b1[..]
+ * For the dense and selection rows this is the reference's Controller::cost(task) (controller.hpp:148-152: the norm of A ddq - b), what
+ * `-l cost_<task>` logs every tick (src/robot_dart/talos.cpp:504-505).  Identity: objective = 1/2 sum_t w_t (cost_t^2 - ||b_t||^2) +
+ * 1/2 hessian_reg ||x||^2, b_t the right-hand side as it enters g (b1; on the torque rows scale_j tau_ref_j - scale_j h_a(joint_j)).  Costs are formed from x and tau as written, whatever the status: the caller masks by status.  One workgroup per
+ * instance, no atomics, a fixed order of summation: the same bits from run to run and between the three entry points below (F32 handles
+ * read float, sum in double, write float). */
+typedef struct {
+    int32_t stride;      /* tick t (0-based) is recorded when (t + 1) % stride == 0: n_rec = n_ticks / stride entries; >= 1 */
+    void* q;             /* [n_rec][batch][nq]  the state AFTER the recorded tick (each field may be NULL: not recorded) */
+    void* v;             /* [n_rec][batch][nv] */
+    void* x;             /* [n_rec][batch][ldx] ldx = n (one slot) / the largest n over the mix's slots, as wbcqp_mixed_io.out.x */
+    void* tau;           /* [n_rec][batch][na] */
+    int32_t* status;     /* [n_rec][batch] */
+    int32_t* iters;      /* [n_rec][batch] */
+    void* objective;     /* [n_rec][batch] */
+    void* cost;          /* [n_rec][batch][ldc] ldc = n_tasks (one slot) / the largest n_tasks over the mix's slots; zero past the own slot's n_tasks */
+} wbcqp_trace;
+
+/* The costs of a solved record: rows as given to wbcqp_solve_batch (A, b1 and Acop are read), x [batch][n] and tau [batch][na] as it wrote
+ * them (tau may be NULL when the stack has no torque task); cost [batch][n_tasks].  DEVICE pointers, asynchronous on `stream`. */
+int wbcqp_task_costs(wbcqp_handle* handle, int slot, int batch, const wbcqp_inputs* rows, const void* x, const void* tau, void* cost,
+                     void* stream);
+/* wbcqp_rollout / wbcqp_rollout_mixed that also keep every stride-th tick's results in `trace` (DEVICE pointers).  trace == NULL, or one
+ * whose fields are all NULL, is the untraced call.  The outputs of io, iters_sum and ticks_ok are those of the untraced call bit for bit;
+ * trace entry r is what (r + 1) stride calls of wbcqp_tick / wbcqp_tick_mixed leave for that tick (q_next, v_next, x, tau, status, iters,
+ * objective) and its cost row is wbcqp_task_costs on that tick's record.  The solve and the integration of a recorded tick write straight
+ * into the trace (a recorded last tick is copied there from io).  Refused with WBCQP_ERR_INVALID before anything is launched, besides
+ * what the untraced call refuses: stride < 1, a cost without a tau (a stack with a torque task, trace->tau and io->out.tau NULL). */
+int wbcqp_rollout_traced(wbcqp_handle* handle, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_trace* trace,
+                         void* stream);
+int wbcqp_rollout_mixed_traced(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule,
+                               const wbcqp_rollout_io* io, const wbcqp_trace* trace, void* stream);
 
 /* The same sequence captured once into a HIP graph and replayed: one graph launch per tick instead of four kernel
  * launches (what matters when the batch is small -- one robot at 1 kHz is the reference's own use case).  The graph is

@@ -144,7 +144,7 @@ def check_resources(usage: dict) -> None:
         raise RuntimeError("kernel-resource remarks not understood: %d solve_queue_kernel entries among %d kernels -- the build's register checks would "
                            "pass vacuously; refuse to ship" % (len(solve), len(usage)))
     for name, u in usage.items():
-        if ("solve_kernel" in name or "solve_queue_kernel" in name or "terms_kernel" in name or "integrate_kernel" in name) and (u.get("AGPRs", 0) != 0 or u.get("ScratchSize [bytes/lane]", 0) != 0 or u.get("VGPRs Spill", 0) != 0):
+        if ("solve_kernel" in name or "solve_queue_kernel" in name or "terms_kernel" in name or "integrate_kernel" in name or "task_costs_kernel" in name) and (u.get("AGPRs", 0) != 0 or u.get("ScratchSize [bytes/lane]", 0) != 0 or u.get("VGPRs Spill", 0) != 0):
             raise RuntimeError("%s: AGPRs %s, scratch %s B/lane, VGPR spills %s -- refuse to ship (see the comment in build.py)" %
                                (name, u.get("AGPRs"), u.get("ScratchSize [bytes/lane]"), u.get("VGPRs Spill")))
         # two workgroups per CU is what the queue kernels are sized and measured for (four waves each, one per SIMD: two waves per SIMD)

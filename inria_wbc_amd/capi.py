@@ -29,7 +29,8 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_allgather_tau", "wbcqp_integrate", "wbcqp_integrate_host", "wbcqp_set_model", "wbcqp_check_model", "wbcqp_problem_data",
            "wbcqp_problem_data_host", "wbcqp_tick", "wbcqp_tick_host", "wbcqp_tick_graph_create", "wbcqp_tick_graph_launch", "wbcqp_tick_graph_destroy",
            "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout",
-           "wbcqp_tick_mixed", "wbcqp_rollout_mixed")
+           "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced")
+TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
 
 c_i32_p = C.POINTER(C.c_int32)
@@ -133,6 +134,10 @@ class CMixedIO(C.Structure):
 _lib = None
 
 
+class CTrace(C.Structure):
+    _fields_ = [("stride", C.c_int32)] + [(k, C.c_void_p) for k in TRACE_FIELDS]
+
+
 def load_library(path: Optional[str] = None):
     """Loads libwbcqp.so -- after torch, when torch is installed: the library links libamdhip64.so.7, and a process in which it comes FIRST gets
     /opt/rocm's HIP runtime while a later `import torch` brings torch's bundled one.  Two runtimes on one GPU work, but the first one then answers
@@ -177,6 +182,10 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_tick_graph_destroy.argtypes = [C.c_void_p, C.c_void_p]
     lib.wbcqp_tick_mixed.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, c_i32_p, C.POINTER(CMixedIO), C.c_void_p]
     lib.wbcqp_rollout_mixed.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, c_i32_p, C.POINTER(CRolloutIO), C.c_void_p]
+    lib.wbcqp_task_costs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wbcqp_rollout_traced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CTrace), C.c_void_p]
+    lib.wbcqp_rollout_mixed_traced.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, c_i32_p, C.POINTER(CRolloutIO), C.POINTER(CTrace),
+                                               C.c_void_p]
     _lib = lib
     return lib
 
@@ -507,6 +516,60 @@ class Handle:
         io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
         self._check(self.lib.wbcqp_rollout_mixed(self._h, C.byref(mix), int(B), int(K), schedule.ctypes.data_as(c_i32_p), C.byref(io),
                                                  C.c_void_p(stream)))
+        del keep
+
+    def task_costs(self, slot: int, batch: int, rows: Dict[str, "object"], x, tau, cost, stream: int = 0):
+        """Per-task costs ||A_t x - b_t|| of a solved record (wbcqp_task_costs), device tensors: rows (A, b1, Acop read) as given to
+        solve_batch, x [B, n], tau [B, na] (may be None without a torque task), cost [B, n_tasks] written."""
+        cin = CInputs()
+        for k in ("A", "b1", "Acop"):
+            setattr(cin, k, self._ptr(rows.get(k)))
+        self._check(self.lib.wbcqp_task_costs(self._h, slot, batch, C.byref(cin), self._ptr(x), self._ptr(tau), self._ptr(cost),
+                                              C.c_void_p(stream)))
+
+    @staticmethod
+    def _trace(trace, stride: int):
+        """wbcqp_trace from a dict of device tensors (any of TRACE_FIELDS; a missing one is not recorded), or None: no trace."""
+        if trace is None:
+            return None
+        ct = CTrace()
+        ct.stride = int(stride)
+        for k in TRACE_FIELDS:
+            setattr(ct, k, Handle._ptr(trace.get(k)))
+        return C.byref(ct)
+
+    def rollout_traced(self, slot: int, batch: int, n_ticks: int, state, limits, out, q_next, v_next, dt: float, trace=None, stride: int = 1,
+                       q_solver=None, iters_sum=None, ticks_ok=None, stream: int = 0):
+        """rollout() that also keeps every stride-th tick's results (wbcqp_rollout_traced).  trace: dict of device tensors, q [n_rec, B, nq],
+        v [n_rec, B, nv], x [n_rec, B, n], tau [n_rec, B, na], status / iters [n_rec, B] int32, objective [n_rec, B], cost [n_rec, B, n_tasks]
+        (n_rec = n_ticks // stride); a field left out is not recorded; trace=None is rollout()."""
+        st = self._structs[slot]
+        io = CRolloutIO()
+        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr(), self._ptr(state.get("momentum")))
+        io.tlb = self._ptr(limits.get("tlb")) if st.act_bounds else None
+        io.tub = self._ptr(limits.get("tub")) if st.act_bounds else None
+        io.w = self._ptr(limits.get("w"))
+        io.out = self._outs(out)
+        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
+        io.dt = float(dt)
+        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
+        self._check(self.lib.wbcqp_rollout_traced(self._h, slot, batch, n_ticks, C.byref(io), self._trace(trace, stride), C.c_void_p(stream)))
+
+    def rollout_mixed_traced(self, slots: Sequence[int], schedule, state, w: Sequence, out, q_next, v_next, dt: float, trace=None, stride: int = 1,
+                             tlb=None, tub=None, q_solver=None, iters_sum=None, ticks_ok=None, stream: int = 0):
+        """rollout_mixed() that also keeps every stride-th tick's results (wbcqp_rollout_mixed_traced); trace as for rollout_traced, with
+        x [n_rec, B, max n] and cost [n_rec, B, max n_tasks] over the slots (zero past an instance's own slot's n / n_tasks)."""
+        schedule = np.ascontiguousarray(schedule, dtype=np.int32)
+        K, B = schedule.shape
+        mix, keep = self._mix(slots, w, tlb, tub)
+        io = CRolloutIO()
+        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), self._ptr(state.get("ref")), self._ptr(state.get("momentum")))
+        io.out = self._outs(out)
+        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
+        io.dt = float(dt)
+        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
+        self._check(self.lib.wbcqp_rollout_mixed_traced(self._h, C.byref(mix), int(B), int(K), schedule.ctypes.data_as(c_i32_p), C.byref(io),
+                                                        self._trace(trace, stride), C.c_void_p(stream)))
         del keep
 
     def tick_host(self, slot: int, q: np.ndarray, v: np.ndarray, ref: np.ndarray, tlb, tub, w, dt: float, want_rows: bool = False):

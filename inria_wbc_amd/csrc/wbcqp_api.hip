@@ -8,6 +8,7 @@
 #include "wbcqp_terms.hpp"
 #include "wbcqp_dense.hpp"
 #include "wbcqp_small.hpp"
+#include "wbcqp_costs.hpp"
 
 #include "../../include/wbcqp.h"
 
@@ -675,6 +676,42 @@ int ensure(wbcqp_handle* h, Staging& s, size_t bytes)
     return WBCQP_OK;
 }
 
+// per-task costs of `count` solved instances of slot s (task_costs_kernel, wbcqp_costs.hpp): record rows A, b1, Acop, x [count][ldx], tau [count][na];
+// cost row perm[j] (or j) of width ldc.  A is staged in LDS where it fits 48 KB (every shipped stack: Talos 16.7 KB); beyond that the lanes read it
+// from global memory -- the same products in the same order
+constexpr int kCostLdsStage = 48 * 1024;
+
+int launch_costs(wbcqp_handle* h, const Slot& s, int count, const void* A, const void* b1, const void* Acop, const void* x, int ldx, const void* tau,
+                 void* cost, int ldc, const int* perm, hipStream_t stream)
+{
+    if (count <= 0) return WBCQP_OK;
+    const DevStruct& D = s.host;
+    int lda = odd(D.nv);
+    int lds = cost_lds_doubles(D, lda) * 8 + D.r1 * 4;
+    if (lds > kCostLdsStage) {
+        lda = 0;
+        lds = cost_lds_doubles(D, 0) * 8 + D.r1 * 4;
+    }
+    if (h->dtype == WBCQP_F64) {
+        CostArgs<double> a{D, static_cast<const double*>(A), static_cast<const double*>(b1), static_cast<const double*>(Acop), static_cast<const double*>(x),
+                           static_cast<const double*>(tau), static_cast<double*>(cost), perm, count, ldx, ldc, lda};
+        hipLaunchKernelGGL(task_costs_kernel<double>, dim3(count), dim3(kCostThreads), lds, stream, a);
+    }
+    else {
+        CostArgs<float> a{D, static_cast<const float*>(A), static_cast<const float*>(b1), static_cast<const float*>(Acop), static_cast<const float*>(x),
+                          static_cast<const float*>(tau), static_cast<float*>(cost), perm, count, ldx, ldc, lda};
+        hipLaunchKernelGGL(task_costs_kernel<float>, dim3(count), dim3(kCostThreads), lds, stream, a);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return WBCQP_OK;
+}
+
+// a trace whose fields are all NULL is no trace
+const wbcqp_trace* trace_or_null(const wbcqp_trace* tr)
+{
+    return (tr && (tr->q || tr->v || tr->x || tr->tau || tr->status || tr->iters || tr->objective || tr->cost)) ? tr : nullptr;
+}
+
 } // namespace
 
 extern "C" {
@@ -990,6 +1027,22 @@ int wbcqp_solve_batch(wbcqp_handle* h, int slot, int batch, const wbcqp_inputs* 
     G.in = *in;
     G.out = *out;
     return wbcqp_solve_ragged(h, 1, &G, stream);
+}
+
+int wbcqp_task_costs(wbcqp_handle* h, int slot, int batch, const wbcqp_inputs* rows, const void* x, const void* tau, void* cost, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (slot < 0 || slot >= WBCQP_MAX_STRUCTURES || !h->slots[slot].set) return fail(h, WBCQP_ERR_INVALID, "slot has no structure");
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (batch == 0) return WBCQP_OK;
+    const Slot& s = h->slots[slot];
+    const wbcqp_layout& L = s.layout;
+    if (!rows || (L.len_A && !rows->A) || (L.len_b1 && !rows->b1) || (L.len_Acop && !rows->Acop))
+        return fail(h, WBCQP_ERR_INVALID, "rows A, b1 (Acop with a cop task) are required");
+    if (!x || !cost) return fail(h, WBCQP_ERR_INVALID, "x / cost is NULL");
+    if (s.host.n_acteq > 0 && !tau) return fail(h, WBCQP_ERR_INVALID, "tau is required: the stack has a torque task");
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_costs(h, s, batch, rows->A, rows->b1, rows->Acop, x, L.n, tau, cost, L.len_w, nullptr, static_cast<hipStream_t>(stream));
 }
 
 int wbcqp_solve_batch_host(wbcqp_handle* h, int slot, int batch, const wbcqp_inputs* in, const wbcqp_outputs* out)
@@ -1687,7 +1740,24 @@ static int tick_impl(wbcqp_handle* h, int slot, int batch, const wbcqp_tick_io* 
                           io->out.status, io->q_next, io->v_next, io->q_solver, stream, acc);
 }
 
+static int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_trace* tr, void* stream);
+
 int wbcqp_rollout(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, void* stream)
+{
+    return rollout_impl(h, slot, batch, n_ticks, io, nullptr, stream);
+}
+
+int wbcqp_rollout_traced(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_trace* trace, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (trace && trace->stride < 1) return fail(h, WBCQP_ERR_INVALID, "trace: stride must be >= 1");
+    if (trace && trace->cost && io && slot >= 0 && slot < WBCQP_MAX_STRUCTURES && h->slots[slot].set && h->slots[slot].host.n_acteq > 0 && !trace->tau &&
+        !io->out.tau)
+        return fail(h, WBCQP_ERR_INVALID, "trace: the costs of a stack with a torque task need tau (trace->tau or io->out.tau)");
+    return rollout_impl(h, slot, batch, n_ticks, io, trace_or_null(trace), stream);
+}
+
+static int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_trace* tr, void* stream)
 {
     if (!h) return WBCQP_ERR_INVALID;
     if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
@@ -1825,11 +1895,29 @@ int wbcqp_rollout(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp
     const bool own_stream = S == 1;
     if (!own_stream)
         for (int k = 0; k < S; ++k) HIP_TRY(h, hipStreamWaitEvent(h->roll_subs[k].stream, h->roll_start, 0));
+    // with a trace: a recorded tick's solve and integration write into the trace's entry (the next tick reads its state from there), a
+    // recorded last tick writes io's outputs and is copied into its entry after the join
+    const int na = s.host.na;
+    auto pick = [&](void* io_f, void* tr_f, bool recorded, bool last, size_t r0, size_t len, size_t ebytes) -> void* {
+        if (recorded && tr_f && !(last && io_f)) return static_cast<char*>(tr_f) + r0 * len * ebytes;
+        return io_f;
+    };
+    const char* qsrc = static_cast<const char*>(io->state.q); // the state the next tick starts from (the first tick reads the caller's q / v in place)
+    const char* vsrc = static_cast<const char*>(io->state.v);
     // tick t of every sub-batch is enqueued before tick t + 1 of any: the streams then advance together on the device (enqueued one
     // sub-batch after the other, the last stream's first tick would reach the device when the first stream is almost through), and the
     // tail of one sub-batch's solve (its longest QP) runs beside the bulk of another's
     for (int t = 0; t < n_ticks && rc_all == WBCQP_OK; ++t) {
         const bool last = t + 1 == n_ticks;
+        const bool recorded = tr && (t + 1) % tr->stride == 0;
+        const size_t r0 = recorded ? (size_t)((t + 1) / tr->stride - 1) * B : 0; // first row of the trace entry
+        char* qdst = static_cast<char*>(last ? io->q_next : pick(qbuf[(t + 1) & 1], tr ? tr->q : nullptr, recorded, false, r0, T.nq, es));
+        char* vdst = static_cast<char*>(last ? io->v_next : pick(vbuf[(t + 1) & 1], tr ? tr->v : nullptr, recorded, false, r0, T.nv, es));
+        void* xo = pick(io->out.x, tr ? tr->x : nullptr, recorded, last, r0, L.n, es);
+        void* tauo = pick(io->out.tau, tr ? tr->tau : nullptr, recorded, last, r0, na, es);
+        void* objo = pick(io->out.objective, tr ? tr->objective : nullptr, recorded, last, r0, 1, es);
+        int32_t* sto = static_cast<int32_t*>(pick(io->out.status, tr ? tr->status : nullptr, recorded, last, r0, 1, 4));
+        int32_t* ito = static_cast<int32_t*>(pick(io->out.iters, tr ? tr->iters : nullptr, recorded, last, r0, 1, 4));
         for (int k = 0; k < S && rc_all == WBCQP_OK; ++k) {
             const size_t b0 = (size_t)k * batch / S, b1 = (size_t)(k + 1) * batch / S;
             const int nb = (int)(b1 - b0);
@@ -1841,27 +1929,47 @@ int wbcqp_rollout(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp
             d.rows.blb = rec + roff[6] + b0 * rlen[6] * es; d.rows.bub = rec + roff[7] + b0 * rlen[7] * es;
             d.rows.Acop = rec + roff[8] + b0 * rlen[8] * es;
             d.rows.tlb = at(io->tlb, b0 * L.len_tlb); d.rows.tub = at(io->tub, b0 * L.len_tub); d.rows.w = at(io->w, b0 * L.len_w);
-            d.out.x = atw(io->out.x, b0 * L.n); d.out.tau = atw(io->out.tau, b0 * s.host.na); d.out.objective = atw(io->out.objective, b0);
-            d.out.status = io->out.status + b0; d.out.iters = io->out.iters + b0;
+            d.out.x = atw(xo, b0 * L.n); d.out.tau = atw(tauo, b0 * na); d.out.objective = atw(objo, b0);
+            d.out.status = sto + b0; d.out.iters = ito + b0;
             d.out.n_active = io->out.n_active ? io->out.n_active + b0 : nullptr;
             d.out.active_mask = io->out.active_mask ? io->out.active_mask + b0 * 8 : nullptr;
-            d.state.q = (t == 0) ? at(io->state.q, b0 * T.nq) : (const void*)(qbuf[t & 1] + b0 * T.nq * es);
-            d.state.v = (t == 0) ? at(io->state.v, b0 * T.nv) : (const void*)(vbuf[t & 1] + b0 * T.nv * es);
+            d.state.q = qsrc + b0 * T.nq * es;
+            d.state.v = vsrc + b0 * T.nv * es;
             d.state.ref = at(io->state.ref, ((size_t)t * B + b0) * T.nref);
             d.state.momentum = last ? atw(io->state.momentum, b0 * 6) : nullptr;
-            d.q_next = last ? atw(io->q_next, b0 * T.nq) : (void*)(qbuf[(t + 1) & 1] + b0 * T.nq * es);
-            d.v_next = last ? atw(io->v_next, b0 * T.nv) : (void*)(vbuf[(t + 1) & 1] + b0 * T.nv * es);
+            d.q_next = qdst + b0 * T.nq * es;
+            d.v_next = vdst + b0 * T.nv * es;
             d.q_solver = last ? atw(io->q_solver, b0 * T.nv) : nullptr;
             d.dt = io->dt;
             h->graph_ord = own_stream ? nullptr : &sub.ord; // a sub-batch's own launch-order state and queue counter (as a captured tick has)
-            const RollAcc acc = {io->out.iters + b0, io->iters_sum ? io->iters_sum + b0 : nullptr, io->ticks_ok ? io->ticks_ok + b0 : nullptr, t == 0 ? 1 : 0};
+            const RollAcc acc = {d.out.iters, io->iters_sum ? io->iters_sum + b0 : nullptr, io->ticks_ok ? io->ticks_ok + b0 : nullptr, t == 0 ? 1 : 0};
             rc_all = tick_impl(h, slot, nb, &d, own_stream ? sm : sub.stream, acc); // (the per-instance totals ride along with the integration)
             h->graph_ord = nullptr;
+            if (rc_all == WBCQP_OK && recorded && tr->cost) // (before the next tick's rows kernel overwrites the record: same stream)
+                rc_all = launch_costs(h, s, nb, d.rows.A, d.rows.b1, L.len_Acop ? d.rows.Acop : nullptr, d.out.x, L.n, d.out.tau,
+                                      static_cast<char*>(tr->cost) + (r0 + b0) * L.len_w * es, L.len_w, nullptr, own_stream ? sm : sub.stream);
         }
+        qsrc = qdst;
+        vsrc = vdst;
     }
     for (int k = 0; k < S && !own_stream; ++k) {
         HIP_TRY(h, hipEventRecord(h->roll_subs[k].done, h->roll_subs[k].stream));
         HIP_TRY(h, hipStreamWaitEvent(sm, h->roll_subs[k].done, 0));
+    }
+    if (rc_all == WBCQP_OK && tr && n_ticks % tr->stride == 0) { // the last tick is recorded: its outputs went to io, copied into the last entry
+        const size_t r0 = (size_t)(n_ticks / tr->stride - 1) * B;
+        auto cp = [&](void* dst, const void* src, size_t bytes) -> int {
+            if (dst && src && bytes) HIP_TRY(h, hipMemcpyAsync(static_cast<char*>(dst) + r0 * bytes / B, src, bytes, hipMemcpyDeviceToDevice, sm));
+            return WBCQP_OK;
+        };
+        int rc = cp(tr->q, io->q_next, B * T.nq * es);
+        if (rc == WBCQP_OK) rc = cp(tr->v, io->v_next, B * T.nv * es);
+        if (rc == WBCQP_OK) rc = cp(tr->x, io->out.x, B * L.n * es);
+        if (rc == WBCQP_OK) rc = cp(tr->tau, io->out.tau, B * na * es);
+        if (rc == WBCQP_OK) rc = cp(tr->objective, io->out.objective, B * es);
+        if (rc == WBCQP_OK) rc = cp(tr->status, io->out.status, B * 4);
+        if (rc == WBCQP_OK) rc = cp(tr->iters, io->out.iters, B * 4);
+        rc_all = rc;
     }
     HIP_TRY(h, hipEventRecord(h->roll_done, sm));
     if (meas && rc_all == WBCQP_OK) {
@@ -1889,6 +1997,7 @@ struct MixCall { // the checked arguments of a mixed call
     void *q_next, *v_next, *q_solver;
     double dt;
     int32_t *iters_sum, *ticks_ok;
+    const wbcqp_trace* trace; // null: untraced
 };
 
 int check_mix(wbcqp_handle* h, const MixCall& c)
@@ -1958,8 +2067,10 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
     const Slot& s0 = h->slots[mix.slots[0]];
     const TermsDev& T0 = s0.terms;
     constexpr size_t es = sizeof(TI);
-    int ldx = 0;
+    int ldx = 0, ldc = 0;
     for (int k = 0; k < K; ++k) ldx = std::max(ldx, h->slots[mix.slots[k]].layout.n);
+    for (int k = 0; k < K; ++k) ldc = std::max(ldc, h->slots[mix.slots[k]].layout.len_w);
+    const wbcqp_trace* tr = c.trace;
     // the plan: per tick, the instances of set 0, then of set 1, ... (ascending within a set), and the sets' counts
     std::vector<int> counts((size_t)c.n_ticks * K, 0);
     for (int t = 0; t < c.n_ticks; ++t)
@@ -2025,8 +2136,14 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
     const TI* v = static_cast<const TI*>(c.state.v);
     for (int t = 0; t < c.n_ticks; ++t) {
         const bool last = t + 1 == c.n_ticks;
+        // a recorded tick (trace) writes its outputs and state into the trace's entry; a recorded last tick writes io's, copied there below
+        const bool recorded = tr && (t + 1) % tr->stride == 0;
+        const size_t r0 = recorded ? (size_t)((t + 1) / tr->stride - 1) * B : 0;
+        auto ent = [&](void* f, size_t len, size_t eb) -> void* { return recorded && f ? static_cast<char*>(f) + r0 * len * eb : nullptr; };
         TI* qn = last ? static_cast<TI*>(c.q_next) : reinterpret_cast<TI*>(stt + (t & 1) * qb);
         TI* vn = last ? static_cast<TI*>(c.v_next) : reinterpret_cast<TI*>(stt + 2 * qb + (t & 1) * vb);
+        if (!last && recorded && tr->q) qn = static_cast<TI*>(ent(tr->q, T0.nq, es));
+        if (!last && recorded && tr->v) vn = static_cast<TI*>(ent(tr->v, T0.nv, es));
         const int* perm = P.dev + (size_t)t * B;
         wbcqp_group groups[kMaxGroups];
         MixedScatterArgs<TI> sa{};
@@ -2077,10 +2194,35 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
         if (last) { // (the outputs of the last tick only: what a roll-out reports)
             sa.x = static_cast<TI*>(c.out.x); sa.tau = static_cast<TI*>(c.out.tau); sa.objective = static_cast<TI*>(c.out.objective);
             sa.status = c.out.status; sa.iters = c.out.iters; sa.n_active = c.out.n_active; sa.amask = c.out.active_mask;
+            if (recorded && !sa.objective) sa.objective = static_cast<TI*>(ent(tr->objective, 1, es));
+        }
+        else if (recorded) {
+            sa.x = static_cast<TI*>(ent(tr->x, ldx, es)); sa.tau = static_cast<TI*>(ent(tr->tau, T0.na, es)); sa.objective = static_cast<TI*>(ent(tr->objective, 1, es));
+            sa.status = static_cast<int*>(ent(tr->status, 1, 4)); sa.iters = static_cast<int*>(ent(tr->iters, 1, 4));
         }
         sa.iters_sum = c.iters_sum; sa.ticks_ok = c.ticks_ok; sa.first = t == 0 ? 1 : 0;
         hipLaunchKernelGGL(mixed_integrate_kernel<TI>, dim3((B + 3) / 4), dim3(256), 0, sm, sa);
         HIP_TRY(h, hipGetLastError());
+        if (recorded && tr->cost) // every set's costs from its own record and outputs, rows put in instance order (before the next tick's rows kernels)
+            for (int g = 0; g < ng; ++g) {
+                rc = launch_costs(h, h->slots[groups[g].slot], groups[g].batch, groups[g].in.A, groups[g].in.b1, groups[g].in.Acop, groups[g].out.x,
+                                  sa.g[g].n, groups[g].out.tau, static_cast<TI*>(tr->cost) + r0 * ldc, ldc, perm + sa.off[g], sm);
+                if (rc != WBCQP_OK) return rc;
+            }
+        if (last && recorded) { // the last tick is recorded: its outputs went to io
+            auto cp = [&](void* f, const void* src, size_t len, size_t eb) -> int {
+                if (f && src && len) HIP_TRY(h, hipMemcpyAsync(static_cast<char*>(f) + r0 * len * eb, src, (size_t)B * len * eb, hipMemcpyDeviceToDevice, sm));
+                return WBCQP_OK;
+            };
+            rc = cp(tr->q, c.q_next, T0.nq, es);
+            if (rc == WBCQP_OK) rc = cp(tr->v, c.v_next, T0.nv, es);
+            if (rc == WBCQP_OK) rc = cp(tr->x, c.out.x, ldx, es);
+            if (rc == WBCQP_OK) rc = cp(tr->tau, c.out.tau, T0.na, es);
+            if (rc == WBCQP_OK) rc = cp(tr->objective, c.out.objective, 1, es);
+            if (rc == WBCQP_OK) rc = cp(tr->status, c.out.status, 1, 4);
+            if (rc == WBCQP_OK) rc = cp(tr->iters, c.out.iters, 1, 4);
+            if (rc != WBCQP_OK) return rc;
+        }
         q = qn;
         v = vn;
     }
@@ -2106,7 +2248,7 @@ int wbcqp_tick_mixed(wbcqp_handle* h, const wbcqp_mix* mix, int batch, const int
 {
     if (!h) return WBCQP_ERR_INVALID;
     if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
-    const MixCall c{mix, batch, 1, which, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, nullptr, nullptr};
+    const MixCall c{mix, batch, 1, which, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, nullptr, nullptr, nullptr};
     return mixed_call(h, c, stream);
 }
 
@@ -2114,7 +2256,18 @@ int wbcqp_rollout_mixed(wbcqp_handle* h, const wbcqp_mix* mix, int batch, int n_
 {
     if (!h) return WBCQP_ERR_INVALID;
     if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
-    const MixCall c{mix, batch, n_ticks, schedule, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, io->iters_sum, io->ticks_ok};
+    const MixCall c{mix, batch, n_ticks, schedule, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, io->iters_sum, io->ticks_ok, nullptr};
+    return mixed_call(h, c, stream);
+}
+
+int wbcqp_rollout_mixed_traced(wbcqp_handle* h, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule, const wbcqp_rollout_io* io,
+                               const wbcqp_trace* trace, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
+    if (trace && trace->stride < 1) return fail(h, WBCQP_ERR_INVALID, "trace: stride must be >= 1");
+    const MixCall c{mix, batch, n_ticks, schedule, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, io->iters_sum, io->ticks_ok,
+                    trace_or_null(trace)};
     return mixed_call(h, c, stream);
 }
 
