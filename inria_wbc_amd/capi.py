@@ -364,11 +364,7 @@ class Handle:
                 continue
             assert t.is_cuda and t.is_contiguous() and t.numel() == batch * L[k], (k, tuple(t.shape), batch, L[k])
             setattr(cin, k, t.data_ptr())
-        cout = COutputs()
-        for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask"):  # active_mask: int32 [batch, 8], in/out
-            t = outputs.get(k)
-            setattr(cout, k, t.data_ptr() if t is not None and t.numel() else None)
-        return cin, cout
+        return cin, self._outs(outputs)
 
     def solve_batch(self, slot: int, batch: int, inputs: Dict[str, "object"], outputs: Dict[str, "object"], stream: int = 0):
         cin, cout = self._pack(slot, batch, inputs, outputs)
@@ -400,8 +396,7 @@ class Handle:
         """q, v, ref -> M, h, A, b1, Ac, bc, blb, bub on device tensors (wbcqp_problem_data)."""
         st = self._structs[slot]
         L = st.field_lengths()
-        cs = CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr() if state.get("ref") is not None else None,
-                    state["momentum"].data_ptr() if state.get("momentum") is not None else None)  # momentum: [batch, 6] output, optional
+        cs = self._state(state)
         cin = CInputs()
         for k in FIELDS:
             t = rows.get(k)
@@ -431,12 +426,9 @@ class Handle:
     def _tick_io(self, slot: int, batch: int, state, rows, out, q_next, v_next, dt: float, q_solver=None) -> CTickIO:
         cin, cout = self._pack(slot, batch, rows, out)
         io = CTickIO()
-        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr(),
-                          state["momentum"].data_ptr() if state.get("momentum") is not None else None)
+        io.state = self._state(state, need_ref=True)
         io.rows, io.out = cin, cout
-        io.q_next, io.v_next = q_next.data_ptr(), v_next.data_ptr()
-        io.q_solver = q_solver.data_ptr() if q_solver is not None else None
-        io.dt = float(dt)
+        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver), float(dt)
         return io
 
     def tick(self, slot: int, batch: int, state, rows, out, q_next, v_next, dt: float, q_solver=None, stream: int = 0):
@@ -448,25 +440,9 @@ class Handle:
                 ticks_ok=None, stream: int = 0):
         """n_ticks control ticks of every instance in one launch, no batch barrier (wbcqp_rollout).  state: q [B, nq], v [B, nv],
         ref [n_ticks, B, nref] (+ optional momentum [B, 6]); limits: tlb, tub, w; out: x, tau, status, iters of the LAST tick."""
-        st = self._structs[slot]
-        io = CRolloutIO()
-        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr(),
-                          state["momentum"].data_ptr() if state.get("momentum") is not None else None)
         assert state["ref"].is_contiguous() and state["ref"].shape[0] == n_ticks and state["ref"].shape[1] == batch
-        io.tlb = limits["tlb"].data_ptr() if limits.get("tlb") is not None and st.act_bounds else None
-        io.tub = limits["tub"].data_ptr() if limits.get("tub") is not None and st.act_bounds else None
-        io.w = limits["w"].data_ptr()
-        cout = COutputs()
-        for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask"):
-            t = out.get(k)
-            setattr(cout, k, t.data_ptr() if t is not None and t.numel() else None)
-        io.out = cout
-        io.q_next, io.v_next = q_next.data_ptr(), v_next.data_ptr()
-        io.q_solver = q_solver.data_ptr() if q_solver is not None else None
-        io.dt = float(dt)
-        io.iters_sum = iters_sum.data_ptr() if iters_sum is not None else None
-        io.ticks_ok = ticks_ok.data_ptr() if ticks_ok is not None else None
-        self._check(self.lib.wbcqp_rollout(self._h, slot, batch, n_ticks, C.byref(io), C.c_void_p(stream)))
+        limits["w"]  # (a call without weights is refused here, not in the library)
+        self.rollout_traced(slot, batch, n_ticks, state, limits, out, q_next, v_next, dt, None, 1, q_solver, iters_sum, ticks_ok, stream)
 
     @staticmethod
     def _ptr(t):
@@ -481,9 +457,22 @@ class Handle:
 
     def _outs(self, out) -> COutputs:
         cout = COutputs()
-        for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask"):
+        for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask"):  # active_mask: int32 [batch, 8], in/out
             setattr(cout, k, self._ptr(out.get(k)))
         return cout
+
+    def _state(self, state, need_ref: bool = False) -> CState:
+        """wbcqp_state from device tensors q, v (ref, momentum [batch, 6]: an output); need_ref: a state without ref is refused here."""
+        return CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr() if need_ref else self._ptr(state.get("ref")),
+                      self._ptr(state.get("momentum")))
+
+    def _rollout_io(self, state, out, q_next, v_next, dt: float, q_solver, iters_sum, ticks_ok, need_ref: bool = False) -> CRolloutIO:
+        io = CRolloutIO()
+        io.state = self._state(state, need_ref)
+        io.out = self._outs(out)
+        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver), float(dt)
+        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
+        return io
 
     def tick_mixed(self, slots: Sequence[int], which, state, w: Sequence, out, q_next, v_next, dt: float, tlb=None, tub=None, q_solver=None,
                    stream: int = 0):
@@ -493,10 +482,8 @@ class Handle:
         which = np.ascontiguousarray(which, dtype=np.int32)
         mix, keep = self._mix(slots, w, tlb, tub)
         io = CMixedIO()
-        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), self._ptr(state.get("ref")), self._ptr(state.get("momentum")))
-        io.out = self._outs(out)
-        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
-        io.dt = float(dt)
+        io.state, io.out = self._state(state), self._outs(out)
+        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver), float(dt)
         self._check(self.lib.wbcqp_tick_mixed(self._h, C.byref(mix), int(which.size), which.ctypes.data_as(c_i32_p), C.byref(io),
                                               C.c_void_p(stream)))
         del keep
@@ -505,18 +492,7 @@ class Handle:
                       q_solver=None, iters_sum=None, ticks_ok=None, stream: int = 0):
         """K ticks of a fleet in mixed contact sets, enqueued up front (wbcqp_rollout_mixed).  schedule: host int array [K, B] of indices
         into slots; state: q [B, nq], v [B, nv], ref [K, B, nref] (+ momentum [B, 6] of the last tick's state); out: the last tick's."""
-        schedule = np.ascontiguousarray(schedule, dtype=np.int32)
-        K, B = schedule.shape
-        mix, keep = self._mix(slots, w, tlb, tub)
-        io = CRolloutIO()
-        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), self._ptr(state.get("ref")), self._ptr(state.get("momentum")))
-        io.out = self._outs(out)
-        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
-        io.dt = float(dt)
-        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
-        self._check(self.lib.wbcqp_rollout_mixed(self._h, C.byref(mix), int(B), int(K), schedule.ctypes.data_as(c_i32_p), C.byref(io),
-                                                 C.c_void_p(stream)))
-        del keep
+        self.rollout_mixed_traced(slots, schedule, state, w, out, q_next, v_next, dt, None, 1, tlb, tub, q_solver, iters_sum, ticks_ok, stream)
 
     def task_costs(self, slot: int, batch: int, rows: Dict[str, "object"], x, tau, cost, stream: int = 0):
         """Per-task costs ||A_t x - b_t|| of a solved record (wbcqp_task_costs), device tensors: rows (A, b1, Acop read) as given to
@@ -544,15 +520,10 @@ class Handle:
         v [n_rec, B, nv], x [n_rec, B, n], tau [n_rec, B, na], status / iters [n_rec, B] int32, objective [n_rec, B], cost [n_rec, B, n_tasks]
         (n_rec = n_ticks // stride); a field left out is not recorded; trace=None is rollout()."""
         st = self._structs[slot]
-        io = CRolloutIO()
-        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr(), self._ptr(state.get("momentum")))
+        io = self._rollout_io(state, out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok, need_ref=True)
         io.tlb = self._ptr(limits.get("tlb")) if st.act_bounds else None
         io.tub = self._ptr(limits.get("tub")) if st.act_bounds else None
         io.w = self._ptr(limits.get("w"))
-        io.out = self._outs(out)
-        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
-        io.dt = float(dt)
-        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
         self._check(self.lib.wbcqp_rollout_traced(self._h, slot, batch, n_ticks, C.byref(io), self._trace(trace, stride), C.c_void_p(stream)))
 
     def rollout_mixed_traced(self, slots: Sequence[int], schedule, state, w: Sequence, out, q_next, v_next, dt: float, trace=None, stride: int = 1,
@@ -562,12 +533,7 @@ class Handle:
         schedule = np.ascontiguousarray(schedule, dtype=np.int32)
         K, B = schedule.shape
         mix, keep = self._mix(slots, w, tlb, tub)
-        io = CRolloutIO()
-        io.state = CState(state["q"].data_ptr(), state["v"].data_ptr(), self._ptr(state.get("ref")), self._ptr(state.get("momentum")))
-        io.out = self._outs(out)
-        io.q_next, io.v_next, io.q_solver = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver)
-        io.dt = float(dt)
-        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
+        io = self._rollout_io(state, out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok)
         self._check(self.lib.wbcqp_rollout_mixed_traced(self._h, C.byref(mix), int(B), int(K), schedule.ctypes.data_as(c_i32_p), C.byref(io),
                                                         self._trace(trace, stride), C.c_void_p(stream)))
         del keep

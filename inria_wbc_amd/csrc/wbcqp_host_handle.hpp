@@ -1,0 +1,430 @@
+// wbcqp_host_handle.hpp -- host side of the C ABI (wbcqp_api.hip): the handle and its slots, error reporting, device and page-locked buffers, the
+// ONE description of the per-instance arrays of a call (fields, block layout, staging of the host-pointer entry points), the argument checks the entry
+// points share and the F64 / F32 fork.  Host code only; included by wbcqp_api.hip alone.
+#pragma once
+#include "wbcqp_device.hpp"
+#include "wbcqp_terms.hpp"
+#include "wbcqp_dense.hpp"
+#include "wbcqp_small.hpp"
+#include "wbcqp_costs.hpp"
+
+#include "../../include/wbcqp.h"
+
+#include <dlfcn.h>
+#include <limits>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+
+using namespace wbcqp;
+
+
+namespace {
+
+thread_local std::string g_create_error;
+
+struct Slot {
+    bool set = false;
+    DevStruct host{};           // sizes, LDS layout and device pointers of the tables: travels by value with every launch
+    DevStruct host_cp{};        // the same with the compact LDS layout (wbcqp_compact.hpp); host_cp.compact == 0: not eligible
+    std::vector<void*> allocs;  // device arrays owned by this slot
+    wbcqp_layout layout{};      // what wbcqp_layout_of reports: the compact layout where the structure is eligible
+    int lds_full = 0, lds_cp = 0;
+    bool small = false;         // eligible for the one-wavefront-per-QP kernel (wbcqp_small.hpp)
+    int spec = 0;               // 1-based index of the compact kernel's instantiation for this very layout (kSpecDims), 0: the generic kernel
+    std::vector<int> sel_col_h;       // host copies of what wbcqp_set_model needs of the structure: the posture task's columns
+    std::vector<double> force_gen_h;  // and the contacts' force generators (the contact points sit in their skew blocks)
+    double* ffc_dev = nullptr;  // the force blocks' factor for one weight (DevStruct::ffc; owned through `allocs`), null: none (no contacts, not compact, disabled)
+    bool ffc_built = false;     // ... made from the first QP of the slot's first compact launch (solve_ragged)
+    bool has_model = false;     // wbcqp_set_model: tree + task bindings for wbcqp_problem_data
+    std::vector<double> tree;   // ... the tree as numbers (sizes, parents, joint types, placements, inertias, gravity): the slots of a mix must agree on it
+    TermsDev terms{};
+    std::vector<void*> model_allocs;
+};
+
+struct Staging {
+    void* dev = nullptr;
+    size_t bytes = 0;
+};
+// page-locked host memory for the host-pointer entry points at small batches: the input arrays of a QP record (eleven, twelve with a cop task; five output
+// arrays) cross PCIe as ONE copy each way instead of eleven (five) -- at batch 1 the copies' fixed cost is most of the call
+struct Pinned {
+    void* host = nullptr;
+    size_t bytes = 0;
+};
+constexpr size_t kPackedBytes = 1u << 20; // above this the arrays go up one by one (the extra host copy would cost more than it saves)
+
+} // namespace
+
+// launch-order state: the order left by one launch for the next one of the same shape on the same stream.  The handle has
+// one PER STREAM it has launched on (two launches in flight on two streams share neither the order buffer -- the schedule
+// kernel of one would overwrite what the solve kernel of the other is reading -- nor the queue counter); every captured tick
+// (wbcqp_graph) and every sub-batch of a roll-out has its own, so that a replay never touches a buffer another launch may
+// resize or overwrite (a graph bakes the buffer's address into its kernel nodes).
+struct OrderState {
+    int* order = nullptr;        // [2][cap]: longest-first, then the packed order (pack_order_kernel)
+    bool packed = false;         // the second half is valid for total / sig / stream
+    int age = 0;                 // launches that have used the order since it was computed
+    int cap = 0;
+    int total = 0;               // 0: no valid order
+    unsigned long long sig = 0;  // shape of the launch the order belongs to
+    hipStream_t stream = nullptr;
+    int* queue = nullptr;        // the queue counter pair of solve_queue_kernel that goes with this order (allocated on first use)
+};
+
+constexpr size_t kMaxQueues = 16;
+constexpr int kQueueMinLds = 48 * 1024; // workgroups at least this large take their QPs from the queue by default (measured: below it the dispatcher wins, launch())
+constexpr int kQueue3MinLds = 40 * 1024; // ... and from 40 KB on where the launch runs three per CU through solve_queue3_kernel (the dispatcher's solve_kernel holds
+                                         // two); a 40-48 KB stack that cannot take the twin (actuation bounds, warm start) stays with the dispatcher
+constexpr int kLdsThree = 54592;        // the largest dynamic LDS block of which a CU holds three (tools/ubench/lds_granule.hip)
+constexpr int kOrderRefresh = 4; // default period of the launch-order renewal (WBCQP_FLAG_REFRESH)
+
+struct wbcqp_handle {
+    int device = 0;
+    int dtype = WBCQP_F64;
+    std::string err;
+    Slot slots[WBCQP_MAX_STRUCTURES];
+    Staging stage_in, stage_out;
+    Pinned pin_in, pin_out;
+    // per kernel variant (0: full layout, 1: compact, 2 + i: the compact kernel specialised for kSpecDims[i]): largest dynamic LDS size set so far
+    int max_lds[2 + kNumSpecs] = {};
+    long long* dbg = nullptr; // diagnostic builds only (wbcqp_debug_set_stamp_buffer)
+    // longest-first schedule (schedule_kernel): launch order for the next solve of the same shape on the same stream
+    int flags = 0;
+    // one order state (order buffer + queue counter pair) per stream this handle has launched on; a launch on a stream beyond
+    // kMaxQueues distinct ones runs in index order on the hardware's dispatcher and leaves no state behind
+    struct StreamState {
+        hipStream_t stream;
+        OrderState ord;
+    };
+    std::vector<StreamState> streams;
+    int last_stream = -1;            // index of the stream state the most recent launch used (wbcqp_launch_order reports that one)
+    OrderState* graph_ord = nullptr; // wbcqp_tick_graph_create: the launches of this tick use the graph's own order state
+    bool capturing = false;          // ... and a captured tick always renews its order
+    int n_cu = 0;
+    int dense_max_lds = 0;
+    // wbcqp_solve_dense_host: the reference's HQPOutput, owned by the solver and valid until the next call
+    std::vector<double> dense_x, dense_obj;
+    std::vector<int32_t> dense_status, dense_iters, dense_nact;
+    wbcqp_dense_output dense_out{};
+    int lds_pad = 0; // diagnostic (env WBCQP_DEBUG_LDS_PAD): extra dynamic LDS per workgroup, to force a lower residency
+    int queue_lds[2 + kNumSpecs], queue_occ[2 + kNumSpecs] = {}; // occupancy of solve_queue_kernel<., CP, SPEC> at queue_lds bytes of LDS
+    int queue_occ_warm[2 + kNumSpecs] = {};                      // ... of solve_queue_kernel_warm<., SPEC> (WBCQP_FLAG_WARM_START launches that kernel)
+    bool debug_launch = false;                                   // env WBCQP_DEBUG_LAUNCH, read once at wbcqp_create (never on the per-tick path)
+    bool no_ffcache = false;                                     // env WBCQP_DEBUG_NO_FFCACHE: every QP eliminates its force blocks itself (what tests compare the cache with)
+    int queue_occ3[2 + kNumSpecs] = {};                          // ... of solve_queue3_kernel<., SPEC> where queue_three says it holds three
+    bool warned_occupancy = false;                               // the one-time note of launch() when the runtime's occupancy answer is overruled
+    bool queue_three[2 + kNumSpecs] = {};                        // ... and whether solve_queue3_kernel<., SPEC> holds three workgroups per CU at that size
+    // wbcqp_rollout: sub-batches on streams of their own (each with its own launch-order state and queue counter), the record
+    // arrays and the state ping-pong of the whole batch
+    struct RollSub {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;
+        OrderState ord;
+    };
+    std::vector<RollSub> roll_subs;
+    hipEvent_t roll_start = nullptr;
+    hipEvent_t roll_done = nullptr;  // end of the previous roll-out: the next one (on whatever stream) waits for it before it reuses the buffers
+    // how many sub-batches a roll-out is cut into is MEASURED, per (slot, batch): the device time of every roll-out lies between
+    // roll_start and roll_done (both timed events); the next call reads it without blocking (hipEventQuery) and keeps, per shape, a
+    // running figure of microseconds per tick for one sub-batch (= what K calls of wbcqp_tick do) and for two
+    struct RollStat {
+        int slot = -1, batch = 0, calls = 0;
+        double us[3] = {0.0, 0.0, 0.0}; // [S] running mean, 0: never measured
+        int cold[3] = {1, 1, 1};        // [S] the next measurement of this form is its first: it paid the form's allocations and stream set-up, it is not kept
+    };
+    std::vector<RollStat> roll_stats;
+    struct RollMeas { // one timed event pair around a roll-out, read by a later call once the device has passed it
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        int stat = -1, S = 0, ticks = 0;
+        bool pending = false;
+    };
+    RollMeas roll_meas[4];
+    Staging roll_rec, roll_state;
+    // wbcqp_tick_mixed / wbcqp_rollout_mixed: the per-tick permutations go up through a ring of page-locked buffers (an entry is reused
+    // once the call that last used it is done on the device: four calls ago), the per-set records, gathered weights and outputs, and the
+    // state ping-pong of a roll-out
+    struct MixPlan {
+        Pinned pin;
+        int* dev = nullptr;
+        size_t cap = 0; // ints
+        hipEvent_t done = nullptr;
+        bool used = false;
+    };
+    MixPlan mix_plan[4];
+    int mix_next = 0;
+    Staging mix_rec, mix_state;
+    hipEvent_t mix_done = nullptr; // end of the previous mixed call: the next one (on whatever stream) waits for it before it reuses the buffers
+};
+
+namespace {
+
+int fail(wbcqp_handle* h, int code, const std::string& msg)
+{
+    if (h)
+        h->err = msg;
+    else
+        g_create_error = msg;
+    return code;
+}
+
+#define HIP_TRY(h, expr)                                                                         \
+    do {                                                                                         \
+        hipError_t e_ = (expr);                                                                  \
+        if (e_ != hipSuccess)                                                                    \
+            return fail(h, WBCQP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
+    } while (0)
+
+#define WB_TRY(expr)                          \
+    do {                                      \
+        const int rc_ = (expr);               \
+        if (rc_ != WBCQP_OK) return rc_;      \
+    } while (0)
+
+int ensure_pinned(wbcqp_handle* h, Pinned& p, size_t bytes)
+{
+    if (p.bytes >= bytes) return WBCQP_OK;
+    if (p.host) (void)hipHostFree(p.host);
+    p.host = nullptr;
+    p.bytes = 0;
+    HIP_TRY(h, hipHostMalloc(&p.host, bytes, hipHostMallocDefault));
+    p.bytes = bytes;
+    return WBCQP_OK;
+}
+
+int ensure(wbcqp_handle* h, Staging& s, size_t bytes)
+{
+    if (s.bytes >= bytes) return WBCQP_OK;
+    if (s.dev) (void)hipFree(s.dev);
+    s.dev = nullptr;
+    s.bytes = 0;
+    HIP_TRY(h, hipMalloc(&s.dev, bytes));
+    s.bytes = bytes;
+    return WBCQP_OK;
+}
+
+template <typename T>
+int upload(wbcqp_handle* h, Slot& s, const T* src, size_t count, const T** dst)
+{
+    void* p = nullptr;
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    HIP_TRY(h, hipMalloc(&p, bytes));
+    s.allocs.push_back(p);
+    if (count) HIP_TRY(h, hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    *dst = static_cast<const T*>(p);
+    return WBCQP_OK;
+}
+
+void release_model(Slot& s)
+{
+    for (void* p : s.model_allocs) (void)hipFree(p);
+    s.model_allocs.clear();
+    s.has_model = false;
+    s.tree.clear();
+}
+
+void release(Slot& s)
+{
+    for (void* p : s.allocs) (void)hipFree(p);
+    s.allocs.clear();
+    s.set = false;
+    release_model(s);
+}
+
+// ---- the F64 / F32 fork: f(Tag<double>{}) or f(Tag<float>{}) by the handle's dtype -----------------------------------------------------------------
+template <typename T> struct Tag { using type = T; };
+template <typename F> int with_dtype(const wbcqp_handle* h, F&& f) { return h->dtype == WBCQP_F64 ? f(Tag<double>{}) : f(Tag<float>{}); }
+#define WB_TI(tag) typename decltype(tag)::type
+inline size_t elem_size(const wbcqp_handle* h) { return h->dtype == WBCQP_F64 ? 8 : 4; }
+
+// ---- the per-instance arrays of a call, described once ----------------------------------------------------------------------------------------------
+// In the order of the members of wbcqp_inputs, wbcqp_outputs and wbcqp_state, then the q_next / v_next / q_solver of a tick: the pointers of a call are
+// one array indexed by Field (Io), filled from and turned back into the ABI's structs as a whole.
+enum Field { F_M, F_h, F_A, F_b1, F_Ac, F_bc, F_blb, F_bub, F_tlb, F_tub, F_w, F_Acop, // wbcqp_inputs
+             F_x, F_tau, F_status, F_iters, F_obj, F_nact, F_amask,                   // wbcqp_outputs
+             F_q, F_v, F_ref, F_mom,                                                  // wbcqp_state
+             F_qn, F_vn, F_qs, F_N };
+struct FieldInfo {
+    const char* name;
+    int elem; // bytes of one element; 0: the handle's dtype
+};
+constexpr FieldInfo kField[F_N] = {{"M", 0}, {"h", 0}, {"A", 0}, {"b1", 0}, {"Ac", 0}, {"bc", 0}, {"blb", 0}, {"bub", 0}, {"tlb", 0}, {"tub", 0}, {"w", 0}, {"Acop", 0},
+                                   {"x", 0}, {"tau", 0}, {"status", 4}, {"iters", 4}, {"objective", 0}, {"n_active", 4}, {"active_mask", 32},
+                                   {"q", 0}, {"v", 0}, {"ref", 0}, {"momentum", 0}, {"q_next", 0}, {"v_next", 0}, {"q_solver", 0}};
+static_assert(sizeof(wbcqp_inputs) == (F_Acop - F_M + 1) * sizeof(void*) && offsetof(wbcqp_inputs, Acop) == (F_Acop - F_M) * sizeof(void*), "Field follows wbcqp_inputs");
+static_assert(sizeof(wbcqp_outputs) == (F_amask - F_x + 1) * sizeof(void*) && offsetof(wbcqp_outputs, objective) == (F_obj - F_x) * sizeof(void*), "Field follows wbcqp_outputs");
+static_assert(sizeof(wbcqp_state) == (F_mom - F_q + 1) * sizeof(void*) && offsetof(wbcqp_state, momentum) == (F_mom - F_q) * sizeof(void*), "Field follows wbcqp_state");
+
+// bytes per instance of every field, for slot s and elements of es bytes
+struct FieldBytes {
+    size_t b[F_N];
+};
+FieldBytes field_bytes(const Slot& s, size_t es)
+{
+    const wbcqp_layout& L = s.layout;
+    const TermsDev& T = s.terms;
+    const int len[F_N] = {L.len_M, L.len_h, L.len_A, L.len_b1, L.len_Ac, L.len_bc, L.len_blb, L.len_bub, L.len_tlb, L.len_tub, L.len_w, L.len_Acop,
+                          L.n, s.host.na, 1, 1, 1, 1, 1, T.nq, T.nv, T.nref, 6, T.nq, T.nv, T.nv};
+    FieldBytes r;
+    for (int f = 0; f < F_N; ++f) r.b[f] = (size_t)len[f] * (kField[f].elem ? (size_t)kField[f].elem : es);
+    return r;
+}
+
+struct Io {
+    void* p[F_N] = {};
+    Io() = default;
+    Io(const wbcqp_inputs* in, const wbcqp_outputs* out, const wbcqp_state* st = nullptr, void* q_next = nullptr, void* v_next = nullptr, void* q_solver = nullptr)
+    {
+        if (in) std::memcpy(p + F_M, in, sizeof(*in));
+        if (out) std::memcpy(p + F_x, out, sizeof(*out));
+        if (st) std::memcpy(p + F_q, st, sizeof(*st));
+        p[F_qn] = q_next; p[F_vn] = v_next; p[F_qs] = q_solver;
+    }
+    wbcqp_inputs inputs() const { wbcqp_inputs r; std::memcpy(&r, p + F_M, sizeof(r)); return r; }
+    wbcqp_outputs outputs() const { wbcqp_outputs r; std::memcpy(&r, p + F_x, sizeof(r)); return r; }
+    wbcqp_state state() const { wbcqp_state r; std::memcpy(&r, p + F_q, sizeof(r)); return r; }
+    wbcqp_tick_io tick_io(double dt) const { return wbcqp_tick_io{state(), inputs(), outputs(), p[F_qn], p[F_vn], p[F_qs], dt}; }
+    // the same arrays from instance `first` on (null stays null)
+    Io from(size_t first, const FieldBytes& fb) const
+    {
+        Io r;
+        for (int f = 0; f < F_N; ++f) r.p[f] = p[f] ? static_cast<char*>(p[f]) + first * fb.b[f] : nullptr;
+        return r;
+    }
+};
+
+// one array of a block: which field (-1: none of them, elements of the handle's dtype), the caller's side, its size and its place in the block
+struct Arr {
+    int f;
+    void* host;
+    size_t bytes, off;
+};
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+// block layout: the arrays one after the other from byte `at`, each on a 256-byte boundary; returns the end
+size_t lay(Arr* a, int n, size_t at = 0)
+{
+    for (int i = 0; i < n; ++i) {
+        a[i].off = at;
+        at += al256(a[i].bytes);
+    }
+    return at;
+}
+// ... of the fields `fields` of `count` instances (an array is laid out whether or not the caller has one)
+size_t lay(const FieldBytes& fb, size_t count, const Field* fields, int n, const Io& host, Arr* a, size_t at = 0)
+{
+    for (int i = 0; i < n; ++i) a[i] = Arr{fields[i], host.p[fields[i]], count * fb.b[fields[i]], 0};
+    return lay(a, n, at);
+}
+void point(Io& d, void* base, const Arr* a, int n)
+{
+    for (int i = 0; i < n; ++i) d.p[a[i].f] = static_cast<char*>(base) + a[i].off;
+}
+constexpr Field kInputFields[12] = {F_M, F_h, F_A, F_b1, F_Ac, F_bc, F_blb, F_bub, F_tlb, F_tub, F_w, F_Acop};
+constexpr Field kRecordFields[10] = {F_M, F_h, F_A, F_b1, F_Ac, F_bc, F_blb, F_bub, F_Acop, F_mom}; // what the rows kernel writes: the record (nine), the momentum
+constexpr int kNumRecord = 9;
+
+// ---- staging of the host-pointer entry points ---------------------------------------------------------------------------------------------------
+// Their arrays cross in the handle's two device blocks (stage_in, stage_out), on the null stream.  packed: through page-locked memory as ONE copy each
+// way (at batch 1 the copies' fixed cost is most of the call); async: one asynchronous copy per array; blocking: one hipMemcpy per array;
+// blocking_float: the same where the caller's arrays are double and the device's float (wbcqp_solve_dense_host on an F32 handle)
+enum class Xfer { packed, async, blocking, blocking_float };
+
+int stage_begin(wbcqp_handle* h, size_t in_bytes, size_t out_bytes, bool packed)
+{
+    WB_TRY(ensure(h, h->stage_in, in_bytes + 256));
+    WB_TRY(ensure(h, h->stage_out, out_bytes + 256));
+    if (packed) {
+        WB_TRY(ensure_pinned(h, h->pin_in, kPackedBytes));
+        WB_TRY(ensure_pinned(h, h->pin_out, kPackedBytes));
+    }
+    return WBCQP_OK;
+}
+
+inline bool is_real(const Arr& a) { return a.f < 0 || kField[a.f].elem == 0; }
+
+// the arrays the caller has go up into the block at dev (packed: the first block_bytes of it in one copy)
+int stage_up(wbcqp_handle* h, void* dev, const Arr* a, int n, size_t block_bytes, Xfer how)
+{
+    char* d = static_cast<char*>(dev);
+    if (how == Xfer::packed) {
+        char* pin = static_cast<char*>(h->pin_in.host);
+        for (int i = 0; i < n; ++i)
+            if (a[i].bytes && a[i].host) std::memcpy(pin + a[i].off, a[i].host, a[i].bytes);
+        HIP_TRY(h, hipMemcpyAsync(d, pin, block_bytes, hipMemcpyHostToDevice, nullptr));
+        return WBCQP_OK;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!a[i].bytes || !a[i].host) continue;
+        if (how == Xfer::blocking_float && is_real(a[i])) {
+            const double* sd = static_cast<const double*>(a[i].host);
+            std::vector<float> tmp(sd, sd + a[i].bytes / 4);
+            HIP_TRY(h, hipMemcpy(d + a[i].off, tmp.data(), a[i].bytes, hipMemcpyHostToDevice));
+        }
+        else if (how == Xfer::async) HIP_TRY(h, hipMemcpyAsync(d + a[i].off, a[i].host, a[i].bytes, hipMemcpyHostToDevice, nullptr));
+        else HIP_TRY(h, hipMemcpy(d + a[i].off, a[i].host, a[i].bytes, hipMemcpyHostToDevice));
+    }
+    return WBCQP_OK;
+}
+
+// ... and come down from it; packed and (unless sync is false) async end in a synchronisation of the null stream
+int stage_down(wbcqp_handle* h, const void* dev, const Arr* a, int n, size_t block_bytes, Xfer how, bool sync = true)
+{
+    const char* d = static_cast<const char*>(dev);
+    if (how == Xfer::packed) { // one copy down, then the arrays are taken apart on the host
+        char* po = static_cast<char*>(h->pin_out.host);
+        HIP_TRY(h, hipMemcpyAsync(po, d, block_bytes, hipMemcpyDeviceToHost, nullptr));
+        HIP_TRY(h, hipStreamSynchronize(nullptr));
+        for (int i = 0; i < n; ++i)
+            if (a[i].bytes && a[i].host) std::memcpy(a[i].host, po + a[i].off, a[i].bytes);
+        return WBCQP_OK;
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!a[i].bytes || !a[i].host) continue;
+        if (how == Xfer::blocking_float && is_real(a[i])) {
+            std::vector<float> tmp(a[i].bytes / 4);
+            HIP_TRY(h, hipMemcpy(tmp.data(), d + a[i].off, a[i].bytes, hipMemcpyDeviceToHost));
+            std::copy(tmp.begin(), tmp.end(), static_cast<double*>(a[i].host));
+        }
+        else if (how == Xfer::async) HIP_TRY(h, hipMemcpyAsync(a[i].host, d + a[i].off, a[i].bytes, hipMemcpyDeviceToHost, nullptr));
+        else HIP_TRY(h, hipMemcpy(a[i].host, d + a[i].off, a[i].bytes, hipMemcpyDeviceToHost));
+    }
+    if (how == Xfer::async && sync) HIP_TRY(h, hipStreamSynchronize(nullptr));
+    return WBCQP_OK;
+}
+
+// ---- the argument checks the entry points share ---------------------------------------------------------------------------------------------------
+Slot* slot_with_model(wbcqp_handle* h, int slot)
+{
+    if (slot >= 0 && slot < WBCQP_MAX_STRUCTURES && h->slots[slot].set && h->slots[slot].has_model) return &h->slots[slot];
+    fail(h, WBCQP_ERR_INVALID, "slot has no model (wbcqp_set_model)");
+    return nullptr;
+}
+
+int need_state(wbcqp_handle* h, const TermsDev& T, const wbcqp_state* st)
+{
+    if (!st || !st->q || !st->v || (T.nref > 0 && !st->ref)) return fail(h, WBCQP_ERR_INVALID, "state arrays q / v / ref are required");
+    return WBCQP_OK;
+}
+
+int need_rows(wbcqp_handle* h, const wbcqp_layout& L, const wbcqp_inputs* rows)
+{
+    if (!rows->M || !rows->h || (L.len_A && !rows->A) || (L.len_b1 && !rows->b1) || (L.len_Ac && !rows->Ac) || (L.len_bc && !rows->bc) ||
+        (L.len_blb && (!rows->blb || !rows->bub)) || (L.len_Acop && !rows->Acop))
+        return fail(h, WBCQP_ERR_INVALID, "row arrays M, h, A, b1, Ac, bc, blb, bub (Acop with a cop task) are required");
+    return WBCQP_OK;
+}
+
+int need_tick_outputs(wbcqp_handle* h, int na, const wbcqp_outputs& out, const void* q_next, const void* v_next)
+{
+    if (!out.x || !out.status || !out.iters || (na > 0 && !out.tau) || !q_next || !v_next)
+        return fail(h, WBCQP_ERR_INVALID, "x, tau, status, iters, q_next, v_next are required");
+    return WBCQP_OK;
+}
+
+} // namespace

@@ -1,4 +1,4 @@
-"""The compact layout's branches that no shipped stack takes together (csrc/wbcqp_api.hip: derive_compact; csrc/wbcqp_compact.hpp: cp::vec_map,
+"""The compact layout's branches that no shipped stack takes together (csrc/wbcqp_host_derive.hpp: derive_compact; csrc/wbcqp_compact.hpp: cp::vec_map,
 cp::fric_in_j): 64-entry vector slots WITH the actuation-bound slots, an odd n (rows of J padded, not aliased), n = 2 mod 4 with fewer than fourteen
 equalities (rows aliased on the next row's dead columns, the friction table over two rows of J per entry), n = 0 mod 4 (padded rows, friction table in J),
 and a small floating-base stack on one contact (n = 30 < 34: cp::fric_in_j == 0, the friction table BEHIND THE ROTATION TABLE IN THE R REGION -- the
