@@ -50,7 +50,8 @@ extern "C" {
  *        take the factor from there, others compute it as before: the same bits either way (env WBCQP_DEBUG_NO_FFCACHE=1, read at wbcqp_create, turns it off).
  *        Added without a change of version: wbcqp_mix, wbcqp_mixed_io, wbcqp_tick_mixed and wbcqp_rollout_mixed (instances of one robot model in
  *        different contact sets, one call); wbcqp_trace, wbcqp_task_costs, wbcqp_rollout_traced and wbcqp_rollout_mixed_traced (per-task costs on
- *        the device, per-tick results of a roll-out)
+ *        the device, per-tick results of a roll-out); wbcqp_program, wbcqp_track, wbcqp_segment, wbcqp_check_program, wbcqp_reference_samples,
+ *        wbcqp_rollout_program and wbcqp_rollout_mixed_program (the references of a roll-out generated on the device from a reference program)
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -584,6 +585,78 @@ int wbcqp_rollout_traced(wbcqp_handle* handle, int slot, int batch, int n_ticks,
                          void* stream);
 int wbcqp_rollout_mixed_traced(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule,
                                const wbcqp_rollout_io* io, const wbcqp_trace* trace, void* stream);
+
+/* ---- References generated on the device from a reference program ----
+ * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the
+ * caller plans on the host and copies up.  Every behaviour of the reference precomputes its references as streams of consecutive min-jerk moves and holds
+ * and plays one sample per tick (include/inria_wbc/trajs/trajectory_generator.hpp:23-156, src/behaviors/humanoid/move_com.cpp:22-60,
+ * src/behaviors/generic/cartesian.cpp:28-61, src/behaviors/humanoid/walk_on_spot.cpp:40-184); a fleet differs between its robots only in WHEN each starts.
+ * A wbcqp_program is that stream as data -- a few dozen numbers and one start tick per instance -- and refgen_kernel (csrc/wbcqp_refgen.hpp) expands it on the
+ * device, a chunk of ticks per launch, into a ring of two chunks that the rows kernel reads: a roll-out of any length needs neither a host plan nor a
+ * reference array sized by n_ticks.
+ *
+ * Timeline: n_intro ticks played once, then n_cycle ticks repeated (n_cycle = 0: the last sample is held).  Instance i is at behaviour tick
+ * tau = tick0 + t - offset[i] on tick t of a call; the sample played is number 0 for tau < 0, tau for tau < n_intro, else
+ * n_intro + (tau - n_intro) % n_cycle (n_cycle = 0: min(tau, n_intro - 1)).  Every track's segments tile the n_intro + n_cycle samples of the timeline.
+ * Sample i of a segment (T, x0, xf, R0, axis, angle) is the reference's closed form at t = dt i, td = t / T:
+ *     s = 6 td^5 - 15 td^4 + 10 td^3,  pos = x0 + (xf - x0) s,  vel = (xf - x0)(30 td^4 - 60 td^3 + 30 td^2) / T,  acc = (xf - x0)(120 td^3 - 180 td^2 + 60 td) / T^2
+ *     R = R0 Rot(axis, angle s), angular velocity / acceleration R0 (angle s' axis), R0 (angle s'' axis)          (trajectory_generator.hpp:41-59, 80-147)
+ * computed in double whatever the handle's dtype.  A hold is a segment with xf = x0 (angle = 0): it comes out as x0 (R0) bit for bit.  The caller makes
+ * n_steps = floor(T / dt) and (axis, angle) from R0' R1 (Eigen::AngleAxisd(Matrix3d)); the library takes them as given.  The result is a pure function of
+ * (program, offset[i], tick): the same bits whichever chunk, call or sub-batch a tick falls in. */
+#define WBCQP_MAX_TRACKS 16
+typedef enum {
+    WBCQP_TRACK_VEC = 0, /* dim 3: pos 3 | vel 3 | acc 3 at the destination (a CoM task's reference, wbcqp_task.ref); dim 1: one number (a posture entry) */
+    WBCQP_TRACK_SE3 = 1  /* placement 12 (translation, rotation column-major) | velocity 6 | acceleration 6 (an SE3 task's or a contact's reference) */
+} wbcqp_track_kind;
+#define WBCQP_TRACK_POSE_ONLY 1 /* velocity and acceleration are written as zeros (what set_se3_ref(SE3, name) / set_com_ref(Vector3d) leave) */
+#define WBCQP_TRACK_RELATIVE 2  /* translations are added to the position `base` row i holds at dst[0]; an SE3 track's rotation becomes R_base(i) R(t) and
+                                   its angular parts are rotated by R_base(i) (`absolute: false` of move_com.cpp, cartesian.cpp's relative targets) */
+typedef struct {
+    int32_t n_steps;   /* ticks of the segment, >= 1 */
+    double T;          /* its duration, > 0 */
+    double x0[3], xf[3]; /* VEC of dim 1: entry 0 */
+    double R0[9];      /* SE3: rotation at the start, row-major */
+    double axis[3];    /* SE3: unit axis of R0' R1 */
+    double angle;      /* SE3: its angle */
+} wbcqp_segment;
+
+typedef struct {
+    int32_t kind;      /* wbcqp_track_kind */
+    int32_t dim;       /* VEC: 1 or 3 */
+    int32_t flags;     /* WBCQP_TRACK_* */
+    int32_t dst[2];    /* offsets into the reference row; dst[1] < 0: one destination (a foot's stream feeds the foot task AND its contact's reference) */
+    int32_t n_segments;
+    const wbcqp_segment* segments; /* HOST [n_segments], consecutive on the timeline */
+} wbcqp_track;
+
+typedef struct {
+    int32_t nref;          /* length of a reference row = the slot's (the mix's) nref */
+    int32_t base_stride;   /* 1: base is [batch][nref]; 0: [1][nref], one row for every instance */
+    const void* base;      /* DEVICE, the handle's dtype: every entry no track writes, and the origin of the RELATIVE tracks */
+    const int32_t* offset; /* HOST [batch]: the call tick at which instance i starts the behaviour */
+    int32_t n_intro, n_cycle;
+    double dt;             /* sample i of a segment is at t = dt i */
+    int32_t n_tracks;      /* <= WBCQP_MAX_TRACKS */
+    const wbcqp_track* tracks; /* HOST [n_tracks] */
+    const int32_t* set_of; /* HOST [n_intro + n_cycle] or NULL: contact set (index into wbcqp_mix.slots) of every sample; read by wbcqp_rollout_mixed_program only */
+} wbcqp_program;
+
+/* Pure host, no device (like wbcqp_check_model); error text through wbcqp_last_error(NULL).  WBCQP_ERR_INVALID for: more than WBCQP_MAX_TRACKS tracks, an
+ * empty timeline, a track whose segments do not sum to n_intro + n_cycle, n_steps < 1 or T <= 0, a destination whose extent leaves [0, nref), two extents
+ * that overlap, dim outside {1, 3}, a non-unit axis, a set_of entry outside [0, n_slots) (n_slots <= 0: set_of is not looked at). */
+int wbcqp_check_program(const wbcqp_program* prog, int batch, int n_slots);
+/* The expansion alone: ref_out (DEVICE, the handle's dtype) [n_ticks][batch][nref] = the references of call ticks [0, n_ticks) of a call at tick0.
+ * Asynchronous on `stream`.  The tables and offsets go up through a ring of four page-locked buffers (a call waits for the one four calls ago). */
+int wbcqp_reference_samples(wbcqp_handle* handle, const wbcqp_program* prog, int batch, int tick0, int n_ticks, void* ref_out, void* stream);
+/* wbcqp_rollout_traced with the references generated on the device: io->state.ref is not read and may be NULL, trace may be NULL.  The rows are made
+ * WBCQP_REFPROG_CHUNK ticks per launch (environment, read at wbcqp_create; default 32) on the stream of the sub-batch that reads them.  Bit for bit
+ * wbcqp_rollout_traced on the output of wbcqp_reference_samples.  Refusals: those of wbcqp_rollout_traced, then wbcqp_check_program's, then nref. */
+int wbcqp_rollout_program(wbcqp_handle* handle, int slot, int batch, int tick0, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_program* prog,
+                          const wbcqp_trace* trace, void* stream);
+/* wbcqp_rollout_mixed_traced likewise; the schedule is made on the host from set_of (required), offset and tick0. */
+int wbcqp_rollout_mixed_program(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, int tick0, int n_ticks, const wbcqp_rollout_io* io,
+                                const wbcqp_program* prog, const wbcqp_trace* trace, void* stream);
 
 /* The same sequence captured once into a HIP graph and replayed: one graph launch per tick instead of four kernel
  * launches (what matters when the batch is small -- one robot at 1 kHz is the reference's own use case).  The graph is

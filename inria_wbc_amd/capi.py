@@ -29,7 +29,8 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_allgather_tau", "wbcqp_integrate", "wbcqp_integrate_host", "wbcqp_set_model", "wbcqp_check_model", "wbcqp_problem_data",
            "wbcqp_problem_data_host", "wbcqp_tick", "wbcqp_tick_host", "wbcqp_tick_graph_create", "wbcqp_tick_graph_launch", "wbcqp_tick_graph_destroy",
            "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout",
-           "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced")
+           "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced",
+           "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program")
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
 
@@ -138,6 +139,21 @@ class CTrace(C.Structure):
     _fields_ = [("stride", C.c_int32)] + [(k, C.c_void_p) for k in TRACE_FIELDS]
 
 
+class CSegment(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("T", C.c_double), ("x0", C.c_double * 3), ("xf", C.c_double * 3), ("R0", C.c_double * 9),
+                ("axis", C.c_double * 3), ("angle", C.c_double)]
+
+
+class CTrack(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("dim", C.c_int32), ("flags", C.c_int32), ("dst", C.c_int32 * 2), ("n_segments", C.c_int32),
+                ("segments", C.POINTER(CSegment))]
+
+
+class CProgram(C.Structure):
+    _fields_ = [("nref", C.c_int32), ("base_stride", C.c_int32), ("base", C.c_void_p), ("offset", c_i32_p), ("n_intro", C.c_int32),
+                ("n_cycle", C.c_int32), ("dt", C.c_double), ("n_tracks", C.c_int32), ("tracks", C.POINTER(CTrack)), ("set_of", c_i32_p)]
+
+
 def load_library(path: Optional[str] = None):
     """Loads libwbcqp.so -- after torch, when torch is installed: the library links libamdhip64.so.7, and a process in which it comes FIRST gets
     /opt/rocm's HIP runtime while a later `import torch` brings torch's bundled one.  Two runtimes on one GPU work, but the first one then answers
@@ -186,8 +202,55 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_rollout_traced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CTrace), C.c_void_p]
     lib.wbcqp_rollout_mixed_traced.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, c_i32_p, C.POINTER(CRolloutIO), C.POINTER(CTrace),
                                                C.c_void_p]
+    lib.wbcqp_check_program.argtypes = [C.POINTER(CProgram), C.c_int, C.c_int]
+    lib.wbcqp_reference_samples.argtypes = [C.c_void_p, C.POINTER(CProgram), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.wbcqp_rollout_program.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CProgram), C.POINTER(CTrace),
+                                          C.c_void_p]
+    lib.wbcqp_rollout_mixed_program.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CProgram),
+                                                C.POINTER(CTrace), C.c_void_p]
     _lib = lib
     return lib
+
+
+class ProgramBuffers:
+    """Host-side wbcqp_program built from a `refprog.Program` (anything with its attributes), the per-instance start ticks and the base rows (a device
+    tensor [B, nref] or [nref] / [1, nref], or None for the device-free check); keeps the arrays alive."""
+
+    def __init__(self, prog, offsets, base=None):
+        self.offsets = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        self.base = base
+        tracks = (CTrack * max(1, len(prog.tracks)))()
+        self._segs = []
+        for k, t in enumerate(prog.tracks):
+            segs = (CSegment * max(1, len(t.segments)))()
+            for j, g in enumerate(t.segments):
+                segs[j].n_steps, segs[j].T, segs[j].angle = int(g.n_steps), float(g.T), float(g.angle)
+                segs[j].x0[:], segs[j].xf[:] = [float(x) for x in g.x0], [float(x) for x in g.xf]
+                segs[j].R0[:] = [float(x) for x in np.asarray(g.R0).reshape(9)]
+                segs[j].axis[:] = [float(x) for x in g.axis]
+            self._segs.append(segs)
+            tracks[k].kind, tracks[k].dim, tracks[k].flags, tracks[k].n_segments = int(t.kind), int(t.dim), int(t.flags), len(t.segments)
+            tracks[k].dst[:] = [int(t.dst[0]), int(t.dst[1])]
+            tracks[k].segments = C.cast(segs, C.POINTER(CSegment))
+        self._tracks = tracks
+        self.set_of = None if prog.set_of is None else np.ascontiguousarray(prog.set_of, dtype=np.int32)
+        p = CProgram()
+        p.nref, p.n_intro, p.n_cycle, p.dt, p.n_tracks = int(prog.nref), int(prog.n_intro), int(prog.n_cycle), float(prog.dt), len(prog.tracks)
+        p.base = base.data_ptr() if base is not None else None
+        p.base_stride = 1 if base is not None and base.dim() == 2 and base.shape[0] > 1 else 0
+        p.offset = self.offsets.ctypes.data_as(c_i32_p)
+        p.tracks = C.cast(tracks, C.POINTER(CTrack))
+        p.set_of = self.set_of.ctypes.data_as(c_i32_p) if self.set_of is not None else None
+        self.c = p
+
+
+def check_program(prog, batch: int, n_slots: int = 0, offsets=None) -> None:
+    """wbcqp_check_program: validates a reference program on the host -- no GPU needed.  Raises WbcqpError with the library's message otherwise."""
+    lib = load_library()
+    pb = ProgramBuffers(prog, np.zeros(batch, np.int32) if offsets is None else offsets)
+    rc = lib.wbcqp_check_program(C.byref(pb.c), int(batch), int(n_slots))
+    if rc != WBCQP_OK:
+        raise WbcqpError(rc, (lib.wbcqp_last_error(None) or b"").decode())
 
 
 class ModelBuffers:
@@ -536,6 +599,41 @@ class Handle:
         io = self._rollout_io(state, out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok)
         self._check(self.lib.wbcqp_rollout_mixed_traced(self._h, C.byref(mix), int(B), int(K), schedule.ctypes.data_as(c_i32_p), C.byref(io),
                                                         self._trace(trace, stride), C.c_void_p(stream)))
+        del keep
+
+    def reference_samples(self, prog, base, offsets, tick0: int, n_ticks: int, out, stream: int = 0):
+        """The references of call ticks [0, n_ticks) of a call at tick0, written to the device tensor out [n_ticks, B, nref] by refgen_kernel
+        (wbcqp_reference_samples).  prog: a refprog.Program; base: device tensor [B, nref] or [nref]; offsets: host ints [B]."""
+        pb = ProgramBuffers(prog, offsets, base)
+        B = pb.offsets.size
+        assert out.is_contiguous() and out.numel() == n_ticks * B * prog.nref, (tuple(out.shape), n_ticks, B, prog.nref)
+        self._check(self.lib.wbcqp_reference_samples(self._h, C.byref(pb.c), B, int(tick0), int(n_ticks), self._ptr(out), C.c_void_p(stream)))
+        return out
+
+    def rollout_program(self, slot: int, batch: int, tick0: int, n_ticks: int, prog, base, offsets, state, limits, out, q_next, v_next, dt: float,
+                        trace=None, stride: int = 1, q_solver=None, iters_sum=None, ticks_ok=None, stream: int = 0):
+        """rollout_traced() with the references generated on the device from a reference program (wbcqp_rollout_program): state needs q and v
+        only; call tick t plays behaviour tick tick0 + t - offsets[i] of instance i."""
+        st = self._structs[slot]
+        pb = ProgramBuffers(prog, offsets, base)
+        assert pb.offsets.size == batch, (pb.offsets.size, batch)
+        io = self._rollout_io(dict(state, ref=None), out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok)
+        io.tlb = self._ptr(limits.get("tlb")) if st.act_bounds else None
+        io.tub = self._ptr(limits.get("tub")) if st.act_bounds else None
+        io.w = self._ptr(limits.get("w"))
+        self._check(self.lib.wbcqp_rollout_program(self._h, slot, batch, int(tick0), n_ticks, C.byref(io), C.byref(pb.c), self._trace(trace, stride),
+                                                   C.c_void_p(stream)))
+
+    def rollout_mixed_program(self, slots: Sequence[int], batch: int, tick0: int, n_ticks: int, prog, base, offsets, state, w: Sequence, out, q_next,
+                              v_next, dt: float, trace=None, stride: int = 1, tlb=None, tub=None, q_solver=None, iters_sum=None, ticks_ok=None,
+                              stream: int = 0):
+        """rollout_mixed_traced() by program (wbcqp_rollout_mixed_program): the library makes the schedule from prog.set_of, offsets and tick0."""
+        pb = ProgramBuffers(prog, offsets, base)
+        assert pb.offsets.size == batch, (pb.offsets.size, batch)
+        mix, keep = self._mix(slots, w, tlb, tub)
+        io = self._rollout_io(dict(state, ref=None), out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok)
+        self._check(self.lib.wbcqp_rollout_mixed_program(self._h, C.byref(mix), batch, int(tick0), n_ticks, C.byref(io), C.byref(pb.c),
+                                                         self._trace(trace, stride), C.c_void_p(stream)))
         del keep
 
     def tick_host(self, slot: int, q: np.ndarray, v: np.ndarray, ref: np.ndarray, tlb, tub, w, dt: float, want_rows: bool = False):

@@ -7,10 +7,11 @@
 //
 // This file holds the exported entry points; the host code behind them is in the wbcqp_host_*.hpp headers, included here and nowhere else (the library
 // stays ONE translation unit): the handle, the description of a call's arrays and the staging (handle), structure -> sizes and LDS layouts (derive),
-// arguments -> kernel launches (launch), the loops over ticks (rollout).
+// arguments -> kernel launches (launch), reference programs (program), the loops over ticks (rollout).
 #include "wbcqp_host_handle.hpp"
 #include "wbcqp_host_derive.hpp"
 #include "wbcqp_host_launch.hpp"
+#include "wbcqp_host_program.hpp"
 #include "wbcqp_host_rollout.hpp"
 
 namespace {
@@ -131,6 +132,7 @@ int wbcqp_create(const wbcqp_desc* desc, wbcqp_handle** out)
     if (const char* pad = std::getenv("WBCQP_DEBUG_LDS_PAD")) h->lds_pad = std::atoi(pad);
     h->debug_launch = std::getenv("WBCQP_DEBUG_LAUNCH") != nullptr;
     h->no_ffcache = std::getenv("WBCQP_DEBUG_NO_FFCACHE") != nullptr;
+    if (const char* ch = std::getenv("WBCQP_REFPROG_CHUNK")) h->ref_chunk = std::max(1, std::min(std::atoi(ch), 4096));
     *out = h;
     return WBCQP_OK;
 }
@@ -170,6 +172,13 @@ int wbcqp_destroy(wbcqp_handle* h)
     if (h->mix_rec.dev) (void)hipFree(h->mix_rec.dev);
     if (h->mix_state.dev) (void)hipFree(h->mix_state.dev);
     if (h->mix_done) (void)hipEventDestroy(h->mix_done);
+    for (auto& pu : h->prog_up) {
+        if (pu.pin.host) (void)hipHostFree(pu.pin.host);
+        if (pu.dev) (void)hipFree(pu.dev);
+        if (pu.done) (void)hipEventDestroy(pu.done);
+    }
+    if (h->roll_ref.dev) (void)hipFree(h->roll_ref.dev);
+    if (h->mix_ref.dev) (void)hipFree(h->mix_ref.dev);
     delete h;
     return WBCQP_OK;
 }
@@ -669,6 +678,45 @@ int wbcqp_rollout_mixed_traced(wbcqp_handle* h, const wbcqp_mix* mix, int batch,
     if (trace && trace->stride < 1) return fail(h, WBCQP_ERR_INVALID, "trace: stride must be >= 1");
     const MixCall c{mix, batch, n_ticks, schedule, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, io->iters_sum, io->ticks_ok,
                     trace_or_null(trace)};
+    return mixed_call(h, c, stream);
+}
+
+int wbcqp_check_program(const wbcqp_program* prog, int batch, int n_slots) { return check_program(nullptr, prog, batch, n_slots); }
+
+int wbcqp_reference_samples(wbcqp_handle* h, const wbcqp_program* prog, int batch, int tick0, int n_ticks, void* ref_out, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    WB_TRY(check_program(h, prog, batch, 0));
+    if (n_ticks < 0) return fail(h, WBCQP_ERR_INVALID, "negative n_ticks");
+    if (batch == 0 || n_ticks == 0) return WBCQP_OK;
+    if (!prog->base || !ref_out) return fail(h, WBCQP_ERR_INVALID, "program: base / ref_out is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t sm = static_cast<hipStream_t>(stream);
+    ProgDev d;
+    WB_TRY(upload_program(h, prog, batch, sm, d));
+    const int rc = launch_refgen(h, d, batch, 0, batch, tick0, n_ticks, h->ref_chunk, ref_out, sm);
+    HIP_TRY(h, hipEventRecord(d.up->done, sm));
+    return rc;
+}
+
+int wbcqp_rollout_program(wbcqp_handle* h, int slot, int batch, int tick0, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_program* prog,
+                          const wbcqp_trace* trace, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (trace && trace->stride < 1) return fail(h, WBCQP_ERR_INVALID, "trace: stride must be >= 1");
+    const ProgCall pc{prog, tick0};
+    return rollout_impl(h, slot, batch, n_ticks, io, trace_or_null(trace), stream, &pc);
+}
+
+int wbcqp_rollout_mixed_program(wbcqp_handle* h, const wbcqp_mix* mix, int batch, int tick0, int n_ticks, const wbcqp_rollout_io* io,
+                                const wbcqp_program* prog, const wbcqp_trace* trace, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
+    if (trace && trace->stride < 1) return fail(h, WBCQP_ERR_INVALID, "trace: stride must be >= 1");
+    const ProgCall pc{prog, tick0};
+    const MixCall c{mix, batch, n_ticks, nullptr, io->state, io->out, io->q_next, io->v_next, io->q_solver, io->dt, io->iters_sum, io->ticks_ok,
+                    trace_or_null(trace), &pc};
     return mixed_call(h, c, stream);
 }
 

@@ -161,6 +161,20 @@ struct wbcqp_handle {
     int mix_next = 0;
     Staging mix_rec, mix_state;
     hipEvent_t mix_done = nullptr; // end of the previous mixed call: the next one (on whatever stream) waits for it before it reuses the buffers
+    // reference programs (wbcqp_program): the segments and offsets of a call go up through a ring of page-locked buffers, as the mixed calls' plans do; the
+    // rings of generated rows (two chunks of ref_chunk ticks) of the one-slot and of the mixed roll-out; the schedule the mixed one makes on the host
+    struct ProgUp {
+        Pinned pin;
+        void* dev = nullptr;
+        size_t cap = 0; // bytes
+        hipEvent_t done = nullptr;
+        bool used = false;
+    };
+    ProgUp prog_up[4];
+    int prog_next = 0;
+    int ref_chunk = 32; // ticks per launch of refgen_kernel (env WBCQP_REFPROG_CHUNK, read at wbcqp_create)
+    Staging roll_ref, mix_ref;
+    std::vector<int32_t> prog_sched;
 };
 
 namespace {

@@ -3,6 +3,7 @@
 // wbcqp_rollout_mixed_traced) -- with the trace writer and the state ping-pong they share.  Included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_host_launch.hpp"
+#include "wbcqp_host_program.hpp"
 
 namespace {
 
@@ -75,7 +76,27 @@ int tick_impl(wbcqp_handle* h, int slot, int batch, const wbcqp_tick_io* io, voi
                           io->out.status, io->q_next, io->v_next, io->q_solver, stream, acc);
 }
 
-int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_trace* tr, void* stream)
+// need_state for a call whose references may come from a program (then state.ref is not read)
+int need_state_or_program(wbcqp_handle* h, const TermsDev& T, const wbcqp_state* st, const ProgCall* pc)
+{
+    if (!pc) return need_state(h, T, st);
+    if (!st->q || !st->v) return fail(h, WBCQP_ERR_INVALID, "state arrays q / v are required");
+    return WBCQP_OK;
+}
+
+// the refusals of a roll-out by program that follow the plain call's: wbcqp_check_program's, then nref and base
+int check_program_call(wbcqp_handle* h, const ProgCall& pc, int batch, int n_slots, int nref)
+{
+    WB_TRY(check_program(h, pc.prog, batch, n_slots));
+    if (pc.prog->nref != nref)
+        return fail(h, WBCQP_ERR_INVALID, "program: nref " + std::to_string(pc.prog->nref) + " is not the slot's " + std::to_string(nref));
+    if (!pc.prog->base) return fail(h, WBCQP_ERR_INVALID, "program: base is NULL");
+    return WBCQP_OK;
+}
+
+// pc: the references come from a program (wbcqp_rollout_program); null: from io->state.ref
+int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_rollout_io* io, const wbcqp_trace* tr, void* stream,
+                 const ProgCall* pc = nullptr)
 {
     if (!h) return WBCQP_ERR_INVALID;
     if (!io) return fail(h, WBCQP_ERR_INVALID, "io is NULL");
@@ -87,9 +108,10 @@ int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_
     if (batch == 0 || n_ticks == 0) return WBCQP_OK;
     const Slot& s = *sp;
     const wbcqp_layout& L = s.layout;
-    WB_TRY(need_state(h, s.terms, &io->state));
+    WB_TRY(need_state_or_program(h, s.terms, &io->state, pc));
     if ((L.len_tlb && (!io->tlb || !io->tub)) || !io->w) return fail(h, WBCQP_ERR_INVALID, "tlb / tub / w are required");
     WB_TRY(need_tick_outputs(h, s.host.na, io->out, io->q_next, io->v_next));
+    if (pc) WB_TRY(check_program_call(h, *pc, batch, 0, s.terms.nref));
     HIP_TRY(h, hipSetDevice(h->device));
     hipStream_t sm = static_cast<hipStream_t>(stream);
     const size_t es = elem_size(h);
@@ -168,12 +190,14 @@ int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_
     const size_t rec_bytes = lay(fb, B, kRecordFields, kNumRecord, Io{}, rec_a);
     const size_t qb = al256(B * fb.b[F_q]), vb = al256(B * fb.b[F_v]);
     const int sub_cap = (batch + S - 1) / S;
-    bool grow = h->roll_rec.bytes < rec_bytes || h->roll_state.bytes < PingPong::bytes(qb, vb);
+    const size_t ring_bytes = pc ? RefFeed::ring_bytes(B, fb.b[F_ref], h->ref_chunk) : 0;
+    bool grow = h->roll_rec.bytes < rec_bytes || h->roll_state.bytes < PingPong::bytes(qb, vb) || h->roll_ref.bytes < ring_bytes;
     for (int k = 0; k < S; ++k) grow = grow || h->roll_subs[k].ord.cap < sub_cap;
     if (grow) { // first call of a larger shape: nothing of an earlier call may still be running on what is replaced
         HIP_TRY(h, hipDeviceSynchronize());
         WB_TRY(ensure(h, h->roll_rec, rec_bytes));
         WB_TRY(ensure(h, h->roll_state, PingPong::bytes(qb, vb)));
+        WB_TRY(ensure(h, h->roll_ref, ring_bytes));
         for (int k = 0; k < S; ++k) {
             OrderState& os = h->roll_subs[k].ord;
             if (os.cap < sub_cap) {
@@ -197,6 +221,8 @@ int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_
         if (!meas->t1) HIP_TRY(h, hipEventCreate(&meas->t1));
         HIP_TRY(h, hipEventRecord(meas->t0, sm));
     }
+    ProgDev prog_dev; // the program's tables go up on the caller's stream, ahead of roll_start: every sub-batch's stream sees them
+    if (pc) WB_TRY(upload_program(h, pc->prog, batch, sm, prog_dev));
     HIP_TRY(h, hipEventRecord(h->roll_start, sm));
     int rc_all = WBCQP_OK;
     // one sub-batch: the ticks go out on the caller's own stream with that stream's launch-order state -- K calls of wbcqp_tick, minus
@@ -209,13 +235,16 @@ int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_
     Io call(nullptr, &io->out, &io->state, io->q_next, io->v_next, io->q_solver);
     call.p[F_tlb] = const_cast<void*>(io->tlb); call.p[F_tub] = const_cast<void*>(io->tub); call.p[F_w] = const_cast<void*>(io->w);
     point(call, h->roll_rec.dev, rec_a, kNumRecord);
+    // tick t's references: the caller's array, or the ring a chunk of generated rows ahead
+    const RefFeed feed = pc ? RefFeed{static_cast<char*>(h->roll_ref.dev), fb.b[F_ref], B, n_ticks, h->ref_chunk, &prog_dev, pc->tick0}
+                            : RefFeed{static_cast<char*>(call.p[F_ref]), fb.b[F_ref], B, n_ticks};
     Io tick = call;
     // tick t of every sub-batch is enqueued before tick t + 1 of any: the streams then advance together on the device (enqueued one
     // sub-batch after the other, the last stream's first tick would reach the device when the first stream is almost through), and the
     // tail of one sub-batch's solve (its longest QP) runs beside the bulk of another's
     for (int t = 0; t < n_ticks && rc_all == WBCQP_OK; ++t) {
         const bool last = t + 1 == n_ticks;
-        if (call.p[F_ref]) tick.p[F_ref] = static_cast<char*>(call.p[F_ref]) + (size_t)t * B * fb.b[F_ref];
+        tick.p[F_ref] = feed.at(t);
         tick.p[F_qn] = tw.dest(t, F_qn, fb.b[F_qn], last ? io->q_next : pp.q(t + 1));
         tick.p[F_vn] = tw.dest(t, F_vn, fb.b[F_vn], last ? io->v_next : pp.v(t + 1));
         for (Field f : {F_x, F_tau, F_obj, F_status, F_iters}) tick.p[f] = tw.dest(t, f, fb.b[f], call.p[f]);
@@ -227,6 +256,7 @@ int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_
             if (nb == 0) continue;
             wbcqp_handle::RollSub& sub = h->roll_subs[k];
             const wbcqp_tick_io d = tick.from(b0, fb).tick_io(io->dt);
+            if ((rc_all = feed.prepare(h, t, (int)b0, nb, own_stream ? sm : sub.stream)) != WBCQP_OK) break;
             h->graph_ord = own_stream ? nullptr : &sub.ord; // a sub-batch's own launch-order state and queue counter (as a captured tick has)
             const RollAcc acc = {d.out.iters, io->iters_sum ? io->iters_sum + b0 : nullptr, io->ticks_ok ? io->ticks_ok + b0 : nullptr, t == 0 ? 1 : 0};
             rc_all = tick_impl(h, slot, nb, &d, own_stream ? sm : sub.stream, acc); // (the per-instance totals ride along with the integration)
@@ -243,6 +273,7 @@ int rollout_impl(wbcqp_handle* h, int slot, int batch, int n_ticks, const wbcqp_
         HIP_TRY(h, hipStreamWaitEvent(sm, h->roll_subs[k].done, 0));
     }
     if (rc_all == WBCQP_OK) rc_all = tw.finish(h, call, fb, sm);
+    if (pc) HIP_TRY(h, hipEventRecord(prog_dev.up->done, sm));
     HIP_TRY(h, hipEventRecord(h->roll_done, sm));
     if (meas && rc_all == WBCQP_OK) {
         HIP_TRY(h, hipEventRecord(meas->t1, sm));
@@ -266,6 +297,7 @@ struct MixCall { // the checked arguments of a mixed call
     double dt;
     int32_t *iters_sum, *ticks_ok;
     const wbcqp_trace* trace; // null: untraced
+    const ProgCall* prog = nullptr; // the references come from a program and `which` is made from its set_of (wbcqp_rollout_mixed_program)
 };
 
 int check_mix(wbcqp_handle* h, const MixCall& c)
@@ -289,9 +321,9 @@ int check_mix(wbcqp_handle* h, const MixCall& c)
     }
     if (c.batch < 0 || c.n_ticks < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch / n_ticks");
     if (c.batch == 0 || c.n_ticks == 0) return WBCQP_OK;
-    if (!c.which) return fail(h, WBCQP_ERR_INVALID, "which / schedule is NULL");
+    if (!c.which && !c.prog) return fail(h, WBCQP_ERR_INVALID, "which / schedule is NULL");
     bool used[kMaxGroups] = {};
-    const size_t N = (size_t)c.batch * c.n_ticks;
+    const size_t N = c.which ? (size_t)c.batch * c.n_ticks : 0; // (a call by program comes here twice: before its schedule exists, and with it)
     for (size_t e = 0; e < N; ++e) {
         const int k = c.which[e];
         if (k < 0 || k >= mix->n_slots)
@@ -304,7 +336,7 @@ int check_mix(wbcqp_handle* h, const MixCall& c)
         if (s.layout.len_w > 0 && !mix->w[k]) return fail(h, WBCQP_ERR_INVALID, "mix: w of slot " + std::to_string(mix->slots[k]) + " is NULL and instances use it");
         if (s.layout.len_tlb > 0 && (!mix->tlb || !mix->tub)) return fail(h, WBCQP_ERR_INVALID, "mix: tlb / tub are required (a slot in use has actuation bounds)");
     }
-    WB_TRY(need_state(h, s0->terms, &c.state));
+    WB_TRY(need_state_or_program(h, s0->terms, &c.state, c.prog));
     return need_tick_outputs(h, s0->terms.na, c.out, c.q_next, c.v_next);
 }
 
@@ -349,7 +381,8 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
     if (!P.done) HIP_TRY(h, hipEventCreateWithFlags(&P.done, hipEventDisableTiming));
     const bool had_mix = h->mix_done != nullptr;
     if (!h->mix_done) HIP_TRY(h, hipEventCreateWithFlags(&h->mix_done, hipEventDisableTiming));
-    if (P.cap < plan_ints || h->mix_rec.bytes < rec_bytes || h->mix_state.bytes < state_bytes) {
+    const size_t ring_bytes = c.prog ? RefFeed::ring_bytes((size_t)B, fb.b[F_ref], h->ref_chunk) : 0;
+    if (P.cap < plan_ints || h->mix_rec.bytes < rec_bytes || h->mix_state.bytes < state_bytes || h->mix_ref.bytes < ring_bytes) {
         // first call of a larger shape: nothing of an earlier call may still be running on what is replaced
         HIP_TRY(h, hipDeviceSynchronize());
         if (P.cap < plan_ints) {
@@ -361,6 +394,7 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
         }
         WB_TRY(ensure(h, h->mix_rec, rec_bytes));
         if (state_bytes) WB_TRY(ensure(h, h->mix_state, state_bytes));
+        WB_TRY(ensure(h, h->mix_ref, ring_bytes));
     }
     WB_TRY(ensure_pinned(h, P.pin, plan_ints * sizeof(int)));
     int* perm_h = static_cast<int*>(P.pin.host);
@@ -380,12 +414,17 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
     if (had_mix) HIP_TRY(h, hipStreamWaitEvent(sm, h->mix_done, 0)); // the previous mixed call is done with the records and the ping-pong
     HIP_TRY(h, hipMemcpyAsync(P.dev, perm_h, plan_ints * sizeof(int), hipMemcpyHostToDevice, sm));
     P.used = true;
+    ProgDev prog_dev;
+    if (c.prog) WB_TRY(upload_program(h, c.prog->prog, B, sm, prog_dev));
+    const RefFeed feed = c.prog ? RefFeed{static_cast<char*>(h->mix_ref.dev), fb.b[F_ref], (size_t)B, c.n_ticks, h->ref_chunk, &prog_dev, c.prog->tick0}
+                                : RefFeed{static_cast<char*>(call.p[F_ref]), fb.b[F_ref], (size_t)B, c.n_ticks};
     char* rec = static_cast<char*>(h->mix_rec.dev);
     const PingPong pp{static_cast<char*>(h->mix_state.dev), qb, vb};
     Io tick = call; // the arrays of one tick, by instance: the state it starts from and the one it leaves, the outputs' destinations
     for (int t = 0; t < c.n_ticks; ++t) {
         const bool last = t + 1 == c.n_ticks;
-        tick.p[F_ref] = static_cast<TI*>(call.p[F_ref]) + (size_t)t * B * T0.nref;
+        tick.p[F_ref] = feed.at(t);
+        WB_TRY(feed.prepare(h, t, 0, B, sm));
         tick.p[F_mom] = last ? call.p[F_mom] : nullptr;
         tick.p[F_qn] = tw.dest(t, F_qn, fb.b[F_qn], last ? c.q_next : pp.q(t));
         tick.p[F_vn] = tw.dest(t, F_vn, fb.b[F_vn], last ? c.v_next : pp.v(t));
@@ -449,15 +488,24 @@ int mixed_run(wbcqp_handle* h, const MixCall& c, hipStream_t sm)
         tick.p[F_v] = tick.p[F_vn];
     }
     WB_TRY(tw.finish(h, call, fb, sm));
+    if (c.prog) HIP_TRY(h, hipEventRecord(prog_dev.up->done, sm));
     HIP_TRY(h, hipEventRecord(P.done, sm));
     HIP_TRY(h, hipEventRecord(h->mix_done, sm));
     return WBCQP_OK;
 }
 
-int mixed_call(wbcqp_handle* h, const MixCall& c, void* stream)
+int mixed_call(wbcqp_handle* h, const MixCall& c0, void* stream)
 {
-    int rc = check_mix(h, c);
-    if (rc != WBCQP_OK || c.batch == 0 || c.n_ticks == 0) return rc;
+    int rc = check_mix(h, c0);
+    if (rc != WBCQP_OK || c0.batch == 0 || c0.n_ticks == 0) return rc;
+    MixCall c = c0;
+    if (c.prog) { // the program's refusals, then the schedule from its set_of and what the plain call checks of a schedule
+        WB_TRY(check_program_call(h, *c.prog, c.batch, c.mix->n_slots, h->slots[c.mix->slots[0]].terms.nref));
+        if (!c.prog->prog->set_of) return fail(h, WBCQP_ERR_INVALID, "program: a mixed roll-out needs set_of");
+        program_schedule(c.prog->prog, c.batch, c.prog->tick0, c.n_ticks, h->prog_sched);
+        c.which = h->prog_sched.data();
+        WB_TRY(check_mix(h, c));
+    }
     HIP_TRY(h, hipSetDevice(h->device));
     return with_dtype(h, [&](auto tag) -> int { return mixed_run<WB_TI(tag)>(h, c, static_cast<hipStream_t>(stream)); });
 }

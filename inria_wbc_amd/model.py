@@ -819,6 +819,14 @@ class WalkOnSpotPlan:
                   ("LIFT_UP_RF", const(lf_low, nf), mj(rf_low, rf_low + up, nf, Tf), const(com_lf, nf), np.full(nf, no_r)),
                   ("LIFT_DOWN_RF", const(lf_low, nf), mj(rf_low + up, rf_low, nf, Tf), const(com_lf, nf), lift(nf, no_r, True)),
                   ("MOVE_COM_RIGHT", const(lf_low, nc), const(rf_low, nc), mj(com_lf, com_rf, nc, Tc), np.full(nc, both))]
+        # the same streams as moves (start, end, duration, ticks), phase by phase: what refprog.walk_on_spot_program turns into segments
+        up_l, up_r = lf_low + up, rf_low + up
+        self.moves = {"lf": [(lf_low, lf_low, Tc, nc), (lf_low, up_l, Tf, nf), (up_l, lf_low, Tf, nf), (lf_low, lf_low, Tc, nc),
+                             (lf_low, lf_low, Tf, nf), (lf_low, lf_low, Tf, nf), (lf_low, lf_low, Tc, nc)],
+                      "rf": [(rf_low, rf_low, Tc, nc), (rf_low, rf_low, Tf, nf), (rf_low, rf_low, Tf, nf), (rf_low, rf_low, Tc, nc),
+                             (rf_low, up_r, Tf, nf), (up_r, rf_low, Tf, nf), (rf_low, rf_low, Tc, nc)],
+                      "com": [(com_init, com_rf, Tc, nc), (com_rf, com_rf, Tf, nf), (com_rf, com_rf, Tf, nf), (com_rf, com_lf, Tc, nc),
+                              (com_lf, com_lf, Tf, nf), (com_lf, com_lf, Tf, nf), (com_lf, com_rf, Tc, nc)]}
         self.phase_names = [p[0] for p in phases]
         self.phase_len = [len(p[4]) for p in phases]
         self.lf_pos = np.concatenate([p[1] for p in phases])

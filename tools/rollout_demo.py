@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Closed-loop squat of a batch of Talos-like robots, every tick on the device (rows -> QP -> integration through wbcqp_tick),
 the CoM reference following etc/talos/squat.yaml's stream.  Prints the CoM height of robot 0 against its reference and the
-tick rate.  Usage (GPU box): python tools/rollout_demo.py [--batch 1024] [--ticks 2000]"""
+tick rate.  Usage (GPU box): python tools/rollout_demo.py [--batch 1024] [--ticks 2000] [--desync] [--rollout]
+--rollout runs the same squat as ONE wbcqp_rollout_program call (the stream as a reference program, a trace entry every 250 ticks)."""
 import argparse
 import os
 import sys
@@ -19,6 +20,7 @@ def main():
     ap.add_argument("--ticks", type=int, default=2000)
     ap.add_argument("--flags", type=lambda x: int(x, 0), default=0, help="wbcqp_desc.flags (launch-order variants, include/wbcqp.h)")
     ap.add_argument("--desync", action="store_true", help="every robot at its own phase of the squat (iteration counts spread and drift)")
+    ap.add_argument("--rollout", action="store_true", help="all the ticks in one wbcqp_rollout_program call: the references generated on the device")
     args = ap.parse_args()
     import torch
     from inria_wbc_amd import capi, structure, trajs
@@ -46,6 +48,26 @@ def main():
     stream9 = torch.from_numpy(np.concatenate([pos, vel, acc], axis=1)).to(dev)
     sp = torch.cuda.current_stream().cuda_stream
     phase = torch.from_numpy(np.random.default_rng(5).integers(0, stream9.shape[0], B)).to(dev) if args.desync else None
+    if args.rollout:  # all the ticks in ONE call: the squat as a reference program, every robot's phase as its start offset
+        from inria_wbc_amd import refprog
+        prog = refprog.move_com_program(tm.nref, blk.ref, m.com(m.q0), [[0.0, 0.0, -0.2]], "001", dt, 2.0, loop=True, absolute=False)
+        offsets = -phase.cpu().numpy() if phase is not None else np.zeros(B, np.int64)
+        n_rec = args.ticks // 250
+        trace = dict(q=torch.zeros(n_rec, B, m.nq, dtype=torch.float64, device=dev), iters=torch.zeros(n_rec, B, dtype=torch.int32, device=dev),
+                     status=torch.zeros(n_rec, B, dtype=torch.int32, device=dev)) if n_rec else None
+        t0 = time.perf_counter()
+        h.rollout_program(0, B, 0, args.ticks, prog, ref, offsets, dict(q=q, v=v), rows, out, qn, vn, dt, trace=trace, stride=250, stream=sp)
+        torch.cuda.synchronize()
+        el = time.perf_counter() - t0
+        for r in range(n_rec):
+            k = 250 * (r + 1) - 1
+            print("tick %5d  CoM z of robot 0: %.4f  (reference %.4f)  mean iterations %.2f  non-optimal %d" %
+                  (k + 1, m.com(trace["q"][r, 0].cpu().numpy())[2], pos[(k - int(offsets[0])) % pos.shape[0]][2], trace["iters"][r].float().mean().item(),
+                   int((trace["status"][r] != 0).sum().item())))
+        print("%d robots x %d ticks in %.2f s, one wbcqp_rollout_program call: %.2f M ticks/s (a 1 kHz controller for %d robots needs %.2f M)" %
+              (B, args.ticks, el, B * args.ticks / el / 1e6, B, B * 1e-3))
+        h.close()
+        return
     t0 = time.perf_counter()
     for k in range(args.ticks):
         if phase is None:
