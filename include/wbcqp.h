@@ -154,11 +154,13 @@ typedef struct {
     /* element counts of the per-QP input arrays below */
     int32_t len_M, len_h, len_A, len_b1, len_Ac, len_bc, len_blb, len_bub, len_tlb, len_tub, len_w;
     int32_t lds_bytes;         /* dynamic LDS one QP (one 256-thread workgroup) needs */
-    int32_t waves_per_cu;      /* resident QPs (workgroups) per CU a launch of THIS structure alone runs with by default: 1 (full layout), 2 (compact
-                                  layout: the kernels' registers admit two), or 3 -- compact layout, NO actuation bounds, 40 KB <= lds_bytes <= 54592:
-                                  such launches take the queue kernel compiled for three waves per SIMD (iCub on one or two feet).  A launch falls
-                                  back to two per CU under WBCQP_FLAG_WARM_START, WBCQP_FLAG_HW_DISPATCH, env WBCQP_DEBUG_LDS_PAD, or when it is ragged
-                                  and any of its groups has actuation bounds; env WBCQP_DEBUG_LAUNCH=1 prints the residency of every launch */
+    int32_t waves_per_cu;      /* resident QPs (workgroups) per CU a launch of THIS structure alone runs with on a handle without flags: 1 (full
+                                  layout), 2 (compact layout: the kernels' registers admit two), or 3 where the launch takes the queue kernel compiled
+                                  for three waves per SIMD.  That is the library's one choosing function asked about this structure (choose_kernel,
+                                  csrc/wbcqp_host_handle.hpp): the kernel the structure runs has such a twin (the generic compact kernel and iCub's),
+                                  no WBCQP_FLAG_WARM_START, no group of the launch has actuation bounds, lds_bytes <= 54592 and no
+                                  WBCQP_DEBUG_LDS_PAD -- and the launch goes through the queue: lds_bytes >= 40 KB and no WBCQP_FLAG_HW_DISPATCH
+                                  (iCub on one or two feet).  env WBCQP_DEBUG_LAUNCH=1 prints the residency of every launch */
     int64_t algorithmic_bytes; /* compact in+out bytes per QP at WBCQP_F64 */
     int32_t wave_per_qp;       /* 1: the structure runs one WAVEFRONT per QP (n <= 16, fixed base, no contacts, bounds only: Franka, Tiago),
                                   four QPs per workgroup, 7.7 KB of LDS per QP; lds_bytes / waves_per_cu then describe the four-wave

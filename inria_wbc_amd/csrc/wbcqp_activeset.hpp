@@ -279,25 +279,86 @@ __device__ __forceinline__ void delete_constraint(Ctx& c, int l)
     bsync();
 }
 
-// Builds the normal np of equality row i (CE.row(i)) in LDS; returns its support and ce0(i). No barrier.
-__device__ __forceinline__ void build_eq_row(Ctx& c, int i, int& k0, int& k1, double& ce0)
+// an equality row staged in c.np: its support [k0, k1) and ce0(i)
+struct EqRow { int k0, k1; double ce0; };
+// Builds the normal np of equality row i (CE.row(i)) of a task stack in LDS; returns its support and ce0(i). No barrier.
+__device__ __forceinline__ EqRow build_eq_row(Ctx& c, int i)
 {
     const int nv = c.nv, k = c.k, nu = c.nu, tid = c.tid;
     if (i < nu) {
         // base dynamics [M_u | -J_u'] x = -h_u
         if (tid < nv) c.np[tid] = c.M[i * c.ldm + tid];
         else if (tid < nv + k) c.np[tid] = -c.Jc[(tid - nv) * c.ldc + i];
-        k0 = 0;
-        k1 = c.n;
-        ce0 = c.h[i];
+        return EqRow{0, c.n, c.h[i]};
     }
-    else {
-        const int rr = i - nu; // contact*6 + row
-        if (tid < nv) c.np[tid] = c.Ac[rr * nv + tid];
-        k0 = 0;
-        k1 = nv;
-        ce0 = -c.bc[rr];
+    const int rr = i - nu; // contact*6 + row
+    if (tid < nv) c.np[tid] = c.Ac[rr * nv + tid];
+    return EqRow{0, nv, -c.bc[rr]};
+}
+
+// The equalities one by one, in eiquadprog's order (where the blocked phase of wbcqp_equality.hpp does not apply).  stage(i) writes row i into c.np
+// (no barrier) and returns its EqRow; then the step along z that satisfies the row, and add_constraint.  Returns false at the first
+// (numerically) redundant equality.
+template <typename F>
+__device__ __forceinline__ bool equality_phase_sequential(Ctx& c, double& f_value, F stage)
+{
+    const int n = c.n, neq = c.neq, tid = c.tid;
+    for (int i = 0; i < neq; ++i) {
+        const EqRow row = stage(i);
+        const int k0 = row.k0, k1 = row.k1;
+        bsync();
+        compute_d(c, k0, k1);
+        STAMP(5)
+        update_z_r(c, 0);
+        STAMP(6)
+        double zz = 0.0, znp = 0.0, npx = 0.0, dn2 = 0.0;
+        if (tid < n) {
+            const double zv = c.z[tid];
+            zz = zv * zv;
+            if (tid >= c.iq) dn2 = c.d[tid] * c.d[tid];
+            if (tid >= k0 && tid < k1) {
+                const double nv_ = c.np[tid];
+                znp = zv * nv_;
+                npx = nv_ * c.x[tid];
+            }
+        }
+        block_sum4(c, zz, znp, npx, dn2);
+        double t2 = 0.0;
+        if (fabs(zz) > 2.220446049250313e-16) t2 = (-npx - row.ce0) / znp;
+        const int iq = c.iq;
+        if (tid < n) c.x[tid] = fma(t2, c.z[tid], c.x[tid]);
+        if (tid >= 128 && tid - 128 < iq) c.u[tid - 128] = fma(-t2, c.r[tid - 128], c.u[tid - 128]);
+        if (tid == kThreads - 1) {
+            c.u[iq] = t2;
+            c.A[i] = -i - 1;
+        }
+        f_value += 0.5 * (t2 * t2) * znp;
+        STAMP(7)
+        const bool ok = add_constraint_hh(c, dn2);
+        STAMP(8)
+        if (!ok) return false;
     }
+    return true;
+}
+
+// After a constraint ip that turned out numerically dependent: take it out again (and out of this pick's candidates), back to the iterate saved at
+// the top of the iteration -- x, u, A and, from A, iai over the nin one-sided rows; the caller picks another row.  Ends with a barrier.
+__device__ __forceinline__ void restore_after_dependent(Ctx& c, int ip, int nin)
+{
+    const int tid = c.tid, n = c.n;
+    if (tid == 0) c.iaexcl[ip] = 0;
+    bsync();
+    delete_constraint(c, ip);
+    for (int i = tid; i < nin; i += kThreads) c.iai[i] = i;
+    bsync();
+    for (int i = tid; i < c.iq; i += kThreads) {
+        const int av = c.Aold[i];
+        c.A[i] = av;
+        if (av >= 0) c.iai[av] = -1;
+        c.u[i] = c.uold[i];
+    }
+    for (int i = tid; i < n; i += kThreads) c.x[i] = c.xold[i];
+    bsync();
 }
 
 // What one thread keeps about the (at most two) rows of s it owns: rows tid and tid + 256

@@ -19,7 +19,7 @@ namespace {
 template <typename TI>
 int solve_ragged(wbcqp_handle* h, int n_groups, const wbcqp_group* groups, hipStream_t hs)
 {
-    int total = 0, lds = 0, used = 0, total_small = 0, used_small = 0;
+    int total = 0, lds = 0, used = 0, total_small = 0, used_small = 0, spec = 0;
     GroupTable<TI> tab{}, tab_small{};
     const bool wave_per_qp = !(h->flags & WBCQP_FLAG_WORKGROUP_PER_QP) && !h->dbg; // (the stamped diagnostic build profiles the four-wave kernels)
     // the compact kernel runs a launch whose groups are all eligible; one group that is not puts the launch on the full layout
@@ -51,6 +51,7 @@ int solve_ragged(wbcqp_handle* h, int n_groups, const wbcqp_group* groups, hipSt
         fill_group(tab.g[used], s, compact, G.batch, &G.in, &G.out);
         tab.g[used].dbg = h->dbg;
         tab.g[used].warm = (h->flags & WBCQP_FLAG_WARM_START) ? 1 : 0;
+        spec = s.spec; // (what choose_kernel makes of it where this group stays the only one)
         ++used;
         total += G.batch;
         const int need = compact ? s.lds_cp : s.lds_full;
@@ -60,20 +61,9 @@ int solve_ragged(wbcqp_handle* h, int n_groups, const wbcqp_group* groups, hipSt
     tab_small.n = used_small;
     if (h->lds_pad > 0) lds = std::min(lds + h->lds_pad, 160 * 1024);
     if (total_small > 0) WB_TRY(launch_small<TI>(h, tab_small, total_small, hs));
-    // a launch of ONE group whose structure is a shipped stack takes that stack's instantiation of the compact kernel (sizes and offsets as
-    // literals: wbcqp_types.hpp); anything else -- ragged launches, other structures, WBCQP_FLAG_GENERIC_KERNEL -- the generic one.  Same bits.
-    int spec = 0;
-    if (compact && used == 1 && !(h->flags & WBCQP_FLAG_GENERIC_KERNEL) && h->lds_pad == 0)
-        for (int g = 0; g < n_groups; ++g)
-            if (groups[g].batch > 0 && !(wave_per_qp && h->slots[groups[g].slot].small)) spec = h->slots[groups[g].slot].spec;
-    if ((h->flags & WBCQP_FLAG_WARM_START) && spec > 1) spec = 0; // the hint's code lives in the generic kernel and Talos's (kWarm)
-    if (!compact) return launch<TI, false>(h, tab, total, lds, hs);
-    switch (spec) {
-    case 1: return launch<TI, true, 1>(h, tab, total, lds, hs);
-    case 2: return launch<TI, true, 2>(h, tab, total, lds, hs);
-    case 3: return launch<TI, true, 3>(h, tab, total, lds, hs);
-    default: return launch<TI, true>(h, tab, total, lds, hs);
-    }
+    const LaunchTable lt = launch_table(tab);
+    const KernelChoice c = choose_kernel(LaunchFacts{compact, lds, lt.act_bounds, spec, used == 1}, h->flags, h->lds_pad);
+    return launch(h, kernel_set<TI>(c.variant), c, lt, total, lds, hs);
 }
 
 } // namespace
@@ -94,8 +84,8 @@ int wbcqp_layout_of(const wbcqp_structure* st, wbcqp_layout* out)
     if (rc != WBCQP_OK) return fail(nullptr, rc, why);
     DevStruct C;
     if (derive_compact(D, C)) {
-        set_lds(L, C.lds_doubles * 8, true, C.act_bounds != 0);
         L.specialised = spec_of(C);
+        set_lds(L, C.lds_doubles * 8, true, C.act_bounds != 0, L.specialised);
     }
     // how a row of kSpecDims (wbcqp_types.hpp) is made: the derived sizes and offsets of a stack, in the order of struct Dims
     if (std::getenv("WBCQP_DEBUG_DUMP_STRUCT") && C.compact)
@@ -128,7 +118,6 @@ int wbcqp_create(const wbcqp_desc* desc, wbcqp_handle** out)
     h->dtype = desc->dtype;
     h->flags = desc->flags;
     h->n_cu = prop.multiProcessorCount;
-    for (int& q : h->queue_lds) q = -1;
     if (const char* pad = std::getenv("WBCQP_DEBUG_LDS_PAD")) h->lds_pad = std::atoi(pad);
     h->debug_launch = std::getenv("WBCQP_DEBUG_LAUNCH") != nullptr;
     h->no_ffcache = std::getenv("WBCQP_DEBUG_NO_FFCACHE") != nullptr;
@@ -272,7 +261,7 @@ int wbcqp_set_structure(wbcqp_handle* h, int slot, const wbcqp_structure* st)
     s.host_cp = DevStruct{};
     if (!(h->flags & WBCQP_FLAG_FULL_LDS) && derive_compact(D, s.host_cp)) {
         s.lds_cp = s.host_cp.lds_doubles * 8;
-        set_lds(L, s.lds_cp, true, s.host_cp.act_bounds != 0);
+        set_lds(L, s.lds_cp, true, s.host_cp.act_bounds != 0, spec_of(s.host_cp));
         if (nc > 0 && !h->no_ffcache) { // room for the force blocks' factor (DevStruct::ffc), invalid (weight NaN) until the slot's first launch makes it
             std::vector<double> init((size_t)nc * kFfcStride, 0.0);
             for (int c = 0; c < nc; ++c) init[(size_t)c * kFfcStride] = std::numeric_limits<double>::quiet_NaN();

@@ -52,22 +52,10 @@ __global__ __launch_bounds__(kThreads) void solve_dense_kernel(const DenseArgs a
     c.nv = n; c.na = 0; c.nc = 0; c.k = 0; c.n = n; c.nu = 0; c.neq = neq; c.nin2 = nin; c.ldj = ldj; c.ldm = 0; c.ldc = 0; c.ldb = 0;
     c.J = lds + a.o_J; c.R = lds + a.o_R;
     c.M = c.Jc = c.Ac = nullptr;
-    {
-        double* vec = lds + a.o_vec;
-        c.h = vec + V_H * kSlot; c.x = vec + V_X * kSlot; c.np = vec + V_NP * kSlot; c.d = vec + V_D * kSlot;
-        c.z = vec + V_Z * kSlot; c.xold = vec + V_XOLD * kSlot; c.r = vec + V_R * kSlot; c.u = vec + V_U * kSlot;
-        c.uold = vec + V_UOLD * kSlot; c.q = vec + V_Q * kSlot; c.g = vec + V_G * kSlot; c.w = vec + V_W * kSlot;
-        c.wrow = vec + V_WROW * kSlot; c.blb = vec + V_BLB * kSlot; c.bub = vec + V_BUB * kSlot; c.tl = vec + V_TL * kSlot;
-        c.tu = vec + V_TU * kSlot; c.bc = vec + V_BC * kSlot; c.rdinv = vec + V_RDINV * kSlot; c.dinv = vec + V_DINV * kSlot;
-        c.red = vec + V_RED * kSlot; c.prm = vec + V_PRM * kSlot; c.b1 = vec + V_B1 * kSlot; c.s = vec + V_S * kSlot;
-        c.stash = vec + V_STASH * kSlot; c.part = vec + V_PART * kSlot;
-    }
+    bind_full_layout(c, lds, a.o_vec, a.o_int);
     c.eqw = a.blocked_eq ? lds + a.o_eqw : nullptr;
     c.eqt = a.blocked_eq ? lds + a.o_eqt : nullptr;
     c.ldb = a.ldb;
-    int* ia = reinterpret_cast<int*>(lds + a.o_int);
-    c.A = ia + kIntA; c.Aold = ia + kIntAold; c.gskip = ia + kIntGskip; c.iai = ia + kIntIai; c.iaexcl = ia + kIntIaexcl;
-    c.meta = ia + kIntMeta;
     c.iq = 0;
     c.R_norm = 1.0;
     const TI* H = static_cast<const TI*>(a.H) + qp * (size_t)n * n;
@@ -271,33 +259,11 @@ __global__ __launch_bounds__(kThreads) void solve_dense_kernel(const DenseArgs a
         if (!ok) status = HQP_ERROR; // redundant equalities
     }
     // ---- ... else one by one (eiquadprog's order)
-    for (int i = 0; i < neq && status == -2 && !a.blocked_eq; ++i) {
-        if (tid < n) c.np[tid] = (double)CE[(size_t)i * n + tid];
-        const double ce = (double)ce0[i];
-        bsync();
-        compute_d(c, 0, n);
-        update_z_r(c, 0);
-        double zz = 0.0, znp = 0.0, npx = 0.0, dn2 = 0.0;
-        if (tid < n) {
-            const double zv = c.z[tid], nv_ = c.np[tid];
-            zz = zv * zv;
-            if (tid >= c.iq) dn2 = c.d[tid] * c.d[tid];
-            znp = zv * nv_;
-            npx = nv_ * c.x[tid];
-        }
-        block_sum4(c, zz, znp, npx, dn2);
-        double t2 = 0.0;
-        if (fabs(zz) > eps) t2 = (-npx - ce) / znp;
-        const int iq = c.iq;
-        if (tid < n) c.x[tid] = fma(t2, c.z[tid], c.x[tid]);
-        if (tid >= 128 && tid - 128 < iq) c.u[tid - 128] = fma(-t2, c.r[tid - 128], c.u[tid - 128]);
-        if (tid == kThreads - 1) {
-            c.u[iq] = t2;
-            c.A[i] = -i - 1;
-        }
-        f_value += 0.5 * (t2 * t2) * znp;
-        if (!add_constraint_hh(c, dn2)) status = HQP_ERROR; // redundant equalities
-    }
+    else if (!equality_phase_sequential(c, f_value, [&](int i) __attribute__((always_inline)) {
+                 if (tid < n) c.np[tid] = (double)CE[(size_t)i * n + tid];
+                 return EqRow{0, n, (double)ce0[i]};
+             }))
+        status = HQP_ERROR; // redundant equalities
     // ---- inequalities
     if (status == -2) {
         for (int i = tid; i < nin; i += kThreads) c.iai[i] = i;
@@ -451,19 +417,7 @@ __global__ __launch_bounds__(kThreads) void solve_dense_kernel(const DenseArgs a
                         bsync();
                     }
                     else {
-                        if (tid == 0) c.iaexcl[ip] = 0;
-                        bsync();
-                        delete_constraint(c, ip);
-                        for (int i = tid; i < nin; i += kThreads) c.iai[i] = i;
-                        bsync();
-                        for (int i = tid; i < c.iq; i += kThreads) {
-                            const int av = c.Aold[i];
-                            c.A[i] = av;
-                            if (av >= 0) c.iai[av] = -1;
-                            c.u[i] = c.uold[i];
-                        }
-                        for (int i = tid; i < n; i += kThreads) c.x[i] = c.xold[i];
-                        bsync();
+                        restore_after_dependent(c, ip, nin);
                         redo_l2 = true;
                     }
                     break;

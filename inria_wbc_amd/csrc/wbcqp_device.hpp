@@ -15,8 +15,9 @@
 // structure (+-e_col bounds rows, +-[M_a | -J_a'] actuation rows, 17x12 friction blocks).
 //
 // Files: wbcqp_types.hpp (shared structures), wbcqp_prims.hpp (wave primitives, context, inner products),
-// wbcqp_factor.hpp (H -> J), wbcqp_equality.hpp (equality phase), wbcqp_activeset.hpp (active-set pieces),
-// wbcqp_integrate.hpp (after the path); this file: one QP on one workgroup (solve_one), the kernels.
+// wbcqp_factor.hpp (H -> J), wbcqp_equality.hpp (equality phase), wbcqp_activeset.hpp (active-set pieces, the one-by-one equality
+// phase, restore_after_dependent), wbcqp_integrate.hpp (after the path); this file: one QP on one workgroup (solve_one), the kernels
+// and what they share (locate_group / group_at, queue_loop).
 #pragma once
 
 #include "wbcqp_types.hpp"
@@ -29,7 +30,6 @@
 
 namespace wbcqp {
 #ifdef __HIPCC__
-
 
 // ------------------------------------------------------------------------------------------------
 // Phases 1-2 for a stack with a "torque" or a "cop" task (tasks.cpp:227-271, :156-178): those level-1 rows couple dv with f and
@@ -195,22 +195,10 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
     c.nblk = S.dense_h ? S.n : S.nv;
     c.neq = S.neq; c.nin2 = S.nin2; c.ldj = S.ldj; c.ldm = S.ldm; c.ldc = S.ldc;
     c.J = lds + S.o_J; c.R = lds + S.o_R; c.M = lds + S.o_M; c.Jc = lds + S.o_Jc; c.Ac = lds + S.o_Ac;
-    {
-        double* vec = lds + S.o_vec;
-        c.h = vec + V_H * kSlot; c.x = vec + V_X * kSlot; c.np = vec + V_NP * kSlot; c.d = vec + V_D * kSlot;
-        c.z = vec + V_Z * kSlot; c.xold = vec + V_XOLD * kSlot; c.r = vec + V_R * kSlot; c.u = vec + V_U * kSlot;
-        c.uold = vec + V_UOLD * kSlot; c.q = vec + V_Q * kSlot; c.g = vec + V_G * kSlot; c.w = vec + V_W * kSlot;
-        c.wrow = vec + V_WROW * kSlot; c.blb = vec + V_BLB * kSlot; c.bub = vec + V_BUB * kSlot; c.tl = vec + V_TL * kSlot;
-        c.tu = vec + V_TU * kSlot; c.bc = vec + V_BC * kSlot; c.rdinv = vec + V_RDINV * kSlot; c.dinv = vec + V_DINV * kSlot;
-        c.red = vec + V_RED * kSlot; c.prm = vec + V_PRM * kSlot; c.b1 = vec + V_B1 * kSlot; c.s = vec + V_S * kSlot;
-        c.stash = vec + V_STASH * kSlot; c.part = vec + V_PART * kSlot;
-    }
+    bind_full_layout(c, lds, S.o_vec, S.o_int);
     c.eqw = lds + S.o_eqw; c.eqt = lds + S.o_eqt; c.ldb = S.ldb;
-    int* ia = reinterpret_cast<int*>(lds + S.o_int);
     const int n = c.n, nv = c.nv, na = c.na, nc = c.nc, k = c.k, nu = c.nu, neq = c.neq, nin2 = c.nin2;
     const int ldj = c.ldj, ldm = c.ldm, ldc = c.ldc;
-    c.A = ia + kIntA; c.Aold = ia + kIntAold; c.gskip = ia + kIntGskip; c.iai = ia + kIntIai; c.iaexcl = ia + kIntIaexcl;
-    c.meta = ia + kIntMeta;
     c.iq = 0;
     c.R_norm = 1.0;
 
@@ -571,41 +559,8 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
         if (!equality_phase_blocked(c, f_value)) status = HQP_ERROR; // redundant equalities
         STAMP(8)
     }
-    for (int i = 0; i < neq && status == -2 && !blocked_eq; ++i) {
-        int k0, k1;
-        double ce0;
-        build_eq_row(c, i, k0, k1, ce0);
-        bsync();
-        compute_d(c, k0, k1);
-        STAMP(5)
-        update_z_r(c, 0);
-        STAMP(6)
-        double zz = 0.0, znp = 0.0, npx = 0.0, dn2 = 0.0;
-        if (tid < n) {
-            const double zv = c.z[tid];
-            zz = zv * zv;
-            if (tid >= c.iq) dn2 = c.d[tid] * c.d[tid];
-            if (tid >= k0 && tid < k1) {
-                const double nv_ = c.np[tid];
-                znp = zv * nv_;
-                npx = nv_ * c.x[tid];
-            }
-        }
-        block_sum4(c, zz, znp, npx, dn2);
-        double t2 = 0.0;
-        if (fabs(zz) > eps) t2 = (-npx - ce0) / znp;
-        const int iq = c.iq;
-        if (tid < n) c.x[tid] = fma(t2, c.z[tid], c.x[tid]);
-        if (tid >= 128 && tid - 128 < iq) c.u[tid - 128] = fma(-t2, c.r[tid - 128], c.u[tid - 128]);
-        if (tid == kThreads - 1) {
-            c.u[iq] = t2;
-            c.A[i] = -i - 1;
-        }
-        f_value += 0.5 * (t2 * t2) * znp;
-        STAMP(7)
-        if (!add_constraint_hh(c, dn2)) status = HQP_ERROR; // redundant equalities
-        STAMP(8)
-    }
+    else if (!equality_phase_sequential(c, f_value, [&](int i) __attribute__((always_inline)) { return build_eq_row(c, i); }))
+        status = HQP_ERROR; // redundant equalities
 
     // ---------------- phase 4: inequality loop (GI steps 1, 2, 2a-2c) ----------------
     // The common iteration (full step, constraint added) takes five barriers:
@@ -901,19 +856,7 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
                     if (accepted) c.R_norm = fmax(c.R_norm, fabs(alpha));
                     else {
                         // numerically dependent: take the constraint out again, back to the saved iterate, pick another
-                        if (tid == 0) c.iaexcl[ip] = 0;
-                        bsync();
-                        delete_constraint(c, ip);
-                        for (int i = tid; i < nin2; i += kThreads) c.iai[i] = i;
-                        bsync();
-                        for (int i = tid; i < c.iq; i += kThreads) {
-                            const int av = c.Aold[i];
-                            c.A[i] = av;
-                            if (av >= 0) c.iai[av] = -1;
-                            c.u[i] = c.uold[i];
-                        }
-                        for (int i = tid; i < n; i += kThreads) c.x[i] = c.xold[i];
-                        bsync();
+                        restore_after_dependent(c, ip, nin2);
                         redo_l2 = true;
                         tau_stale = true;
                     }
@@ -982,6 +925,24 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
 #endif
 }
 
+// The QPs of a launch are numbered group after group.  Launch position b -> the group it falls in (returned) and its index in that group (left
+// in b); count(g): QPs of group g.
+template <typename F>
+__device__ __forceinline__ int locate_group(int& b, const int n_groups, F count)
+{
+    int gi = 0;
+    while (gi + 1 < n_groups && b >= count(gi)) {
+        b -= count(gi);
+        ++gi;
+    }
+    return gi;
+}
+template <typename TI>
+__device__ __forceinline__ const GroupArgs<TI>& group_at(const GroupTable<TI>& tab, int& b)
+{
+    return tab.g[locate_group(b, tab.n, [&](int g) __attribute__((always_inline)) { return tab.g[g].count; })];
+}
+
 // ------------------------------------------------------------------------------------------------
 // the kernel: grid = total QPs, block = 256 threads = four wavefronts = one QP
 // ------------------------------------------------------------------------------------------------
@@ -989,15 +950,10 @@ template <typename TI, bool CP, int SPEC = 0>
 __global__ __launch_bounds__(kThreads) void solve_kernel(const GroupTable<TI> tab)
 {
     extern __shared__ __align__(16) double lds[];
-    int b = tab.order ? tab.order[blockIdx.x] : (int)blockIdx.x, gi = 0;
-    while (gi + 1 < tab.n && b >= tab.g[gi].count) {
-        b -= tab.g[gi].count;
-        ++gi;
-    }
-    const GroupArgs<TI>& ga = tab.g[gi];
-    const DevStruct& S = ga.st;
-    if constexpr (CP) solve_one_compact<TI, SPEC>(ga, S, b, lds, threadIdx.x);
-    else solve_one<TI>(ga, S, b, lds, threadIdx.x);
+    int b = tab.order ? tab.order[blockIdx.x] : (int)blockIdx.x;
+    const GroupArgs<TI>& ga = group_at(tab, b);
+    if constexpr (CP) solve_one_compact<TI, SPEC>(ga, ga.st, b, lds, threadIdx.x);
+    else solve_one<TI>(ga, ga.st, b, lds, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1008,11 +964,11 @@ __global__ __launch_bounds__(kThreads) void solve_kernel(const GroupTable<TI> ta
 // the other engines stand free, and everything behind it in that XCD waits with it.  A queue is list scheduling over
 // all 256 CUs.  *queue: positions handed out beyond the first one of each workgroup; the last fetch of a launch zeroes it
 // for the next launch (stream order makes that visible; no memset on the path, and a captured launch replays as it is).
+// The loop of every queue kernel: solve(ga, b, tid) runs QP b of group ga on this workgroup.
 // ------------------------------------------------------------------------------------------------
-template <typename TI, bool CP, int SPEC = 0>
-__global__ __launch_bounds__(kThreads) void solve_queue_kernel(const GroupTable<TI> tab, int* queue, const int total)
+template <typename TI, typename F>
+__device__ __forceinline__ void queue_loop(const GroupTable<TI>& tab, int* queue, const int total, F solve)
 {
-    extern __shared__ __align__(16) double lds[];
     __shared__ int next_qp;
     for (bool first = true;; first = false) {
         if (threadIdx.x == 0) {
@@ -1028,21 +984,26 @@ __global__ __launch_bounds__(kThreads) void solve_queue_kernel(const GroupTable<
             next_qp = pos < total ? (tab.order ? tab.order[pos] : pos) : -1;
         }
         bsync();
-        int b = uni(next_qp), gi = 0;
+        int b = uni(next_qp);
         if (b < 0) break;
-        while (gi + 1 < tab.n && b >= tab.g[gi].count) {
-            b -= tab.g[gi].count;
-            ++gi;
-        }
-        const GroupArgs<TI>& ga = tab.g[gi];
+        const GroupArgs<TI>& ga = group_at(tab, b);
         // the thread index is made opaque once per QP: otherwise every per-thread offset of solve_one is hoisted out of
         // this loop and stays live across it (measured: 256 VGPRs + 146 AGPRs instead of 240 + 0; build.py refuses that)
         int tid = threadIdx.x;
         asm volatile("" : "+v"(tid));
-        if constexpr (CP) solve_one_compact<TI, SPEC>(ga, ga.st, b, lds, tid);
-        else solve_one<TI>(ga, ga.st, b, lds, tid);
+        solve(ga, b, tid);
         bsync(); // the next QP reuses every byte of LDS, next_qp included
     }
+}
+
+template <typename TI, bool CP, int SPEC = 0>
+__global__ __launch_bounds__(kThreads) void solve_queue_kernel(const GroupTable<TI> tab, int* queue, const int total)
+{
+    extern __shared__ __align__(16) double lds[];
+    queue_loop(tab, queue, total, [&](const GroupArgs<TI>& ga, int b, int tid) __attribute__((always_inline)) {
+        if constexpr (CP) solve_one_compact<TI, SPEC>(ga, ga.st, b, lds, tid);
+        else solve_one<TI>(ga, ga.st, b, lds, tid);
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1054,12 +1015,8 @@ template <typename TI, int SPEC = 0>
 __global__ __launch_bounds__(kThreads) void solve_kernel_warm(const GroupTable<TI> tab)
 {
     extern __shared__ __align__(16) double lds[];
-    int b = tab.order ? tab.order[blockIdx.x] : (int)blockIdx.x, gi = 0;
-    while (gi + 1 < tab.n && b >= tab.g[gi].count) {
-        b -= tab.g[gi].count;
-        ++gi;
-    }
-    const GroupArgs<TI>& ga = tab.g[gi];
+    int b = tab.order ? tab.order[blockIdx.x] : (int)blockIdx.x;
+    const GroupArgs<TI>& ga = group_at(tab, b);
     solve_one_compact<TI, SPEC, true>(ga, ga.st, b, lds, threadIdx.x);
 }
 
@@ -1067,30 +1024,7 @@ template <typename TI, int SPEC = 0>
 __global__ __launch_bounds__(kThreads) void solve_queue_kernel_warm(const GroupTable<TI> tab, int* queue, const int total)
 {
     extern __shared__ __align__(16) double lds[];
-    __shared__ int next_qp;
-    for (bool first = true;; first = false) {
-        if (threadIdx.x == 0) {
-            int pos = (int)blockIdx.x;
-            if (!first) {
-                const int c = atomicAdd(queue, 1);
-                pos = (int)gridDim.x + c;
-                if (c == total - 1) *queue = 0;
-            }
-            next_qp = pos < total ? (tab.order ? tab.order[pos] : pos) : -1;
-        }
-        bsync();
-        int b = uni(next_qp), gi = 0;
-        if (b < 0) break;
-        while (gi + 1 < tab.n && b >= tab.g[gi].count) {
-            b -= tab.g[gi].count;
-            ++gi;
-        }
-        const GroupArgs<TI>& ga = tab.g[gi];
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        solve_one_compact<TI, SPEC, true>(ga, ga.st, b, lds, tid);
-        bsync();
-    }
+    queue_loop(tab, queue, total, [&](const GroupArgs<TI>& ga, int b, int tid) __attribute__((always_inline)) { solve_one_compact<TI, SPEC, true>(ga, ga.st, b, lds, tid); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1100,36 +1034,13 @@ __global__ __launch_bounds__(kThreads) void solve_queue_kernel_warm(const GroupT
 // iCub on one foot, n 50, B = 8192): two per CU without scratch 10.55 M QP/s; this build held at two per CU 9.59 M (the spills cost 9 %);
 // this build at three per CU 12.24 M (+16 %, same bits) -- the chains of a third QP fill the issue slots two leave idle.
 // Taken only for stacks WITHOUT actuation bounds: with them the loop's 38 registers of actuation rows go to scratch and three per CU loses (Talos on one
-// foot: 8.03 M QP/s against 9.32 M at two; wbcqp_api.hip, kThree).
+// foot: 8.03 M QP/s against 9.32 M at two; wbcqp_host_handle.hpp, choose_kernel).
 // ------------------------------------------------------------------------------------------------
 template <typename TI, int SPEC = 0>
 __global__ __launch_bounds__(kThreads, 3) void solve_queue3_kernel(const GroupTable<TI> tab, int* queue, const int total)
 {
     extern __shared__ __align__(16) double lds[];
-    __shared__ int next_qp;
-    for (bool first = true;; first = false) {
-        if (threadIdx.x == 0) {
-            int pos = (int)blockIdx.x;
-            if (!first) {
-                const int c = atomicAdd(queue, 1);
-                pos = (int)gridDim.x + c;
-                if (c == total - 1) *queue = 0;
-            }
-            next_qp = pos < total ? (tab.order ? tab.order[pos] : pos) : -1;
-        }
-        bsync();
-        int b = uni(next_qp), gi = 0;
-        if (b < 0) break;
-        while (gi + 1 < tab.n && b >= tab.g[gi].count) {
-            b -= tab.g[gi].count;
-            ++gi;
-        }
-        const GroupArgs<TI>& ga = tab.g[gi];
-        int tid = threadIdx.x;
-        asm volatile("" : "+v"(tid));
-        solve_one_compact<TI, SPEC>(ga, ga.st, b, lds, tid);
-        bsync();
-    }
+    queue_loop(tab, queue, total, [&](const GroupArgs<TI>& ga, int b, int tid) __attribute__((always_inline)) { solve_one_compact<TI, SPEC>(ga, ga.st, b, lds, tid); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1147,11 +1058,8 @@ __global__ __launch_bounds__(1024) void schedule_kernel(const ScheduleArgs sa, i
     if (tid < 64) hist[tid] = 0;
     bsync();
     auto key_of = [&](int i) {
-        int gi = 0, b = i;
-        while (gi + 1 < sa.n && b >= sa.count[gi]) {
-            b -= sa.count[gi];
-            ++gi;
-        }
+        int b = i;
+        const int gi = locate_group(b, sa.n, [&](int g) { return sa.count[g]; });
         const int it = sa.iters[gi][b];
         return 63 - min(max(it, 0), 63);
     };

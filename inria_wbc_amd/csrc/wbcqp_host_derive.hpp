@@ -7,7 +7,7 @@
 namespace {
 
 int odd(int v) { return v | 1; }
-void set_lds(wbcqp_layout& L, int lds_bytes, bool compact = false, bool act_bounds = false);
+void set_lds(wbcqp_layout& L, int lds_bytes, bool compact = false, bool act_bounds = false, int spec = 0);
 
 // Validates a structure and derives sizes + LDS layout. Pure host code.
 int derive(const wbcqp_structure* st, DevStruct& D, HostBlocks& HB, wbcqp_layout& L, std::string& why)
@@ -189,15 +189,16 @@ bool derive_compact(const DevStruct& F, DevStruct& D)
     return true;
 }
 
-void set_lds(wbcqp_layout& L, int lds_bytes, bool compact, bool act_bounds)
+void set_lds(wbcqp_layout& L, int lds_bytes, bool compact, bool act_bounds, int spec)
 {
     L.lds_bytes = lds_bytes;
     L.waves_per_cu = lds_bytes > 0 ? (160 * 1024) / lds_bytes : 0;
     // registers: the solve kernels allocate up to 256 VGPRs = two waves per SIMD = two workgroups per CU; the compact layout has a twin compiled
     // for three (solve_queue3_kernel), taken when three workgroups fit the CU's LDS: measured (tools/ubench/lds_granule.hip) the third one fits
-    // up to 54 592 bytes of dynamic LDS beside the kernel's static word -- no coarser granule than 16 bytes (the launch asks the runtime itself)
-    const int cap = (compact && !act_bounds && lds_bytes >= kQueue3MinLds && lds_bytes <= kLdsThree) ? 3 : 2; // (below kQueue3MinLds: solve_kernel, two per CU;
-                                                                                                           //  with actuation bounds three per CU measured slower: kThree)
+    // up to 54 592 bytes of dynamic LDS beside the kernel's static word -- no coarser granule than 16 bytes (the launch asks the runtime itself).
+    // Whether a launch of this structure alone, on a handle without flags, takes that twin is choose_kernel's answer, not a rule of this function's
+    const KernelChoice c = choose_kernel(LaunchFacts{compact, lds_bytes, act_bounds, spec, true}, 0);
+    const int cap = (c.three && c.queue) ? 3 : 2;
     if (L.waves_per_cu > cap) L.waves_per_cu = cap;
 }
 

@@ -1,6 +1,6 @@
 // wbcqp_host_handle.hpp -- host side of the C ABI (wbcqp_api.hip): the handle and its slots, error reporting, device and page-locked buffers, the
 // ONE description of the per-instance arrays of a call (fields, block layout, staging of the host-pointer entry points), the argument checks the entry
-// points share and the F64 / F32 fork.  Host code only; included by wbcqp_api.hip alone.
+// points share and the F64 / F32 fork; the launch policy (choose_kernel: which kernel runs a launch).  Host code only; included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_device.hpp"
 #include "wbcqp_terms.hpp"
@@ -23,7 +23,6 @@
 #include <vector>
 
 using namespace wbcqp;
-
 
 namespace {
 
@@ -79,11 +78,66 @@ struct OrderState {
 };
 
 constexpr size_t kMaxQueues = 16;
-constexpr int kQueueMinLds = 48 * 1024; // workgroups at least this large take their QPs from the queue by default (measured: below it the dispatcher wins, launch())
+
+// ---- which kernel runs a launch: the ONE statement of the policy (solve_ragged, launch() and wbcqp_layout_of all ask choose_kernel) ------------------
+constexpr int kQueueMinLds = 48 * 1024; // workgroups at least this large take their QPs from the queue by default (measured: below it the dispatcher wins, wants_queue)
 constexpr int kQueue3MinLds = 40 * 1024; // ... and from 40 KB on where the launch runs three per CU through solve_queue3_kernel (the dispatcher's solve_kernel holds
                                          // two); a 40-48 KB stack that cannot take the twin (actuation bounds, warm start) stays with the dispatcher
 constexpr int kLdsThree = 54592;        // the largest dynamic LDS block of which a CU holds three (tools/ubench/lds_granule.hip)
 constexpr int kOrderRefresh = 4; // default period of the launch-order renewal (WBCQP_FLAG_REFRESH)
+
+// which instantiations of the compact kernel (0: generic, i: kSpecDims[i - 1]) have a three-per-CU twin: the generic one and iCub's.  Not Talos's (two feet:
+// 72 KB of LDS; one foot fits since its layout's last diet, 54 480 B, but LOSES there: 8.03 M QP/s at three per CU against 9.32 M at two -- with actuation
+// bounds the loop keeps the actuation rows in 38 registers, and at 168 they live in scratch, on the chain of every pick; tools/occ3_probe.py --stack
+// talos_single_support).  The generic twin is likewise taken only for stacks WITHOUT actuation bounds (choose_kernel).
+constexpr bool spec_has_three(int spec) { return spec == 0 || spec == 2; }
+// ... and which have a twin with the warm start's pick hint compiled in (WBCQP_FLAG_WARM_START): the generic one and Talos's; a handle with that flag runs
+// every compact launch through one of the two (the other stacks go to the generic one)
+constexpr bool spec_has_warm(int spec) { return spec == 0 || spec == 1; }
+
+// what a launch is, as far as the choice goes
+struct LaunchFacts {
+    bool compact;    // every group of the launch is eligible for the compact layout
+    int lds_bytes;   // dynamic LDS of a workgroup (the largest group's)
+    bool act_bounds; // some group has actuation bounds
+    int spec;        // the structure's instantiation of the compact kernel (Slot::spec), where the launch is one group
+    bool single;     // one group; false: ragged
+};
+struct KernelChoice {
+    int spec;    // the compact kernel's instantiation, 0: the generic one (and the full layout's kernel)
+    int variant; // index into wbcqp_handle::variant: 0 full layout, 1 compact, 1 + spec
+    bool warm;   // the twin with the warm start's pick hint
+    bool three;  // the twin compiled for three workgroups per CU (taken where the launch goes through the queue)
+    bool queue;  // the workgroups take their QPs from the queue; false: the hardware's dispatcher
+};
+
+// The queue pays when a QP is long enough for a hand-over (1 us: atomic + order entry) to vanish and few enough workgroups
+// fit a CU for the dispatcher's binding of a workgroup to one shader engine to leave CUs idle: the humanoid stacks (one
+// or two workgroups per CU; measured on the compact layout, tools/dispatch_sweep.py: 1-2 % over the dispatcher at every
+// batch size).  Small QPs (Franka: 26 KB of LDS) give the dispatcher slack -- measured 27 M QP/s through the queue
+// against 36 M through the hardware.  WBCQP_FLAG_QUEUE forces the queue, WBCQP_FLAG_HW_DISPATCH the dispatcher.
+constexpr bool wants_queue(int lds_bytes, bool three, int flags)
+{
+    return !(flags & WBCQP_FLAG_HW_DISPATCH) && (lds_bytes >= kQueueMinLds || (three && lds_bytes >= kQueue3MinLds) || (flags & WBCQP_FLAG_QUEUE));
+}
+
+// flags: wbcqp_desc.flags; lds_pad: the handle's diagnostic padding (WBCQP_DEBUG_LDS_PAD).  Pure: no device, no handle (wbcqp_layout_of asks with flags 0)
+constexpr KernelChoice choose_kernel(const LaunchFacts& f, int flags, int lds_pad = 0)
+{
+    KernelChoice c{0, 0, false, false, false};
+    if (f.compact) {
+        // a launch of ONE group whose structure is a shipped stack takes that stack's instantiation (sizes and offsets as literals: wbcqp_types.hpp);
+        // anything else -- ragged launches, other structures, WBCQP_FLAG_GENERIC_KERNEL -- the generic one.  Same bits.
+        if (f.single && !(flags & WBCQP_FLAG_GENERIC_KERNEL) && lds_pad == 0) c.spec = f.spec;
+        c.warm = (flags & WBCQP_FLAG_WARM_START) != 0;
+        if (c.warm && !spec_has_warm(c.spec)) c.spec = 0;
+        c.variant = 1 + c.spec;
+        // three per CU: the instantiation has the twin, three workgroups fit the CU's LDS, no warm start and no group has actuation bounds
+        c.three = spec_has_three(c.spec) && !c.warm && !f.act_bounds && f.lds_bytes <= kLdsThree && lds_pad == 0;
+    }
+    c.queue = wants_queue(f.lds_bytes, c.three, flags);
+    return c;
+}
 
 struct wbcqp_handle {
     int device = 0;
@@ -92,8 +146,14 @@ struct wbcqp_handle {
     Slot slots[WBCQP_MAX_STRUCTURES];
     Staging stage_in, stage_out;
     Pinned pin_in, pin_out;
-    // per kernel variant (0: full layout, 1: compact, 2 + i: the compact kernel specialised for kSpecDims[i]): largest dynamic LDS size set so far
-    int max_lds[2 + kNumSpecs] = {};
+    // what the handle remembers per kernel variant (0: full layout, 1: compact, 2 + i: the compact kernel specialised for kSpecDims[i]; KernelSet)
+    struct Variant {
+        int max_lds = 0;  // largest dynamic LDS size the members' attribute was set for
+        int occ_lds = -1; // the LDS size the rest was asked for (-1: never): resident workgroups per CU of the queue kernel, of its warm twin (a
+        int occ = 0, occ_warm = 0, occ3 = 0; // register allocation of its own; the queue kernel's where there is none) and of the three-per-CU twin,
+        bool three = false;                  // and whether that twin holds three at that size
+    };
+    Variant variant[2 + kNumSpecs];
     long long* dbg = nullptr; // diagnostic builds only (wbcqp_debug_set_stamp_buffer)
     // longest-first schedule (schedule_kernel): launch order for the next solve of the same shape on the same stream
     int flags = 0;
@@ -114,13 +174,9 @@ struct wbcqp_handle {
     std::vector<int32_t> dense_status, dense_iters, dense_nact;
     wbcqp_dense_output dense_out{};
     int lds_pad = 0; // diagnostic (env WBCQP_DEBUG_LDS_PAD): extra dynamic LDS per workgroup, to force a lower residency
-    int queue_lds[2 + kNumSpecs], queue_occ[2 + kNumSpecs] = {}; // occupancy of solve_queue_kernel<., CP, SPEC> at queue_lds bytes of LDS
-    int queue_occ_warm[2 + kNumSpecs] = {};                      // ... of solve_queue_kernel_warm<., SPEC> (WBCQP_FLAG_WARM_START launches that kernel)
     bool debug_launch = false;                                   // env WBCQP_DEBUG_LAUNCH, read once at wbcqp_create (never on the per-tick path)
     bool no_ffcache = false;                                     // env WBCQP_DEBUG_NO_FFCACHE: every QP eliminates its force blocks itself (what tests compare the cache with)
-    int queue_occ3[2 + kNumSpecs] = {};                          // ... of solve_queue3_kernel<., SPEC> where queue_three says it holds three
     bool warned_occupancy = false;                               // the one-time note of launch() when the runtime's occupancy answer is overruled
-    bool queue_three[2 + kNumSpecs] = {};                        // ... and whether solve_queue3_kernel<., SPEC> holds three workgroups per CU at that size
     // wbcqp_rollout: sub-batches on streams of their own (each with its own launch-order state and queue counter), the record
     // arrays and the state ping-pong of the whole batch
     struct RollSub {

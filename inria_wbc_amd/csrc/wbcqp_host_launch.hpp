@@ -1,5 +1,6 @@
-// wbcqp_host_launch.hpp -- host side of the C ABI (wbcqp_api.hip): from checked arguments to kernel launches -- the solve (launch: residency, queue and
-// launch order; launch_small), the per-task costs, the force blocks' factor cache, the integration.  Included by wbcqp_api.hip alone.
+// wbcqp_host_launch.hpp -- host side of the C ABI (wbcqp_api.hip): from checked arguments to kernel launches -- the solve (kernel_set: the kernels of a
+// variant by address; launch: order state, residency, the chosen kernel, launch order; launch_small), the per-task costs, the force blocks' factor cache,
+// the integration.  Which kernel a launch takes is choose_kernel's answer (wbcqp_host_handle.hpp).  Included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_host_handle.hpp"
 
@@ -36,203 +37,222 @@ int check_io(wbcqp_handle* h, const Slot& s, int batch, const wbcqp_inputs* in, 
     return WBCQP_OK;
 }
 
-// which instantiations have a three-per-CU twin: the compact kernel, generic or iCub's.  Not Talos's (two feet: 72 KB of LDS; one foot fits since its layout's
-// last diet, 54 480 B, but LOSES there: 8.03 M QP/s at three per CU against 9.32 M at two -- with actuation bounds the loop keeps the actuation rows in 38
-// registers, and at 168 they live in scratch, on the chain of every pick; tools/occ3_probe.py --stack talos_single_support).  The generic twin is likewise
-// taken only for stacks WITHOUT actuation bounds (launch()).
-template <bool CP, int SPEC> constexpr bool kThree = CP && (SPEC == 0 || SPEC == 2);
-// which instantiations have a twin with the warm start's pick hint compiled in (WBCQP_FLAG_WARM_START): the generic compact kernel and Talos's; a handle
-// with that flag runs every compact launch through one of the two (wbcqp_solve_ragged routes the other stacks to the generic one)
-template <bool CP, int SPEC> constexpr bool kWarm = CP && (SPEC == 0 || SPEC == 1);
-
-template <typename TI, bool CP, int SPEC = 0>
-int launch(wbcqp_handle* h, GroupTable<TI>& tab, int total, int lds_bytes, hipStream_t stream)
+// The four-wave solve kernels of one variant (wbcqp_device.hpp), by address: the hardware's dispatch, the queue, their twins with the warm start's pick
+// hint and the queue's twin compiled for three workgroups per CU; null: the variant has no such twin (spec_has_warm, spec_has_three)
+struct KernelSet {
+    const void *dispatch, *queue, *dispatch_warm, *queue_warm, *queue3;
+};
+// ... of the full layout (CP false) or of instantiation SPEC of the compact kernel: the one place that names the kernels
+template <typename TI, bool CP, int SPEC>
+KernelSet kernel_set()
 {
     static_assert(SPEC == 0 || CP, "only the compact kernel is specialised");
-    if (total == 0) return WBCQP_OK;
-    constexpr int V = SPEC > 0 ? 1 + SPEC : (CP ? 1 : 0);
-    if (lds_bytes > h->max_lds[V]) {
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<TI, CP, SPEC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_queue_kernel<TI, CP, SPEC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        if constexpr (kWarm<CP, SPEC>) {
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel_warm<TI, SPEC>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_queue_kernel_warm<TI, SPEC>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        }
-        if constexpr (kThree<CP, SPEC>)
-            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_queue3_kernel<TI, SPEC>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        h->max_lds[V] = lds_bytes;
+    KernelSet k{reinterpret_cast<const void*>(&solve_kernel<TI, CP, SPEC>), reinterpret_cast<const void*>(&solve_queue_kernel<TI, CP, SPEC>), nullptr, nullptr, nullptr};
+    if constexpr (CP && spec_has_warm(SPEC)) {
+        k.dispatch_warm = reinterpret_cast<const void*>(&solve_kernel_warm<TI, SPEC>);
+        k.queue_warm = reinterpret_cast<const void*>(&solve_queue_kernel_warm<TI, SPEC>);
     }
-    // schedule: the order left by the previous launch is used when it is of this very shape and was produced on this
-    // stream (stream order then guarantees that it is complete); otherwise index order
-    OrderState* osp = h->graph_ord;
-    if (!osp) {
-        for (size_t i = 0; i < h->streams.size() && !osp; ++i)
-            if (h->streams[i].stream == stream) { osp = &h->streams[i].ord; h->last_stream = (int)i; }
-        if (!osp && h->streams.size() < kMaxQueues) {
-            h->streams.push_back({stream, OrderState{}});
-            h->last_stream = (int)h->streams.size() - 1;
-            osp = &h->streams.back().ord;
-            osp->stream = stream;
-        }
-        else if (!osp)
-            h->last_stream = -1;
+    if constexpr (CP && spec_has_three(SPEC)) k.queue3 = reinterpret_cast<const void*>(&solve_queue3_kernel<TI, SPEC>);
+    return k;
+}
+template <typename TI>
+KernelSet kernel_set(int variant)
+{
+    static_assert(kNumSpecs == 3, "one case per instantiation");
+    switch (variant) {
+    case 0: return kernel_set<TI, false, 0>();
+    case 2: return kernel_set<TI, true, 1>();
+    case 3: return kernel_set<TI, true, 2>();
+    case 4: return kernel_set<TI, true, 3>();
+    default: return kernel_set<TI, true, 0>();
     }
-    OrderState none{};
-    OrderState& os = osp ? *osp : none;
-    const bool sched = osp && !(h->flags & WBCQP_FLAG_INDEX_ORDER) && total > 1;
-    unsigned long long sig = 1469598103934665603ull;
-    ScheduleArgs sa{};
-    sa.n = tab.n;
+}
+
+// what launch() needs of a group table, whatever its element type: the kernels' argument, where the launch order goes, and the groups' shapes
+struct LaunchTable {
+    void* kernarg;
+    const int** order;
+    ScheduleArgs sa;        // the groups' counts and iteration counts (schedule_kernel)
+    unsigned long long sig; // shape signature: structures, LDS sizes, counts
+    bool act_bounds;        // some group has actuation bounds
+};
+template <typename TI>
+LaunchTable launch_table(GroupTable<TI>& tab)
+{
+    LaunchTable t{&tab, &tab.order, ScheduleArgs{}, 1469598103934665603ull, false};
+    t.sa.n = tab.n;
     for (int g = 0; g < tab.n; ++g) {
-        sig = (sig ^ (unsigned long long)(uintptr_t)tab.g[g].st.rowmeta) * 1099511628211ull;
-        sig = (sig ^ (unsigned long long)tab.g[g].st.lds_doubles) * 1099511628211ull;
-        sig = (sig ^ (unsigned long long)tab.g[g].count) * 1099511628211ull;
-        sa.iters[g] = tab.g[g].iters;
-        sa.count[g] = tab.g[g].count;
+        t.sig = (t.sig ^ (unsigned long long)(uintptr_t)tab.g[g].st.rowmeta) * 1099511628211ull;
+        t.sig = (t.sig ^ (unsigned long long)tab.g[g].st.lds_doubles) * 1099511628211ull;
+        t.sig = (t.sig ^ (unsigned long long)tab.g[g].count) * 1099511628211ull;
+        t.sa.iters[g] = tab.g[g].iters;
+        t.sa.count[g] = tab.g[g].count;
+        t.act_bounds = t.act_bounds || tab.g[g].st.act_bounds;
     }
-    tab.order = (sched && os.total == total && os.sig == sig) ? os.order + (os.packed ? os.cap : 0) : nullptr;
-    // The queue pays when a QP is long enough for a hand-over (1 us: atomic + order entry) to vanish and few enough workgroups
-    // fit a CU for the dispatcher's binding of a workgroup to one shader engine to leave CUs idle: the humanoid stacks (one
-    // or two workgroups per CU; measured on the compact layout, tools/dispatch_sweep.py: 1-2 % over the dispatcher at every
-    // batch size).  Small QPs (Franka: 26 KB of LDS) give the dispatcher slack -- measured 27 M QP/s through the queue
-    // against 36 M through the hardware.  WBCQP_FLAG_QUEUE forces the queue, WBCQP_FLAG_HW_DISPATCH the dispatcher.
-    if (h->queue_lds[V] != lds_bytes) {
-        // Resident workgroups per CU of the kernel that will be launched: the runtime's answer, checked against what THIS kernel's own resources admit on
-        // the device the handle is bound to (wbcqp_create accepts gfx950 only): k workgroups while k (lds + 16) <= 160 KB (measured, tools/ubench/lds_granule.hip)
-        // and k waves per SIMD while k x (its allocated VGPRs, 8-register granule) <= 512 -- both read from the kernel itself (hipFuncGetAttributes), not from a
-        // constant.  A runtime that answers LESS than both admit is not believed: seen when a process holds TWO HIP runtimes (the library loaded before torch:
-        // the first one then answers 1 for every kernel, tools/occ_state_probe.py); workgroups that do not fit wait their turn, results never depend on it.
-        // An answer below the rule for any other reason (registers grown in a variant build, WBCQP_DEBUG_LDS_PAD) moves the rule with it and is kept.
-        bool distrust = false;
-        auto resident_of = [&](const void* kernel, const char* what, int cap, int& occ_out) -> int {
-            int occ = 0;
-            HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kThreads, (size_t)lds_bytes));
-            hipFuncAttributes fa{};
-            HIP_TRY(h, hipFuncGetAttributes(&fa, kernel));
-            const int regs = std::max(8, (fa.numRegs + 7) & ~7);
-            const int admitted = std::min({(160 * 1024) / (lds_bytes + 16), 512 / regs, cap}); // (+ 16: the granule and the kernel's static word, as measured)
-            if (occ < admitted && h->lds_pad == 0) {
-                distrust = true;
-                occ = admitted;
-            }
-            if (h->debug_launch)
-                std::fprintf(stderr, "wbcqp occupancy: %s lds %d B (+ %d static) VGPRs %d -> %d per CU%s\n", what, lds_bytes, (int)fa.sharedSizeBytes, fa.numRegs, occ,
-                             distrust ? " (runtime answered less)" : "");
-            occ_out = occ;
-            return WBCQP_OK;
-        };
+    return t;
+}
+
+// launch(), part 1: the order state of the stream -- the graph's own while a tick is captured, else the handle's for this stream (made on the stream's
+// first launch); null beyond kMaxQueues streams: such a launch runs in index order on the dispatcher and leaves no state behind
+OrderState* order_state_of(wbcqp_handle* h, hipStream_t stream)
+{
+    if (h->graph_ord) return h->graph_ord;
+    for (size_t i = 0; i < h->streams.size(); ++i)
+        if (h->streams[i].stream == stream) {
+            h->last_stream = (int)i;
+            return &h->streams[i].ord;
+        }
+    if (h->streams.size() >= kMaxQueues) {
+        h->last_stream = -1;
+        return nullptr;
+    }
+    h->streams.push_back({stream, OrderState{}});
+    h->last_stream = (int)h->streams.size() - 1;
+    h->streams.back().ord.stream = stream;
+    return &h->streams.back().ord;
+}
+
+// launch(), part 2: the variant's kernels admit lds_bytes of dynamic LDS, and the handle knows how many of their workgroups a CU holds at that size
+int prepare_variant(wbcqp_handle* h, const KernelSet& ks, wbcqp_handle::Variant& v, int lds_bytes)
+{
+    if (lds_bytes > v.max_lds) {
+        for (const void* k : {ks.dispatch, ks.queue, ks.dispatch_warm, ks.queue_warm, ks.queue3})
+            if (k) HIP_TRY(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        v.max_lds = lds_bytes;
+    }
+    if (v.occ_lds == lds_bytes) return WBCQP_OK;
+    // Resident workgroups per CU of the kernel that will be launched: the runtime's answer, checked against what THIS kernel's own resources admit on
+    // the device the handle is bound to (wbcqp_create accepts gfx950 only): k workgroups while k (lds + 16) <= 160 KB (measured, tools/ubench/lds_granule.hip)
+    // and k waves per SIMD while k x (its allocated VGPRs, 8-register granule) <= 512 -- both read from the kernel itself (hipFuncGetAttributes), not from a
+    // constant.  A runtime that answers LESS than both admit is not believed: seen when a process holds TWO HIP runtimes (the library loaded before torch:
+    // the first one then answers 1 for every kernel, tools/occ_state_probe.py); workgroups that do not fit wait their turn, results never depend on it.
+    // An answer below the rule for any other reason (registers grown in a variant build, WBCQP_DEBUG_LDS_PAD) moves the rule with it and is kept.
+    bool distrust = false;
+    auto resident_of = [&](const void* kernel, const char* what, int cap, int& occ_out) -> int {
         int occ = 0;
-        if (int rc = resident_of(reinterpret_cast<const void*>(&solve_queue_kernel<TI, CP, SPEC>), "solve_queue_kernel", 2, occ); rc != WBCQP_OK) return rc;
-        if (occ < 1) return fail(h, WBCQP_ERR_HIP, "solve_queue_kernel: no workgroup fits a CU");
-        h->queue_occ[V] = occ;
-        h->queue_occ_warm[V] = occ;
-        if constexpr (kWarm<CP, SPEC>) { // the warm start's twin is a register allocation of its own: its occupancy, not its sibling's
-            int occw = 0;
-            if (int rc = resident_of(reinterpret_cast<const void*>(&solve_queue_kernel_warm<TI, SPEC>), "solve_queue_kernel_warm", 2, occw); rc != WBCQP_OK) return rc;
-            if (occw < 1) return fail(h, WBCQP_ERR_HIP, "solve_queue_kernel_warm: no workgroup fits a CU");
-            h->queue_occ_warm[V] = occw;
+        HIP_TRY(h, hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, kThreads, (size_t)lds_bytes));
+        hipFuncAttributes fa{};
+        HIP_TRY(h, hipFuncGetAttributes(&fa, kernel));
+        const int regs = std::max(8, (fa.numRegs + 7) & ~7);
+        const int admitted = std::min({(160 * 1024) / (lds_bytes + 16), 512 / regs, cap}); // (+ 16: the granule and the kernel's static word, as measured)
+        if (occ < admitted && h->lds_pad == 0) {
+            distrust = true;
+            occ = admitted;
         }
-        h->queue_lds[V] = lds_bytes;
-        h->queue_three[V] = false;
-        // a workgroup small enough for three on a CU takes the kernel compiled for three waves per SIMD (wbcqp_device.hpp: solve_queue3_kernel)
-        if constexpr (kThree<CP, SPEC>) {
-            if (lds_bytes <= kLdsThree && h->lds_pad == 0) {
-                int occ3 = 0;
-                if (int rc = resident_of(reinterpret_cast<const void*>(&solve_queue3_kernel<TI, SPEC>), "solve_queue3_kernel", 3, occ3); rc != WBCQP_OK) return rc;
-                if (occ3 >= 3) {
-                    h->queue_three[V] = true;
-                    h->queue_occ3[V] = occ3;
-                }
-            }
-        }
-        if (distrust && !h->warned_occupancy) {
-            h->warned_occupancy = true;
-            std::fprintf(stderr, "wbcqp: the HIP runtime reports fewer resident workgroups per CU than LDS (%d B) and the kernel's registers admit; launching %d per CU anyway. "
-                                 "Two HIP runtimes in this process (libwbcqp.so loaded before torch)?  See INTEGRATION.md.\n", lds_bytes,
-                         h->queue_three[V] ? h->queue_occ3[V] : h->queue_occ[V]);
+        if (h->debug_launch)
+            std::fprintf(stderr, "wbcqp occupancy: %s lds %d B (+ %d static) VGPRs %d -> %d per CU%s\n", what, lds_bytes, (int)fa.sharedSizeBytes, fa.numRegs, occ,
+                         distrust ? " (runtime answered less)" : "");
+        occ_out = occ;
+        return WBCQP_OK;
+    };
+    WB_TRY(resident_of(ks.queue, "solve_queue_kernel", 2, v.occ));
+    if (v.occ < 1) return fail(h, WBCQP_ERR_HIP, "solve_queue_kernel: no workgroup fits a CU");
+    v.occ_warm = v.occ;
+    if (ks.queue_warm) { // the warm start's twin is a register allocation of its own: its occupancy, not its sibling's
+        WB_TRY(resident_of(ks.queue_warm, "solve_queue_kernel_warm", 2, v.occ_warm));
+        if (v.occ_warm < 1) return fail(h, WBCQP_ERR_HIP, "solve_queue_kernel_warm: no workgroup fits a CU");
+    }
+    v.occ_lds = lds_bytes;
+    v.three = false;
+    // a workgroup small enough for three on a CU takes the kernel compiled for three waves per SIMD (wbcqp_device.hpp: solve_queue3_kernel)
+    if (ks.queue3 && lds_bytes <= kLdsThree && h->lds_pad == 0) {
+        int occ3 = 0;
+        WB_TRY(resident_of(ks.queue3, "solve_queue3_kernel", 3, occ3));
+        if (occ3 >= 3) {
+            v.three = true;
+            v.occ3 = occ3;
         }
     }
-    // three per CU: where the twin holds three AND no group of the launch has actuation bounds (kThree's comment says why)
-    bool warm = false; // the handle asked for the warm start's pick hint: the kernels that carry its code
-    if constexpr (kWarm<CP, SPEC>) warm = (h->flags & WBCQP_FLAG_WARM_START) != 0;
-    bool three = false;
-    if constexpr (kThree<CP, SPEC>) {
-        three = h->queue_three[V] && !warm;
-        for (int g = 0; g < tab.n; ++g) three = three && !tab.g[g].st.act_bounds;
+    if (distrust && !h->warned_occupancy) {
+        h->warned_occupancy = true;
+        std::fprintf(stderr, "wbcqp: the HIP runtime reports fewer resident workgroups per CU than LDS (%d B) and the kernel's registers admit; launching %d per CU anyway. "
+                             "Two HIP runtimes in this process (libwbcqp.so loaded before torch)?  See INTEGRATION.md.\n", lds_bytes, v.three ? v.occ3 : v.occ);
     }
-    const int queue_occ = three ? h->queue_occ3[V] : (warm ? h->queue_occ_warm[V] : h->queue_occ[V]);
-    if (h->debug_launch)
-        std::fprintf(stderr, "wbcqp launch: V %d spec %d total %d lds %d occupancy %d three %d n_cu %d flags 0x%x\n", V, SPEC, total, lds_bytes, queue_occ, (int)three,
-                     h->n_cu, (unsigned)h->flags);
-    int* queue = nullptr;
-    if (osp && !(h->flags & WBCQP_FLAG_HW_DISPATCH) && (lds_bytes >= kQueueMinLds || (three && lds_bytes >= kQueue3MinLds) || (h->flags & WBCQP_FLAG_QUEUE))) {
-        if (!os.queue && !h->graph_ord) {
-            HIP_TRY(h, hipMalloc(&os.queue, 2 * sizeof(int)));
-            HIP_TRY(h, hipMemset(os.queue, 0, 2 * sizeof(int)));
-        }
-        queue = os.queue;
-    }
-    if (queue) {
-        const long long resident = (long long)queue_occ * h->n_cu;
-        if constexpr (kThree<CP, SPEC>) {
-            if (three)
-                hipLaunchKernelGGL((solve_queue3_kernel<TI, SPEC>), dim3((unsigned)(total < resident ? total : resident)), dim3(kThreads), lds_bytes,
-                                   stream, tab, queue, total);
-        }
-        if constexpr (kWarm<CP, SPEC>) {
-            if (warm)
-                hipLaunchKernelGGL((solve_queue_kernel_warm<TI, SPEC>), dim3((unsigned)(total < resident ? total : resident)), dim3(kThreads), lds_bytes,
-                                   stream, tab, queue, total);
-        }
-        if (!three && !warm)
-            hipLaunchKernelGGL((solve_queue_kernel<TI, CP, SPEC>), dim3((unsigned)(total < resident ? total : resident)), dim3(kThreads), lds_bytes,
-                               stream, tab, queue, total);
-    }
-    else {
-        if constexpr (kWarm<CP, SPEC>) {
-            if (warm) hipLaunchKernelGGL((solve_kernel_warm<TI, SPEC>), dim3(total), dim3(kThreads), lds_bytes, stream, tab);
-        }
-        if (!warm) hipLaunchKernelGGL((solve_kernel<TI, CP, SPEC>), dim3(total), dim3(kThreads), lds_bytes, stream, tab);
-    }
+    return WBCQP_OK;
+}
+
+// launch(), part 3: the chosen kernel of the set goes off, through the queue of `resident` workgroups or one workgroup per QP on the dispatcher
+int launch_chosen(wbcqp_handle* h, const KernelSet& ks, const KernelChoice& c, void* kernarg, int* queue, long long resident, int total, int lds_bytes, hipStream_t stream)
+{
+    const void* kernel = queue ? (c.three ? ks.queue3 : (c.warm ? ks.queue_warm : ks.queue)) : (c.warm ? ks.dispatch_warm : ks.dispatch);
+    if (!kernel) return fail(h, WBCQP_ERR_INVALID, "no solve kernel for the chosen variant"); // (choose_kernel and kernel_set share spec_has_warm / spec_has_three)
+    void* args[3] = {kernarg, &queue, &total}; // (hipLaunchKernel: the runtime entry hipLaunchKernelGGL ends in; a failure is read back below, as after the other launches)
+    (void)hipLaunchKernel(kernel, dim3((unsigned)(queue && resident < total ? resident : total)), dim3(kThreads), args, (size_t)lds_bytes, stream);
     HIP_TRY(h, hipGetLastError());
+    return WBCQP_OK;
+}
+
+// launch(), part 4: the launch order for the next launch of this shape on this stream, from the iteration counts this one leaves
+int renew_order(wbcqp_handle* h, OrderState& os, const LaunchTable& t, bool used_order, long long resident, int queue_occ, int total, hipStream_t stream)
+{
     // the order is renewed every `period` launches: iteration counts drift slowly from tick to tick, the queue absorbs what
     // drift there is, and the two order kernels (4.5 + 15 us) are then a fraction of a launch instead of a twentieth
     const int asked = (h->flags >> WBCQP_FLAG_REFRESH_SHIFT) & 0xff;
     const int period = h->capturing ? 1 : (asked ? asked : kOrderRefresh);
-    if (sched && tab.order && os.age + 1 < period)
+    if (used_order && os.age + 1 < period) {
         ++os.age;
-    else if (sched) {
-        os.age = 0;
-        if (total > os.cap) { // first launch of a larger shape (a graph's buffer has its final size from the start)
-            if (h->graph_ord) return fail(h, WBCQP_ERR_INVALID, "captured tick: launch larger than the graph's order buffer");
-            HIP_TRY(h, hipStreamSynchronize(stream));
-            if (os.order) (void)hipFree(os.order);
-            os.order = nullptr;
-            os.cap = 0;
-            os.total = 0;
-            HIP_TRY(h, hipMalloc(&os.order, 2 * sizeof(int) * (size_t)total));
-            os.cap = total;
-        }
-        hipLaunchKernelGGL(schedule_kernel, dim3(1), dim3(1024), 0, stream, sa, os.order, total);
-        HIP_TRY(h, hipGetLastError());
-        // a few QPs per resident workgroup, one structure, taken from the queue: pack the order (pack_order_kernel)
-        const long long resident = queue ? (long long)queue_occ * h->n_cu : 0;
-        // (with two workgroups per CU the packed order measured no better than plain longest-first: WBCQP_FLAG_QUEUE asks for it)
-        os.packed = queue && !(h->flags & WBCQP_FLAG_NO_PACKING) && (queue_occ == 1 || (h->flags & WBCQP_FLAG_QUEUE)) && tab.n == 1 && resident % kPackSubs == 0 &&
-                          total % kPackSubs == 0 && total > resident && total <= 8 * resident && total / kPackSubs <= kPackMaxItems;
-        if (os.packed) {
-            PackArgs pa{tab.g[0].iters, os.order, os.order + os.cap, total, (int)(resident / kPackSubs)};
-            hipLaunchKernelGGL(pack_order_kernel, dim3(kPackSubs), dim3(256), 0, stream, pa);
-            HIP_TRY(h, hipGetLastError());
-        }
-        os.total = total;
-        os.sig = sig;
-        os.stream = stream;
+        return WBCQP_OK;
     }
+    os.age = 0;
+    if (total > os.cap) { // first launch of a larger shape (a graph's buffer has its final size from the start)
+        if (h->graph_ord) return fail(h, WBCQP_ERR_INVALID, "captured tick: launch larger than the graph's order buffer");
+        HIP_TRY(h, hipStreamSynchronize(stream));
+        if (os.order) (void)hipFree(os.order);
+        os.order = nullptr;
+        os.cap = 0;
+        os.total = 0;
+        HIP_TRY(h, hipMalloc(&os.order, 2 * sizeof(int) * (size_t)total));
+        os.cap = total;
+    }
+    hipLaunchKernelGGL(schedule_kernel, dim3(1), dim3(1024), 0, stream, t.sa, os.order, total);
+    HIP_TRY(h, hipGetLastError());
+    // a few QPs per resident workgroup, one structure, taken from the queue (resident > 0): pack the order (pack_order_kernel)
+    // (with two workgroups per CU the packed order measured no better than plain longest-first: WBCQP_FLAG_QUEUE asks for it)
+    os.packed = resident > 0 && !(h->flags & WBCQP_FLAG_NO_PACKING) && (queue_occ == 1 || (h->flags & WBCQP_FLAG_QUEUE)) && t.sa.n == 1 && resident % kPackSubs == 0 &&
+                total % kPackSubs == 0 && total > resident && total <= 8 * resident && total / kPackSubs <= kPackMaxItems;
+    if (os.packed) {
+        PackArgs pa{t.sa.iters[0], os.order, os.order + os.cap, total, (int)(resident / kPackSubs)};
+        hipLaunchKernelGGL(pack_order_kernel, dim3(kPackSubs), dim3(256), 0, stream, pa);
+        HIP_TRY(h, hipGetLastError());
+    }
+    os.total = total;
+    os.sig = t.sig;
+    os.stream = stream;
     return WBCQP_OK;
+}
+
+// `total` QPs of the groups of t on four-wave workgroups of lds_bytes, by the kernel choose_kernel names (c; ks: that variant's kernels)
+int launch(wbcqp_handle* h, const KernelSet& ks, KernelChoice c, const LaunchTable& t, int total, int lds_bytes, hipStream_t stream)
+{
+    if (total == 0) return WBCQP_OK;
+    wbcqp_handle::Variant& v = h->variant[c.variant];
+    WB_TRY(prepare_variant(h, ks, v, lds_bytes));
+    // schedule: the order left by the previous launch is used when it is of this very shape and was produced on this
+    // stream (stream order then guarantees that it is complete); otherwise index order
+    OrderState* os = order_state_of(h, stream);
+    const bool sched = os && !(h->flags & WBCQP_FLAG_INDEX_ORDER) && total > 1;
+    *t.order = (sched && os->total == total && os->sig == t.sig) ? os->order + (os->packed ? os->cap : 0) : nullptr;
+    // what the device can still overrule: the twin does not hold three workgroups per CU after all (the runtime's occupancy answer, prepare_variant) --
+    // then two per CU, and the queue only where it is taken without the twin; and a stream without an order state has no queue counter
+    if (c.three && !v.three) {
+        c.three = false;
+        c.queue = wants_queue(lds_bytes, false, h->flags);
+    }
+    const int queue_occ = c.three ? v.occ3 : (c.warm ? v.occ_warm : v.occ);
+    if (h->debug_launch)
+        std::fprintf(stderr, "wbcqp launch: V %d spec %d total %d lds %d occupancy %d three %d n_cu %d flags 0x%x\n", c.variant, c.spec, total, lds_bytes, queue_occ,
+                     (int)c.three, h->n_cu, (unsigned)h->flags);
+    int* queue = nullptr;
+    if (os && c.queue) {
+        if (!os->queue && !h->graph_ord) {
+            HIP_TRY(h, hipMalloc(&os->queue, 2 * sizeof(int)));
+            HIP_TRY(h, hipMemset(os->queue, 0, 2 * sizeof(int)));
+        }
+        queue = os->queue;
+    }
+    const long long resident = queue ? (long long)queue_occ * h->n_cu : 0;
+    WB_TRY(launch_chosen(h, ks, c, t.kernarg, queue, resident, total, lds_bytes, stream));
+    return sched ? renew_order(h, *os, t, *t.order != nullptr, resident, queue_occ, total, stream) : WBCQP_OK;
 }
 
 // the small structures of a launch: one wavefront per QP, four per workgroup, in table order (no launch order: the QPs are

@@ -182,6 +182,23 @@ struct Ctx {
 #endif
 };
 
+// the full layout's 26 vector slots (fixed multiples of kSlot from o_vec: wbcqp_types.hpp) and six int arrays (kInt* from o_int), bound once for
+// the kernels that use it (solve_one, solve_dense_kernel)
+__device__ __forceinline__ void bind_full_layout(Ctx& c, double* lds, int o_vec, int o_int)
+{
+    double* vec = lds + o_vec;
+    c.h = vec + V_H * kSlot; c.x = vec + V_X * kSlot; c.np = vec + V_NP * kSlot; c.d = vec + V_D * kSlot;
+    c.z = vec + V_Z * kSlot; c.xold = vec + V_XOLD * kSlot; c.r = vec + V_R * kSlot; c.u = vec + V_U * kSlot;
+    c.uold = vec + V_UOLD * kSlot; c.q = vec + V_Q * kSlot; c.g = vec + V_G * kSlot; c.w = vec + V_W * kSlot;
+    c.wrow = vec + V_WROW * kSlot; c.blb = vec + V_BLB * kSlot; c.bub = vec + V_BUB * kSlot; c.tl = vec + V_TL * kSlot;
+    c.tu = vec + V_TU * kSlot; c.bc = vec + V_BC * kSlot; c.rdinv = vec + V_RDINV * kSlot; c.dinv = vec + V_DINV * kSlot;
+    c.red = vec + V_RED * kSlot; c.prm = vec + V_PRM * kSlot; c.b1 = vec + V_B1 * kSlot; c.s = vec + V_S * kSlot;
+    c.stash = vec + V_STASH * kSlot; c.part = vec + V_PART * kSlot;
+    int* ia = reinterpret_cast<int*>(lds + o_int);
+    c.A = ia + kIntA; c.Aold = ia + kIntAold; c.gskip = ia + kIntGskip; c.iai = ia + kIntIai; c.iaexcl = ia + kIntIaexcl;
+    c.meta = ia + kIntMeta;
+}
+
 // ---- workgroup-wide reductions: wave-level DPP reduce, four partials through LDS, one barrier ----
 __device__ __forceinline__ double block_sum(Ctx& c, double v)
 {

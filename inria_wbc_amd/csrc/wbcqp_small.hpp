@@ -17,6 +17,7 @@
 #include "wbcqp_prims.hpp"
 #include "wbcqp_factor.hpp"
 #include "wbcqp_compact.hpp"
+#include "wbcqp_device.hpp"
 
 namespace wbcqp {
 #ifdef __HIPCC__
@@ -465,13 +466,9 @@ __global__ __launch_bounds__(kThreads) void solve_small_kernel(const GroupTable<
 {
     extern __shared__ __align__(16) double lds[];
     const int wave = uni((int)threadIdx.x >> 6), lane = threadIdx.x & (kWave - 1);
-    int b = (int)blockIdx.x * kWaves + wave, gi = 0;
+    int b = (int)blockIdx.x * kWaves + wave;
     if (b >= total) return;
-    while (gi + 1 < tab.n && b >= tab.g[gi].count) {
-        b -= tab.g[gi].count;
-        ++gi;
-    }
-    const GroupArgs<TI>& ga = tab.g[gi];
+    const GroupArgs<TI>& ga = group_at(tab, b); // (wbcqp_device.hpp)
     solve_one_wave<TI>(ga, ga.st, b, lds + wave * sm::COUNT, lane);
 }
 

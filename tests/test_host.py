@@ -324,7 +324,7 @@ def test_layout_reports_three_only_where_three_fit():
     two_feet = capi.layout_of(structure.icub_structure())  # BASELINE config 3's stack: 52.8 KB since its rows of J are n long and the friction table lives in them
     assert two_feet["n"] == 62 and two_feet["waves_per_cu"] == 3 and two_feet["specialised"] == 2 and 3 * two_feet["lds_bytes"] <= 160 * 1024
     # Talos on one foot fits since its layout's last diet (54 480 B) but stays at two: with actuation bounds the three-per-CU kernel measured SLOWER (its 38
-    # registers of actuation rows go to scratch: csrc/wbcqp_host_launch.hpp, kThree)
+    # registers of actuation rows go to scratch: csrc/wbcqp_host_handle.hpp, spec_has_three)
     one_foot_talos = capi.layout_of(structure.talos_structure(single_support=True))
     assert one_foot_talos["waves_per_cu"] == 2 and one_foot_talos["specialised"] == 3 and one_foot_talos["lds_bytes"] <= 54592
     assert capi.layout_of(structure.talos_structure())["waves_per_cu"] == 2
