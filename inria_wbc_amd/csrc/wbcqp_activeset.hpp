@@ -7,6 +7,42 @@
 namespace wbcqp {
 #ifdef __HIPCC__
 
+// The unconstrained minimiser x0 = -H^-1 g = -J (J' g) into c.x (J'g in c.d, J J'g in c.z); returns f = 0.5 g'x0.  Also zeroes u and A and sets
+// iq = 0.  J = U^-1 is still upper triangular and block diagonal here (first block c.nblk wide): both products run over the structural range
+// only, two lanes per column / row whose halves meet by DPP (2 n <= 256).  Ends with block_sum's barrier: x0 is visible to every thread.
+__device__ __forceinline__ double unconstrained_minimum(Ctx& c)
+{
+    const int tid = c.tid, n = c.n, ldj = c.ldj;
+    const int idx = tid >> 1, hf = tid & 1;
+    const int ic = min(idx, n - 1);
+    {
+        const int kb0 = blk_begin(ic, c.nblk), len = ic + 1 - kb0, hl = (len + 1) >> 1;
+        const int ka = kb0 + hf * hl, kb = hf ? ic + 1 : kb0 + hl;
+        double dv = dot8(c.J + ic, ldj, c.g, 1, ka, kb);
+        dv += dpp_get<0xB1>(dv);
+        if (hf == 0 && idx < n) c.d[idx] = dv;
+    }
+    for (int i = tid; i < n + 2; i += kThreads) {
+        c.u[i] = 0.0;
+        c.A[i] = 0;
+    }
+    c.iq = 0;
+    bsync();
+    double part = 0.0;
+    {
+        const int ce = blk_end(ic, c.nblk), len = ce - ic, hl = (len + 1) >> 1;
+        const int ca = ic + hf * hl, cb = hf ? ce : ic + hl;
+        double zv = dot8(c.J + ic * ldj, 1, c.d, 1, ca, cb);
+        zv += dpp_get<0xB1>(zv);
+        if (hf == 0 && idx < n) {
+            c.z[idx] = zv;
+            c.x[idx] = -zv;
+            part = 0.5 * c.g[idx] * (-zv);
+        }
+    }
+    return block_sum(c, part);
+}
+
 // d = J' np over the support [k0, k1) of np (eiquadprog compute_d).
 // threads 0..127 own column idx for the first half of the support, threads 128..255 for the second half;
 // the two partial sums meet in LDS.  Ends with a barrier: d is visible to every thread on return.
@@ -474,6 +510,34 @@ __device__ __forceinline__ void own_rows_eval(Ctx& c, const OwnRows& o, const do
             if (v < 0.0 && c.iai[i] != -1) best = vi_min(best, ValIdx{v, i});
         }
     }
+}
+
+// ---- write-out, the part no layout changes.  The active-set mask (GroupArgs::amask set): bit r of the QP's eight words = one-sided row r (r < 256) is
+// active at the solution; `on` is the calling thread's row tid.
+template <typename TI>
+__device__ __forceinline__ void write_active_mask(const GroupArgs<TI>& ga, size_t qp, const Ctx& c, bool on)
+{
+    const unsigned long long m = __ballot(on);
+    if (c.lane == 0) {
+        ga.amask[qp * 8 + 2 * c.wave] = (unsigned)(m & 0xffffffffull);
+        ga.amask[qp * 8 + 2 * c.wave + 1] = (unsigned)(m >> 32);
+    }
+}
+// status, iterations, objective, size of the active set (c.iq); in the diagnostic build also the phase stamps
+template <typename TI>
+__device__ __forceinline__ void write_results(const GroupArgs<TI>& ga, size_t qp, Ctx& c, int status, int iters, double f_value)
+{
+    if (c.tid == 0) {
+        ga.status[qp] = status;
+        ga.iters[qp] = iters;
+        if (ga.objective) ga.objective[qp] = (TI)f_value;
+        if (ga.n_active) ga.n_active[qp] = c.iq;
+    }
+#ifdef WBCQP_STAMPS
+    STAMP(17)
+    if (c.tid == WBCQP_STAMP_TID && ga.dbg) // (the stamps are per wave: -DWBCQP_STAMP_TID=192 shows wave 3's view of the phases)
+        for (int i = 0; i < kStamps; ++i) ga.dbg[qp * kStamps + i] = c.st_acc_[i];
+#endif
 }
 
 #endif // __HIPCC__

@@ -296,31 +296,6 @@ template <int SPEC> __device__ __forceinline__ Dims dims_of(const DevStruct& S)
     else return dims_from(S);
 }
 
-// One contact's force block on one wave (8 x 8 lane grid, 2 x 2 positions per lane): H_ff = wt F'F + reg I eliminated to (1 / sqrt(pivot), Y) with
-// J_ff = Y diag(1 / sqrt(pivot)).  hF enters as the lane's tile of F'F; tF returns the lane's (at most two) diagonal elements of H_ff, in the order the
-// kernel adds them to tr(H).  The solve kernels and ffcache_kernel (which makes DevStruct::ffc) both run THIS function: a cached factor is the computed
-// one bit for bit.
-__device__ __forceinline__ void force_block_factor(Ctx& c, double (&hF)[2][2], double (&yF)[2][2], double (&tF)[2], double wt, double reg, int la, int le,
-                                                   double* RBf, double* YBf, double* dinv_out, int lane)
-{
-    tF[0] = 0.0;
-    tF[1] = 0.0;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int w = 0; w < 2; ++w) {
-            const int r = la + 8 * u, q = le + 8 * w;
-            if (r < 12 && q < 12) {
-                hF[u][w] = wt * hF[u][w] + ((r == q) ? reg : 0.0);
-                if (r == q) tF[u] = hF[u][w]; // (r == q needs u == w: la, le < 8)
-            }
-            else hF[u][w] = (r == q) ? 1.0 : 0.0;
-            yF[u][w] = 0.0;
-        }
-    publish_panel<3, 2, true, 0>(c, hF, yF, la, le, 0, RBf, YBf);
-    eliminate_block<3, 2, true, 0>(c, hF, yF, la, le, 12, RBf, YBf, dinv_out, lane < 4, lane & 3);
-}
-
 // makes DevStruct::ffc from the force-regularisation weights of ONE QP (wbcqp_api.hip launches it once per slot, ahead of the slot's first solve, on that
 // launch's stream): one wave per contact, the solve kernels' own code
 template <typename TI>
@@ -389,7 +364,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
     c.iq = 0;
     c.R_norm = 1.0;
 
-    const int n_dense = D.n_dense, n_sel = D.n_sel, n_bound = D.n_bound, r1 = D.r1, n_tasks = D.n_tasks;
+    const int n_dense = D.n_dense, n_tasks = D.n_tasks;
     const size_t qp = (size_t)b;                       // torque limits, weights and every output: the QP's index in the batch
     const size_t qr = (size_t)(brec >= 0 ? brec : b);  // the record (M .. bub): wbcqp_rollout's workgroups keep one record slot each
     double* const As = c.J;                  // dense task rows are staged in the J region (J appears after the elimination)
@@ -438,37 +413,14 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 tcv[r] = S.force_gen[ct * 72 + r * 12 + mm];
             }
         }
-        // the short vectors: one (clamped) element per thread each
-        const TI vb1 = ga.b1[qr * r1 + min(tid, r1 - 1)];
-        const TI vw = ga.w[qp * n_tasks + min(tid, n_tasks - 1)];
-        TI vce = TI(0), vbl = TI(0), vbu = TI(0), vtl = TI(0), vtu = TI(0), vha = TI(0);
+        TaskConsts<TI> tk;
+        load_task_constants(ga, S, D, qp, qr, tid, tk);
+        TI vce = TI(0);
         if (neq > 0) {
             if (tid < nu) vce = ga.h[qr * nv + tid];
             else if (nc > 0) vce = ga.bc[qr * (nc * 6) + min(tid - nu, nc * 6 - 1)];
         }
-        if (n_bound > 0) {
-            vbl = ga.blb[qr * n_bound + min(tid, n_bound - 1)];
-            vbu = ga.bub[qr * n_bound + min(tid, n_bound - 1)];
-        }
-        if (D.act_bounds) {
-            vtl = ga.tlb[qp * na + min(tid, na - 1)];
-            vtu = ga.tub[qp * na + min(tid, na - 1)];
-            vha = ga.h[qr * nv + nu + min(tid, na - 1)];
-        }
         meta0 = (nin2 > 0) ? S.rowmeta[min(tid, nin2 - 1)] : 0;
-        const int drt = (n_dense > 0) ? S.dense_row_task[min(tid, n_dense - 1)] : 0;
-        int selc = 0, selt = 0, frt = 0;
-        double ftc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (n_sel > 0) {
-            selc = S.sel_col[min(tid, n_sel - 1)];
-            selt = S.sel_task[min(tid, n_sel - 1)];
-        }
-        if (nc > 0) {
-            const int fm = min(tid, k - 1);
-            frt = S.forcereg_task[fm / 12];
-#pragma unroll
-            for (int qd = 0; qd < 6; ++qd) ftc[qd] = S.ft[(fm / 12) * 72 + (fm % 12) * 6 + qd];
-        }
         // ---- land
         if (lenA > 0) {
 #pragma unroll
@@ -503,23 +455,10 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             }
         }
         if (tid < neq) ce0v[tid] = (tid < nu) ? (double)vce : -(double)vce; // ce0 = h_u | -bc
-        if (tid < r1) c.b1[tid] = (double)vb1;
-        if (tid < n_tasks) c.w[tid] = (double)vw;
-        if (tid < n_bound) {
-            c.blb[tid] = (double)vbl;
-            c.bub[tid] = (double)vbu;
-        }
-        if (D.act_bounds && tid < na) { // lb - h_a, ub - h_a (computeProblemData, actuation tasks)
-            c.tl[tid] = (double)vtl - (double)vha;
-            c.tu[tid] = (double)vtu - (double)vha;
-        }
+        land_task_vectors(c, D, tk);
         // tails of arrays longer than the register rounds (none for the reference's stacks)
         for (int e = tid + RA * kThreads; e < lenA; e += kThreads) As[S.apack[e]] = (double)pA[e];
         for (int e = tid + RC * kThreads; e < lenAc; e += kThreads) Nm[S.acpack[e]] = (double)pAc[e];
-        if (tid < nv) { // diagonal additions / right-hand sides of the selection rows
-            c.z[tid] = 0.0;
-            c.d[tid] = 0.0;
-        }
         if (tid >= n && tid < VS) { // finite padding for act_dot's unconditional reads; never written again
             c.z[tid] = 0.0;
             c.x[tid] = 0.0;
@@ -527,25 +466,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
         if (tid < VS) c.np[tid] = 0.0;                    // ... which may run into the slot behind x (cp::VecMap)
         if (tid >= n_tasks && tid < VS) c.w[tid] = 0.0;   // ... and into the one behind x_old: the weights' tail (r replaces the slot from entry neq on)
         bsync();
-        if (tid < n_dense) { // (row weight, right-hand side) pairs behind the staged rows: one 16-byte read per row
-            As[n_dense * 64 + 2 * tid] = c.w[drt];
-            As[n_dense * 64 + 2 * tid + 1] = c.b1[tid];
-        }
-        // selection rows (posture): H(c,c) += w, g(c) -= w b  (distinct columns)
-        for (int sidx = tid; sidx < n_sel; sidx += kThreads) {
-            const int col = (sidx == tid) ? selc : S.sel_col[sidx];
-            const double wt = c.w[(sidx == tid) ? selt : S.sel_task[sidx]];
-            c.z[col] = wt;
-            c.d[col] = wt * c.b1[n_dense + sidx];
-        }
-        // force regularisation: g_f = -w F' b
-        if (tid < k) {
-            const double* bb = c.b1 + n_dense + n_sel + 6 * (tid / 12);
-            double sacc = 0.0;
-#pragma unroll
-            for (int qd = 0; qd < 6; ++qd) sacc = fma(ftc[qd], bb[qd], sacc);
-            c.g[nv + tid] = -c.w[frt] * sacc;
-        }
+        stage_task_constants(c, S, D, As, tk);
     }
     bsync();
     STAMP(0)
@@ -560,86 +481,18 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
         const int ta = tid >> 4, te = tid & 15;
         double h[NU][NU];
         double trace = 0.0;
-        {
-#pragma unroll
-            for (int u = 0; u < NU; ++u)
-#pragma unroll
-                for (int w = 0; w < NU; ++w) h[u][w] = 0.0;
-            double gacc[4] = {0.0, 0.0, 0.0, 0.0};
-            const double* Ai = As + ta * 2; // (layout of a staged row: wbcqp_types.hpp, apack)
-            const double* Aj = As + te * 2;
-            const double* WB = As + n_dense * 64;
-            auto ldrow = [&](int r, double2v (&ai)[2], double2v (&aj)[2], double2v& wb) __attribute__((always_inline)) {
-                ai[0] = ld2(Ai + r * 64);
-                ai[1] = ld2(Ai + r * 64 + 32);
-                aj[0] = ld2(Aj + r * 64);
-                aj[1] = ld2(Aj + r * 64 + 32);
-                wb = ld2(WB + 2 * r);
-            };
-            auto macrow = [&](const double2v (&ai)[2], const double2v (&aj)[2], const double2v& wb) __attribute__((always_inline)) {
-                const double a[4] = {ai[0].x, ai[0].y, ai[1].x, ai[1].y};
-                const double ajw[4] = {aj[0].x * wb.x, aj[0].y * wb.x, aj[1].x * wb.x, aj[1].y * wb.x};
-#pragma unroll
-                for (int u = 0; u < NU; ++u)
-#pragma unroll
-                    for (int w = u; w < NU; ++w) h[u][w] = fma(a[u], ajw[w], h[u][w]);
-#pragma unroll
-                for (int w = 0; w < NU; ++w) gacc[w] = fma(ajw[w], wb.y, gacc[w]);
-            };
-            if (n_dense > 0) {
-                const int nd = opaque_uniform(n_dense); // (a literal in the specialised builds: as a loop bound it would unroll forty row bodies)
-                double2v ai0[2], aj0[2], ai1[2], aj1[2], wb0, wb1;
-                ldrow(0, ai0, aj0, wb0);
-                int r = 0;
-                for (; r + 2 <= nd; r += 2) {
-                    ldrow(r + 1, ai1, aj1, wb1);
-                    macrow(ai0, aj0, wb0);
-                    ldrow(min(r + 2, nd - 1), ai0, aj0, wb0);
-                    macrow(ai1, aj1, wb1);
-                }
-                if (r < nd) macrow(ai0, aj0, wb0);
-            }
-            if (ta == 0) {
-#pragma unroll
-                for (int w = 0; w < NU; ++w) {
-                    const int col = te + 16 * w;
-                    if (col < nv) c.g[col] = -gacc[w] - c.d[col];
-                }
-            }
-            if (ta == te) {
-#pragma unroll
-                for (int u = 0; u < NU; ++u) {
-                    const int i = ta + 16 * u;
-                    if (i < nv) {
-                        h[u][u] += c.z[i] + S.hessian_reg;
-                        trace += h[u][u];
-                    }
-                }
-            }
-        }
+        // (the row count is a literal in the specialised builds: as a loop bound it would unroll forty row bodies)
+        assemble_hvv<NU>(c, S, As, As + n_dense * 64, opaque_uniform(n_dense), h, trace);
         STAMP(1)
-#pragma unroll
-        for (int u = 0; u < NU; ++u)
-#pragma unroll
-            for (int w = u; w < NU; ++w) {
-                const int r = ta + 16 * u, q = te + 16 * w;
-                if (r >= nv || q >= nv) h[u][w] = (r == q) ? 1.0 : 0.0;
-            }
+        pad_identity<NU>(h, ta, te, nv);
         double y[NU][NU];
 #pragma unroll
         for (int u = 0; u < NU; ++u)
 #pragma unroll
             for (int w = 0; w < NU; ++w) y[u][w] = 0.0;
         const int la = c.lane >> 3, le = c.lane & 7;
-        double hF[2][2], yF[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-        {
-            const int cs = (c.wave < nc) ? c.wave : 0;
-            const double* ftf = S.ftf + cs * 144;
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int w = 0; w < 2; ++w) hF[u][w] = (nc > 0) ? ftf[min(la + 8 * u, 11) * 12 + min(le + 8 * w, 11)] : 0.0;
-        }
+        double hF[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, yF[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        if (nc > 0) load_ftf_tile(S, (c.wave < nc) ? c.wave : 0, la, le, hF);
         // the panels lie behind the staged rows: a fast thread may publish while a slow one still reads its last task row
         publish_panel<4, NU, false, 0>(c, h, y, ta, te, 0, RB, YB);
         eliminate_block<4, NU, false, 0>(c, h, y, ta, te, opaque_uniform((nv + 3) & ~3) /* not a constant for the unroller (a specialised build would lay out thirteen panel bodies: 256 VGPRs + 256 AGPRs + scratch) */, RB, YB, c.dinv, tid >= 128 && tid < 132, tid & 3);
@@ -687,25 +540,8 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 slot[4 + c.wave] = dw;
             }
         }
-        // final: J(r,q) = Y(r,q) dinv[q], J(r,r) = dinv[r]
-#pragma unroll
-        for (int u = 0; u < NU; ++u)
-#pragma unroll
-            for (int w = u; w < NU; ++w) {
-                const int r = ta + 16 * u, q = te + 16 * w;
-                if (q < nv && r < q) c.J[r * ldj + q] = y[u][w] * c.dinv[q];
-                else if (r == q && r < nv) c.J[r * ldj + r] = c.dinv[r];
-            }
-        if (c.wave < nc) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int w = u; w < 2; ++w) {
-                    const int r = la + 8 * u, q = le + 8 * w;
-                    if (q < 12 && r < q) c.J[(fb + r) * ldj + fb + q] = yF[u][w] * c.dinv[fb + q];
-                    else if (r == q && r < 12) c.J[(fb + r) * ldj + fb + r] = c.dinv[fb + r];
-                }
-        }
+        store_j_dv<NU>(c, y, ta, te);
+        if (c.wave < nc) store_j_force(c, yF, fb, la, le);
         bsync();
         {
             const double* slot = c.red + c.rslot * 16;
@@ -717,37 +553,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
     STAMP(3)
 
     // ---------------- x = -H^-1 g = -J (J' g); f = 0.5 g'x ----------------
-    double f_value;
-    {
-        const int idx = tid >> 1, hf = tid & 1;
-        const int ic = min(idx, n - 1);
-        {
-            const int kb0 = blk_begin(ic, nv), len = ic + 1 - kb0, hl = (len + 1) >> 1;
-            const int ka = kb0 + hf * hl, kb = hf ? ic + 1 : kb0 + hl;
-            double dv = dot8(c.J + ic, ldj, c.g, 1, ka, kb);
-            dv += dpp_get<0xB1>(dv);
-            if (hf == 0 && idx < n) c.d[idx] = dv;
-        }
-        for (int i = tid; i < n + 2; i += kThreads) {
-            c.u[i] = 0.0;
-            c.A[i] = 0;
-        }
-        c.iq = 0;
-        bsync();
-        double part = 0.0;
-        {
-            const int ce = blk_end(ic, nv), len = ce - ic, hl = (len + 1) >> 1;
-            const int ca = ic + hf * hl, cb = hf ? ce : ic + hl;
-            double zv = dot8(c.J + ic * ldj, 1, c.d, 1, ca, cb);
-            zv += dpp_get<0xB1>(zv);
-            if (hf == 0 && idx < n) {
-                c.z[idx] = zv;
-                c.x[idx] = -zv;
-                part = 0.5 * c.g[idx] * (-zv);
-            }
-        }
-        f_value = block_sum(c, part); // (its barrier also publishes x0 to the equality phase)
-    }
+    double f_value = unconstrained_minimum(c); // (its barrier also publishes x0 to the equality phase)
     STAMP(4)
 
     const double eps = 2.220446049250313e-16;
@@ -1798,26 +1604,9 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
         }
         if (tid < na) to[tid] = (TI)((double)hav + tact[tid]);
     }
-    if (ga.amask) { // bit r = one-sided row r is active at the solution (the next tick's hint under WBCQP_FLAG_WARM_START)
-        const signed char* actf = reinterpret_cast<const signed char*>(reinterpret_cast<int*>(lds + D.o_int) + cp::IACT);
-        const bool on = (status == HQP_OPTIMAL) && nin2 > 0 && tid < nin2 && actf[tid] != 0;
-        const unsigned long long m = __ballot(on);
-        if (c.lane == 0) {
-            ga.amask[qp * 8 + 2 * c.wave] = (unsigned)(m & 0xffffffffull);
-            ga.amask[qp * 8 + 2 * c.wave + 1] = (unsigned)(m >> 32);
-        }
-    }
-    if (tid == 0) {
-        ga.status[qp] = status;
-        ga.iters[qp] = D.max_iter - left;
-        if (ga.objective) ga.objective[qp] = (TI)f_value;
-        if (ga.n_active) ga.n_active[qp] = c.iq;
-    }
-#ifdef WBCQP_STAMPS
-    STAMP(17)
-    if (tid == WBCQP_STAMP_TID && ga.dbg) // (the stamps are per wave: -DWBCQP_STAMP_TID=192 shows wave 3's view of the phases)
-        for (int i = 0; i < kStamps; ++i) ga.dbg[qp * kStamps + i] = c.st_acc_[i];
-#endif
+    if (ga.amask) // (the next tick's hint under WBCQP_FLAG_WARM_START)
+        write_active_mask(ga, qp, c, (status == HQP_OPTIMAL) && nin2 > 0 && tid < nin2 && act[tid] != 0);
+    write_results(ga, qp, c, status, D.max_iter - left, f_value);
 }
 
 #endif // __HIPCC__

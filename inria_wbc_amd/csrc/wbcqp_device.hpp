@@ -202,7 +202,8 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
     c.iq = 0;
     c.R_norm = 1.0;
 
-    const int n_dense = S.n_dense, n_sel = S.n_sel, n_bound = S.n_bound, r1 = S.r1, n_tasks = S.n_tasks;
+    const Dims D = dims_from(S); // (what the pieces shared with the compact kernels read their sizes from)
+    const int n_dense = S.n_dense;
     const size_t qp = (size_t)b;
     double* As = c.R;  // dense task rows are staged in the (not yet used) R region
 
@@ -231,35 +232,12 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
         }
         // the short vectors: one (clamped) element per thread each
         const TI vh = ga.h[qp * nv + min(tid, nv - 1)];
-        const TI vb1 = ga.b1[qp * r1 + min(tid, r1 - 1)];
-        const TI vw = ga.w[qp * n_tasks + min(tid, n_tasks - 1)];
-        TI vbc = TI(0), vbl = TI(0), vbu = TI(0), vtl = TI(0), vtu = TI(0), vha = TI(0);
+        TI vbc = TI(0);
         if (nc > 0) vbc = ga.bc[qp * (nc * 6) + min(tid, nc * 6 - 1)];
-        if (n_bound > 0) {
-            vbl = ga.blb[qp * n_bound + min(tid, n_bound - 1)];
-            vbu = ga.bub[qp * n_bound + min(tid, n_bound - 1)];
-        }
-        if (S.act_bounds) {
-            vtl = ga.tlb[qp * na + min(tid, na - 1)];
-            vtu = ga.tub[qp * na + min(tid, na - 1)];
-            vha = ga.h[qp * nv + nu + min(tid, na - 1)];
-        }
+        TaskConsts<TI> tk;
+        load_task_constants(ga, S, D, qp, qp, tid, tk);
         const int meta0 = (nin2 > 0) ? S.rowmeta[min(tid, nin2 - 1)] : 0;
         const int meta1 = (nin2 > 0) ? S.rowmeta[min(tid + kThreads, nin2 - 1)] : 0;
-        const int drt = (n_dense > 0) ? S.dense_row_task[min(tid, n_dense - 1)] : 0;
-        // selection rows (posture) and force-regularisation right-hand sides: constants now, arithmetic after the barrier
-        int selc = 0, selt = 0, frt = 0;
-        double ftc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        if (n_sel > 0) {
-            selc = S.sel_col[min(tid, n_sel - 1)];
-            selt = S.sel_task[min(tid, n_sel - 1)];
-        }
-        if (nc > 0) {
-            const int fm = min(tid, k - 1);
-            frt = S.forcereg_task[fm / 12];
-#pragma unroll
-            for (int qd = 0; qd < 6; ++qd) ftc[qd] = S.ft[(fm / 12) * 72 + (fm % 12) * 6 + qd];
-        }
         // while the record is on its way: J starts from zero (only the factorisation's final writes touch it)
         for (int e = tid; e < n * ldj; e += kThreads) c.J[e] = 0.0;
         // ---- land: packed M goes straight to both triangles of the full matrix (offsets from the structure's table)
@@ -288,20 +266,10 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
             if (tid < nc * 6) c.bc[tid] = (double)vbc;
         }
         if (tid < nv) c.h[tid] = (double)vh;
-        if (tid < r1) c.b1[tid] = (double)vb1;
-        if (tid < n_tasks) c.w[tid] = (double)vw;
-        if (tid < n_bound) {
-            c.blb[tid] = (double)vbl;
-            c.bub[tid] = (double)vbu;
-        }
-        if (S.act_bounds && tid < na) { // lb - h_a, ub - h_a (computeProblemData, actuation tasks)
-            c.tl[tid] = (double)vtl - (double)vha;
-            c.tu[tid] = (double)vtu - (double)vha;
-        }
+        land_task_vectors(c, D, tk);
         if (S.cop_task >= 0 && tid < 3 * k) c.xold[tid] = (double)ga.Acop[qp * (size_t)(3 * k) + tid]; // cop rows (slot idle until the loop)
         if (tid < nin2) c.meta[tid] = meta0;
         if (tid + kThreads < nin2) c.meta[tid + kThreads] = meta1;
-        c.iai[tid] = drt; // parked until w has landed (iai is initialised in phase 4)
         // tails of arrays longer than the register rounds (none for the humanoid stacks)
         for (int e = tid + RM * kThreads; e < lenM; e += kThreads) {
             const unsigned pk = S.mpack[e];
@@ -313,30 +281,8 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
         for (int e = tid + RC * kThreads; e < lenAc; e += kThreads) c.Ac[e] = (double)pAc[e];
         for (int e = tid + RT * kThreads; e < lenT; e += kThreads) c.eqw[e] = S.force_gen[e];
         for (int i = tid + 2 * kThreads; i < nin2; i += kThreads) c.meta[i] = S.rowmeta[i];
-        if (tid < nv) { // diagonal additions / right-hand sides of the selection rows
-            c.z[tid] = 0.0;
-            c.d[tid] = 0.0;
-        }
         bsync();
-        if (tid < n_dense) { // (row weight, right-hand side) pairs behind the staged rows: one 16-byte read per row
-            As[n_dense * 64 + 2 * tid] = c.w[c.iai[tid]];
-            As[n_dense * 64 + 2 * tid + 1] = c.b1[tid];
-        }
-        // selection rows (posture): H(c,c) += w, g(c) -= w b  (distinct columns)
-        for (int sidx = tid; sidx < n_sel; sidx += kThreads) {
-            const int col = (sidx == tid) ? selc : S.sel_col[sidx];
-            const double wt = c.w[(sidx == tid) ? selt : S.sel_task[sidx]];
-            c.z[col] = wt;
-            c.d[col] = wt * c.b1[n_dense + sidx];
-        }
-        // force regularisation: g_f = -w F' b
-        if (tid < k) {
-            const double* bb = c.b1 + n_dense + n_sel + 6 * (tid / 12);
-            double sacc = 0.0;
-#pragma unroll
-            for (int qd = 0; qd < 6; ++qd) sacc = fma(ftc[qd], bb[qd], sacc);
-            c.g[nv + tid] = -c.w[frt] * sacc;
-        }
+        stage_task_constants(c, S, D, As, tk);
         // Jc = T' A_c  (12 x nv per contact): thread = (row m of Jc, every G-th column), its six T coefficients in registers
         if (k > 0) {
             const int G = kThreads / k;
@@ -370,72 +316,9 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
         const int ta = tid >> 4, te = tid & 15;
         double h[4][4];
         double trace = 0.0;
-        {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) h[u][w] = 0.0;
-            // rows of the next task line are in flight while this one multiplies; g_j = -sum_r w_r A(r,j) b(r) rides along
-            double gacc[4] = {0.0, 0.0, 0.0, 0.0};
-            const double* Ai = As + ta * 2; // (layout of a staged row: wbcqp_types.hpp, apack)
-            const double* Aj = As + te * 2;
-            const double* WB = As + n_dense * 64;
-            auto ldrow = [&](int r, double2v (&ai)[2], double2v (&aj)[2], double2v& wb) __attribute__((always_inline)) {
-                ai[0] = ld2(Ai + r * 64);
-                ai[1] = ld2(Ai + r * 64 + 32);
-                aj[0] = ld2(Aj + r * 64);
-                aj[1] = ld2(Aj + r * 64 + 32);
-                wb = ld2(WB + 2 * r);
-            };
-            auto macrow = [&](const double2v (&ai)[2], const double2v (&aj)[2], const double2v& wb) __attribute__((always_inline)) {
-                const double a[4] = {ai[0].x, ai[0].y, ai[1].x, ai[1].y};
-                const double ajw[4] = {aj[0].x * wb.x, aj[0].y * wb.x, aj[1].x * wb.x, aj[1].y * wb.x};
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int w = u; w < 4; ++w) h[u][w] = fma(a[u], ajw[w], h[u][w]);
-#pragma unroll
-                for (int w = 0; w < 4; ++w) gacc[w] = fma(ajw[w], wb.y, gacc[w]);
-            };
-            if (n_dense > 0) {
-                double2v ai0[2], aj0[2], ai1[2], aj1[2], wb0, wb1;
-                ldrow(0, ai0, aj0, wb0);
-                int r = 0;
-                for (; r + 2 <= n_dense; r += 2) {
-                    ldrow(r + 1, ai1, aj1, wb1);
-                    macrow(ai0, aj0, wb0);
-                    ldrow(min(r + 2, n_dense - 1), ai0, aj0, wb0);
-                    macrow(ai1, aj1, wb1);
-                }
-                if (r < n_dense) macrow(ai0, aj0, wb0);
-            }
-            if (ta == 0) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const int col = te + 16 * w;
-                    if (col < nv) c.g[col] = -gacc[w] - c.d[col];
-                }
-            }
-            if (ta == te) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int i = ta + 16 * u;
-                    if (i < nv) {
-                        h[u][u] += c.z[i] + S.hessian_reg;
-                        trace += h[u][u];
-                    }
-                }
-            }
-        }
+        assemble_hvv<4>(c, S, As, As + n_dense * 64, n_dense, h, trace);
         STAMP(1)
-        // positions past nv: identity, so that the pivots of the padded last panel are inert
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int w = u; w < 4; ++w) {
-                const int r = ta + 16 * u, q = te + 16 * w;
-                if (r >= nv || q >= nv) h[u][w] = (r == q) ? 1.0 : 0.0;
-            }
+        pad_identity<4>(h, ta, te, nv);
         // ---- H -> J = U^-1 by blocked elimination (eliminate_block), four pivots per barrier
         double y[4][4];
 #pragma unroll
@@ -445,64 +328,23 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
         // the force-regularisation blocks H_ff = w F'F + reg I (12 x 12 per contact) go one per wave afterwards; their
         // constants are fetched now so that the loads overlap the dv block
         const int la = c.lane >> 3, le = c.lane & 7;
-        double hF[2][2], yF[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
-        {
-            const int cs = (c.wave < nc) ? c.wave : 0;
-            const double* ftf = S.ftf + cs * 144;
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int w = 0; w < 2; ++w) hF[u][w] = (nc > 0) ? ftf[min(la + 8 * u, 11) * 12 + min(le + 8 * w, 11)] : 0.0;
-        }
+        double hF[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, yF[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+        if (nc > 0) load_ftf_tile(S, (c.wave < nc) ? c.wave : 0, la, le, hF);
         publish_panel<4, 4, false, 0>(c, h, y, ta, te, 0, c.s, c.stash);
         eliminate_block<4, 4, false, 0>(c, h, y, ta, te, (nv + 3) & ~3, c.s, c.stash, c.dinv, tid >= 128 && tid < 132, tid & 3);
         STAMP(2)
         bsync();
-        // final: J(r,q) = Y(r,q) dinv[q], J(r,r) = dinv[r]
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int w = u; w < 4; ++w) {
-                const int r = ta + 16 * u, q = te + 16 * w;
-                if (q < nv && r < q) c.J[r * ldj + q] = y[u][w] * c.dinv[q];
-                else if (r == q && r < nv) c.J[r * ldj + r] = c.dinv[r];
-            }
+        store_j_dv<4>(c, y, ta, te);
         // ---- force blocks: wave-local (8 x 8 lane grid, 2 x 2 positions per lane), no workgroup barrier inside
         for (int ct = c.wave; ct < nc; ct += kWaves) {
             const int fb = nv + 12 * ct;
-            const double wt = c.w[S.forcereg_task[ct]];
-            if (ct != c.wave) { // contacts beyond the first four: fetch now
-                const double* ftf = S.ftf + ct * 144;
-#pragma unroll
-                for (int u = 0; u < 2; ++u)
-#pragma unroll
-                    for (int w = 0; w < 2; ++w) hF[u][w] = ftf[min(la + 8 * u, 11) * 12 + min(le + 8 * w, 11)];
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int w = 0; w < 2; ++w) {
-                    const int r = la + 8 * u, q = le + 8 * w;
-                    if (r < 12 && q < 12) {
-                        hF[u][w] = wt * hF[u][w] + ((r == q) ? S.hessian_reg : 0.0);
-                        if (r == q) trace += hF[u][w];
-                    }
-                    else hF[u][w] = (r == q) ? 1.0 : 0.0;
-                    yF[u][w] = 0.0;
-                }
-            double* RBf = c.s + c.wave * 128;
-            double* YBf = RBf + 64;
-            publish_panel<3, 2, true, 0>(c, hF, yF, la, le, 0, RBf, YBf);
-            eliminate_block<3, 2, true, 0>(c, hF, yF, la, le, 12, RBf, YBf, c.dinv + fb, c.lane < 4, c.lane & 3);
+            if (ct != c.wave) load_ftf_tile(S, ct, la, le, hF); // contacts beyond the first four: fetch now
+            double tF[2];
+            force_block_factor(c, hF, yF, tF, c.w[S.forcereg_task[ct]], S.hessian_reg, la, le, c.s + c.wave * 128, c.s + c.wave * 128 + 64, c.dinv + fb, c.lane);
+            trace += tF[0];
+            trace += tF[1];
             __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int w = u; w < 2; ++w) {
-                    const int r = la + 8 * u, q = le + 8 * w;
-                    if (q < 12 && r < q) c.J[(fb + r) * ldj + fb + q] = yF[u][w] * c.dinv[fb + q];
-                    else if (r == q && r < 12) c.J[(fb + r) * ldj + fb + r] = c.dinv[fb + r];
-                }
+            store_j_force(c, yF, fb, la, le);
         }
         bsync();
         c1 = block_sum(c, trace);
@@ -513,39 +355,7 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
     STAMP(3)
 
     // ---------------- x = -H^-1 g = -J (J' g); f = 0.5 g'x ----------------
-    // J = U^-1 is still upper triangular and block diagonal here: both products run over the structural range only, two
-    // lanes per column / row whose halves meet by DPP (2 n <= 256).
-    double f_value;
-    {
-        const int idx = tid >> 1, hf = tid & 1;
-        const int ic = min(idx, n - 1);
-        {
-            const int kb0 = blk_begin(ic, c.nblk), len = ic + 1 - kb0, hl = (len + 1) >> 1;
-            const int ka = kb0 + hf * hl, kb = hf ? ic + 1 : kb0 + hl;
-            double dv = dot8(c.J + ic, ldj, c.g, 1, ka, kb);
-            dv += dpp_get<0xB1>(dv);
-            if (hf == 0 && idx < n) c.d[idx] = dv;
-        }
-        for (int i = tid; i < n + 2; i += kThreads) {
-            c.u[i] = 0.0;
-            c.A[i] = 0;
-        }
-        c.iq = 0;
-        bsync();
-        double part = 0.0;
-        {
-            const int ce = blk_end(ic, c.nblk), len = ce - ic, hl = (len + 1) >> 1;
-            const int ca = ic + hf * hl, cb = hf ? ce : ic + hl;
-            double zv = dot8(c.J + ic * ldj, 1, c.d, 1, ca, cb);
-            zv += dpp_get<0xB1>(zv);
-            if (hf == 0 && idx < n) {
-                c.z[idx] = zv;
-                c.x[idx] = -zv;
-                part = 0.5 * c.g[idx] * (-zv);
-            }
-        }
-        f_value = block_sum(c, part);
-    }
+    double f_value = unconstrained_minimum(c);
     STAMP(4)
 
     const double eps = 2.220446049250313e-16;
@@ -904,25 +714,9 @@ __device__ __forceinline__ void solve_one(const GroupArgs<TI>& ga, const DevStru
         }
         for (int rr = tid; rr < na; rr += kThreads) to[rr] = (TI)(c.h[nu + rr] + tact[rr]);
     }
-    if (ga.amask) { // bit r = one-sided row r (r < 256) is active at the solution; this layout does not take the mask as a hint
-        const bool on = (status == HQP_OPTIMAL) && nin2 > 0 && tid < nin2 && c.iai[tid] == -1;
-        const unsigned long long m = __ballot(on);
-        if ((tid & 63) == 0) {
-            ga.amask[qp * 8 + 2 * (tid >> 6)] = (unsigned)(m & 0xffffffffull);
-            ga.amask[qp * 8 + 2 * (tid >> 6) + 1] = (unsigned)(m >> 32);
-        }
-    }
-    if (tid == 0) {
-        ga.status[qp] = status;
-        ga.iters[qp] = iter;
-        if (ga.objective) ga.objective[qp] = (TI)f_value;
-        if (ga.n_active) ga.n_active[qp] = c.iq;
-    }
-#ifdef WBCQP_STAMPS
-    STAMP(17)
-    if (tid == WBCQP_STAMP_TID && ga.dbg) // (the stamps are per wave: -DWBCQP_STAMP_TID=192 shows wave 3's view of the phases)
-        for (int i = 0; i < kStamps; ++i) ga.dbg[qp * kStamps + i] = c.st_acc_[i];
-#endif
+    if (ga.amask) // (this layout does not take the mask as a hint)
+        write_active_mask(ga, qp, c, (status == HQP_OPTIMAL) && nin2 > 0 && tid < nin2 && c.iai[tid] == -1);
+    write_results(ga, qp, c, status, iter, f_value);
 }
 
 // The QPs of a launch are numbered group after group.  Launch position b -> the group it falls in (returned) and its index in that group (left

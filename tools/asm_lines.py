@@ -3,7 +3,7 @@
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 -fno-gpu-rdc -ffp-contract=on --cuda-device-only -gline-tables-only -S \
           -o k.s inria_wbc_amd/csrc/wbcqp_api.hip
-    python tools/asm_lines.py k.s _ZN5wbcqp18solve_queue_kernelIdLb1ELi1E wbcqp_compact.hpp 939 1362
+    python tools/asm_lines.py k.s _ZN5wbcqp18solve_queue_kernelIdLb1ELi1E wbcqp_compact.hpp 1021 1581      # (the inequality loop of solve_one_compact)
 
 Prints, for the given file and line range, the instructions whose innermost .loc names that line, split into VALU / SALU / LDS /
 VMEM / other (inlined callees are attributed to the line of the call through the `inlined_at` chain clang prints as comments is
