@@ -51,7 +51,9 @@ extern "C" {
  *        Added without a change of version: wbcqp_mix, wbcqp_mixed_io, wbcqp_tick_mixed and wbcqp_rollout_mixed (instances of one robot model in
  *        different contact sets, one call); wbcqp_trace, wbcqp_task_costs, wbcqp_rollout_traced and wbcqp_rollout_mixed_traced (per-task costs on
  *        the device, per-tick results of a roll-out); wbcqp_program, wbcqp_track, wbcqp_segment, wbcqp_check_program, wbcqp_reference_samples,
- *        wbcqp_rollout_program and wbcqp_rollout_mixed_program (the references of a roll-out generated on the device from a reference program)
+ *        wbcqp_rollout_program and wbcqp_rollout_mixed_program (the references of a roll-out generated on the device from a reference program);
+ *        wbcqp_observables, wbcqp_set_observed_frames, wbcqp_observe and wbcqp_observe_host (centre of mass and world placements / velocities of
+ *        chosen model frames from (q, v) on the device); wbcqp_set_model now keeps the model's whole frame table on the host
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -587,6 +589,39 @@ int wbcqp_rollout_traced(wbcqp_handle* handle, int slot, int batch, int n_ticks,
                          void* stream);
 int wbcqp_rollout_mixed_traced(wbcqp_handle* handle, const wbcqp_mix* mix, int batch, int n_ticks, const int32_t* schedule,
                                const wbcqp_rollout_io* io, const wbcqp_trace* trace, void* stream);
+
+/* ---- Where the robots are: centre of mass and frame poses from (q, v) ----
+ * What the reference's controller exposes one robot at a time as com() and model_frame_pos(name) (controller.hpp:110,141-146) and its drivers log every
+ * tick as com, lf, rh, ... beside cost_<task>.  One wavefront per instance (observe_kernel, csrc/wbcqp_observe.hpp): the rows kernel's kinematics in the
+ * true world frame.  Per instance, each output optional:
+ *     com       [3]            sum_i m_i (p_i + R_i c_i) / sum_i m_i
+ *     vcom      [3]            its velocity (= the first three entries of wbcqp_state.momentum over the total mass)
+ *     placement [n_frames][12] world placement of every observed frame: rotation row-major (9), translation (3) -- the layout of wbcqp_model.placement
+ *                              (pinocchio's oMf)
+ *     velocity  [n_frames][6]  linear (3), angular (3) velocity of the frame in ITS OWN axes (tsid RobotWrapper::frameVelocity)
+ * No atomics, a fixed order of summation, and an instance's result depends on its own (q, v) row alone: the same bits from run to run and at whatever
+ * index or batch size the row arrives (F32 handles read float, compute in double, write float).
+ * A trace needs no entry point of its own: wbcqp_trace.q and wbcqp_trace.v are [n_rec][batch][.] arrays, so one call with batch = n_rec * batch on those
+ * pointers observes every recorded tick (bit for bit n_rec calls, one per tick).  Likewise a mixed fleet: the observables depend on the tree alone, which
+ * every slot of a mix shares, so any slot of the mix serves (each slot keeps its own selection of frames). */
+#define WBCQP_MAX_OBSERVED 64
+typedef struct {
+    void* com;       /* [batch][3] */
+    void* vcom;      /* [batch][3] */
+    void* placement; /* [batch][n_frames][12] */
+    void* velocity;  /* [batch][n_frames][6] */
+} wbcqp_observables; /* each may be NULL: not computed */
+/* Which frames of the slot's model are observed: indices into wbcqp_model's frame tables (frames: HOST [n_frames], repeats allowed, n_frames 0 .. 64),
+ * uploaded once.  The slot needs a model; a later wbcqp_set_structure or wbcqp_set_model on the slot drops the selection, as it drops the model.
+ * WBCQP_ERR_INVALID for a slot without a model, n_frames outside 0 .. WBCQP_MAX_OBSERVED, a frame index outside the model. */
+int wbcqp_set_observed_frames(wbcqp_handle* handle, int slot, int n_frames, const int32_t* frames);
+/* q [batch][nq], v [batch][nv] and the outputs are DEVICE pointers of the handle's dtype; nothing is copied from the host.  v may be NULL when vcom and
+ * velocity are.  Asynchronous on `stream`, ordered like wbcqp_task_costs.  Refused with WBCQP_ERR_INVALID before anything is launched: a slot without a
+ * model, batch < 0, placement or velocity given while no frames are selected, vcom or velocity given with v == NULL.  batch == 0: WBCQP_OK, nothing
+ * launched. */
+int wbcqp_observe(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream);
+/* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done. */
+int wbcqp_observe_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out);
 
 /* ---- References generated on the device from a reference program ----
  * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the

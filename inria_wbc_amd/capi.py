@@ -30,7 +30,9 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_problem_data_host", "wbcqp_tick", "wbcqp_tick_host", "wbcqp_tick_graph_create", "wbcqp_tick_graph_launch", "wbcqp_tick_graph_destroy",
            "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout",
            "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced",
-           "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program")
+           "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program",
+           "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host")
+OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe writes (wbcqp_observables); per instance 3, 3, n_frames x 12, n_frames x 6
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
 
@@ -154,6 +156,10 @@ class CProgram(C.Structure):
                 ("n_cycle", C.c_int32), ("dt", C.c_double), ("n_tracks", C.c_int32), ("tracks", C.POINTER(CTrack)), ("set_of", c_i32_p)]
 
 
+class CObservables(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in OBSERVABLES]
+
+
 def load_library(path: Optional[str] = None):
     """Loads libwbcqp.so -- after torch, when torch is installed: the library links libamdhip64.so.7, and a process in which it comes FIRST gets
     /opt/rocm's HIP runtime while a later `import torch` brings torch's bundled one.  Two runtimes on one GPU work, but the first one then answers
@@ -208,6 +214,9 @@ def load_library(path: Optional[str] = None):
                                           C.c_void_p]
     lib.wbcqp_rollout_mixed_program.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CProgram),
                                                 C.POINTER(CTrace), C.c_void_p]
+    lib.wbcqp_set_observed_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
+    lib.wbcqp_observe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p]
+    lib.wbcqp_observe_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables)]
     _lib = lib
     return lib
 
@@ -390,6 +399,7 @@ class Handle:
         self.device = device
         self._h = C.c_void_p()
         self._structs: Dict[int, Structure] = {}
+        self._observed: Dict[int, int] = {}  # slot -> number of frames selected by set_observed_frames
         desc = CDesc(device, dtype, flags)
         rc = self.lib.wbcqp_create(C.byref(desc), C.byref(self._h))
         if rc != WBCQP_OK:
@@ -414,6 +424,7 @@ class Handle:
         sb = StructureBuffers(st)
         self._check(self.lib.wbcqp_set_structure(self._h, slot, C.byref(sb.c)))
         self._structs[slot] = st
+        self._observed.pop(slot, None)  # (the library drops the selection with the model)
 
     # ---- device-pointer path (torch tensors are only carriers of device memory) ----
     def _pack(self, slot: int, batch: int, inputs, outputs):
@@ -452,8 +463,42 @@ class Handle:
         """Binds a kinematic tree and its task bindings to a slot that holds the matching structure (wbcqp_set_model)."""
         mb = ModelBuffers(model, tm)
         self._check(self.lib.wbcqp_set_model(self._h, slot, C.byref(mb.model), C.byref(mb.taskmap)))
+        self._observed.pop(slot, None)
         self._models = getattr(self, "_models", {})
         self._models[slot] = (model, tm)
+
+    def set_observed_frames(self, slot: int, frames: Sequence[int]):
+        """Which frames of the slot's model wbcqp_observe reports: indices into the model's frame table (observe.frame_ids turns names into
+        them), repeats allowed, at most 64 (wbcqp_set_observed_frames)."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        self._check(self.lib.wbcqp_set_observed_frames(self._h, slot, int(fr.size), fr.ctypes.data_as(c_i32_p)))
+        self._observed[slot] = int(fr.size)
+
+    def observe(self, slot: int, batch: int, q, v=None, com=None, vcom=None, placement=None, velocity=None, stream: int = 0):
+        """CoM and frame poses of `batch` states on device tensors (wbcqp_observe): q [batch, nq], v [batch, nv] (None when neither vcom nor
+        velocity is asked for); outputs, each optional: com / vcom [batch, 3], placement [batch, n_frames, 12], velocity [batch, n_frames, 6]."""
+        out = CObservables(self._ptr(com), self._ptr(vcom), self._ptr(placement), self._ptr(velocity))
+        self._check(self.lib.wbcqp_observe(self._h, slot, int(batch), self._ptr(q), self._ptr(v), C.byref(out), C.c_void_p(stream)))
+
+    def observe_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+        """wbcqp_observe_host: dict(com [B, 3], placement [B, n_frames, 12]) and, when v is given, vcom [B, 3] and velocity [B, n_frames, 6]
+        (placement / velocity only when frames are selected).  The library cannot be asked how many frames a slot observes, so the outputs are
+        sized from what THIS Handle's set_observed_frames last selected on the slot: a selection made any other way (the raw library, another
+        wrapper of the same handle) is not seen here -- such callers size their own buffers and use observe()."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B = q.shape[0]
+        nf = self._observed.get(slot, 0)
+        res = {"com": np.zeros((B, 3), self.np_dtype)}
+        if nf:
+            res["placement"] = np.zeros((B, nf, 12), self.np_dtype)
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=self.np_dtype)
+            res["vcom"] = np.zeros((B, 3), self.np_dtype)
+            if nf:
+                res["velocity"] = np.zeros((B, nf, 6), self.np_dtype)
+        out = CObservables(*[res[k].ctypes.data if k in res else None for k in OBSERVABLES])
+        self._check(self.lib.wbcqp_observe_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out)))
+        return res
 
     def problem_data(self, slot: int, batch: int, state: Dict[str, "object"], rows: Dict[str, "object"], stream: int = 0):
         """q, v, ref -> M, h, A, b1, Ac, bc, blb, bub on device tensors (wbcqp_problem_data)."""

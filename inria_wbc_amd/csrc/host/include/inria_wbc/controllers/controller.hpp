@@ -91,6 +91,12 @@ namespace inria_wbc {
             virtual void set_contact_se3_ref(const std::string&, const std::vector<double>&) {}  // 12 numbers, or 24 with derivatives
             virtual const double* reference_data() const { return nullptr; }                   // [batch][nref] for wbcqp_tick_host
             virtual void fill_limits(const wbcqp_layout&, TickInputs&) const {}                // constant tlb / tub
+            // where the robots are at the states (q, v): CoM and its velocity (B x 3 each), world placement (B x 12 n: rotation row-major, translation)
+            // and local velocity (B x 6 n: linear, angular) of the n named model frames -- wbcqp_observe_host.  Only a source that holds a model can tell
+            virtual void observe(const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, MatrixXd&, MatrixXd&, MatrixXd&, MatrixXd&)
+            {
+                IWBC_ERROR("this problem source has no model: com_now / model_frame_pos / model_frame_vel need a model-driven source (CONTROLLER.model)");
+            }
         };
 
         class Controller {
@@ -227,6 +233,26 @@ namespace inria_wbc {
             const VectorXi& qp_status() const { return status_; }
             const VectorXi& qp_iterations() const { return iters_; }
             virtual double cost(const std::string& task_name) const = 0;
+
+            // the CoM as the problem source reports it (a model-driven source: the CoM at q0, filled once; com_now() below is the live one)
+            void com(MatrixXd& pos, MatrixXd& vel) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                source_->com(pos, vel);
+            }
+            // Where the robots are NOW -- at the controller's current state (q_tsid(), dq(): after the last tick's integration), computed on the
+            // device by wbcqp_observe_host when somebody asks and kept until the next tick: the batched counterparts of the reference's com() and
+            // model_frame_pos(name) (controller.hpp:110,141-146).  com() of this facade keeps returning the CoM at q0.
+            void com_now(MatrixXd& pos, MatrixXd& vel) const
+            {
+                _ensure_observed(nullptr);
+                pos = obs_com_;
+                vel = obs_vcom_;
+            }
+            // B x 12: rotation row-major (9), translation (3) of the model frame in the world (pinocchio's oMf)
+            MatrixXd model_frame_pos(const std::string& frame) const { return _observed_block(obs_place_, _ensure_observed(&frame), 12); }
+            // B x 6: linear (3), angular (3) velocity of the frame in its own axes (tsid RobotWrapper::frameVelocity)
+            MatrixXd model_frame_vel(const std::string& frame) const { return _observed_block(obs_vel_, _ensure_observed(&frame), 6); }
 
             void set_problem_source(const std::shared_ptr<ProblemSource>& src)
             {
@@ -381,6 +407,52 @@ namespace inria_wbc {
                 self->source_->compute(t_ - dt_, last_q_, last_v_, _stack(), _layout(), self->in_);
                 self->rows_valid_ = true;
             }
+
+            // the observables of the current state, fetched on demand like the rows above: one wbcqp_observe_host per tick at the most (a frame
+            // asked for the first time joins the selection and costs one more).  The answer is kept WITH the state and the source it was made
+            // for, so whatever moves q_tsid_ / v_tsid_ (a tick, qp_step_back, _reset) or replaces the source makes the next call fetch again.
+            // Returns the frame's place in the selection (-1: none asked)
+            int _ensure_observed(const std::string* frame) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                auto self = const_cast<Controller*>(this);
+                int at = -1;
+                bool added = false;
+                if (frame) {
+                    auto it = std::find(obs_names_.begin(), obs_names_.end(), *frame);
+                    at = (int)std::distance(obs_names_.begin(), it);
+                    if (it == obs_names_.end()) {
+                        self->obs_names_.push_back(*frame);
+                        added = true;
+                    }
+                }
+                const bool current = !added && obs_source_ == source_.get() && obs_q_.rows == q_tsid_.rows && obs_q_.data == q_tsid_.data &&
+                                     obs_v_.data == v_tsid_.data;
+                if (!current) {
+                    self->obs_source_ = nullptr;
+                    try {
+                        self->source_->observe(q_tsid_, v_tsid_, obs_names_, self->obs_com_, self->obs_vcom_, self->obs_place_, self->obs_vel_);
+                    }
+                    catch (...) {
+                        if (added) self->obs_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
+                        throw;
+                    }
+                    self->obs_q_ = q_tsid_;
+                    self->obs_v_ = v_tsid_;
+                    self->obs_source_ = source_.get();
+                }
+                return at;
+            }
+            static MatrixXd _observed_block(const MatrixXd& all, int at, int width)
+            {
+                MatrixXd out(all.rows, width);
+                for (int i = 0; i < all.rows; ++i) std::copy(all.row(i) + (size_t)at * width, all.row(i) + (size_t)(at + 1) * width, out.row(i));
+                return out;
+            }
+            std::vector<std::string> obs_names_;
+            MatrixXd obs_com_, obs_vcom_, obs_place_, obs_vel_;
+            MatrixXd obs_q_, obs_v_;                     // the state the four above were computed at
+            const ProblemSource* obs_source_ = nullptr; // ... and by which source (null: nothing kept)
 
             std::shared_ptr<ProblemSource> source_;
             TickInputs in_;

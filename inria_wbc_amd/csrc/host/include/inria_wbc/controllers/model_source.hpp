@@ -194,6 +194,32 @@ namespace inria_wbc {
             {
                 if (cur_ && bounds_.count(slot) && cur_ == &bounds_[slot]) cur_ = nullptr;
                 bounds_.erase(slot);
+                observed_.erase(slot); // (the library drops the selection with the model)
+            }
+
+            // wbcqp_observe_host on the slot in use; the selection of frames goes to the device when it changes, not per call
+            void observe(const MatrixXd& q, const MatrixXd& v, const std::vector<std::string>& frames, MatrixXd& com, MatrixXd& vcom, MatrixXd& place,
+                         MatrixXd& vel) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq() && v.rows == batch_ && v.cols == robot_->nv(), "one state row per instance");
+                IWBC_ASSERT((int)frames.size() <= WBCQP_MAX_OBSERVED, "at most ", WBCQP_MAX_OBSERVED, " frames can be observed");
+                auto known = observed_.find(slot_);
+                if (known == observed_.end() || known->second != frames) {
+                    std::vector<int32_t> ids;
+                    for (const auto& f : frames) ids.push_back(robot_->getFrameId(f));
+                    if (wbcqp_set_observed_frames(handle_, slot_, (int)ids.size(), ids.data()) != WBCQP_OK)
+                        IWBC_ERROR("wbcqp_set_observed_frames failed: ", wbcqp_last_error(handle_));
+                    observed_[slot_] = frames;
+                }
+                const int n = (int)frames.size();
+                com = MatrixXd(batch_, 3);
+                vcom = MatrixXd(batch_, 3);
+                place = MatrixXd(batch_, 12 * n);
+                vel = MatrixXd(batch_, 6 * n);
+                wbcqp_observables out = {com.data.data(), vcom.data.data(), n ? place.data.data() : nullptr, n ? vel.data.data() : nullptr};
+                if (wbcqp_observe_host(handle_, slot_, batch_, q.data.data(), v.data.data(), &out) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_observe_host failed: ", wbcqp_last_error(handle_));
             }
 
             void compute(double, const MatrixXd& q, const MatrixXd& v, const tasks::TaskStack& stack, const wbcqp_layout& L, TickInputs& in) override
@@ -315,6 +341,7 @@ namespace inria_wbc {
             std::vector<double> q0_, posture_user_;
             wbcqp_handle* handle_ = nullptr;
             std::map<int, Bound> bounds_;
+            std::map<int, std::vector<std::string>> observed_; // slot -> the frames selected on it (wbcqp_set_observed_frames)
             Bound* cur_ = nullptr;
             std::map<std::string, std::vector<double>> named_;
             MatrixXd com_pos_, com_vel_;

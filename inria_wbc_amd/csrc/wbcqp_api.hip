@@ -577,7 +577,85 @@ int wbcqp_set_model(wbcqp_handle* h, int slot, const wbcqp_model* md, const wbcq
     }
     s.tree.insert(s.tree.end(), md->placement, md->placement + 12 * nb);
     s.tree.insert(s.tree.end(), md->inertia, md->inertia + 10 * nb);
+    s.frame_body_h.assign(md->frame_body, md->frame_body + md->nframe); // (derive_terms has checked the table)
+    s.frame_place_h.assign(md->frame_placement, md->frame_placement + (size_t)12 * md->nframe);
     return WBCQP_OK;
+}
+
+int wbcqp_set_observed_frames(wbcqp_handle* h, int slot, int n_frames, const int32_t* frames)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (n_frames < 0 || n_frames > WBCQP_MAX_OBSERVED) return fail(h, WBCQP_ERR_INVALID, "n_frames must be in [0, 64]");
+    if (n_frames > 0 && !frames) return fail(h, WBCQP_ERR_INVALID, "frames is NULL");
+    const int nframe = (int)s->frame_body_h.size();
+    std::vector<int> body(n_frames);
+    std::vector<double> place((size_t)12 * n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        if (frames[f] < 0 || frames[f] >= nframe) return fail(h, WBCQP_ERR_INVALID, "an observed frame does not exist in the slot's model");
+        body[f] = s->frame_body_h[frames[f]];
+        std::copy(s->frame_place_h.begin() + (size_t)12 * frames[f], s->frame_place_h.begin() + (size_t)12 * frames[f] + 12, place.begin() + (size_t)12 * f);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    release_observed(*s); // (hipFree waits for whatever still reads the previous selection)
+    if (n_frames == 0) return WBCQP_OK;
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s->obs_body), body.size() * sizeof(int)));
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s->obs_place), place.size() * sizeof(double)));
+    HIP_TRY(h, hipMemcpy(s->obs_body, body.data(), body.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(s->obs_place, place.data(), place.size() * sizeof(double), hipMemcpyHostToDevice));
+    s->n_obs = n_frames;
+    return WBCQP_OK;
+}
+
+int wbcqp_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "observables struct is NULL");
+    if ((out->placement || out->velocity) && s->n_obs == 0)
+        return fail(h, WBCQP_ERR_INVALID, "placement / velocity asked for, but no frames are selected (wbcqp_set_observed_frames)");
+    if ((out->vcom || out->velocity) && !v) return fail(h, WBCQP_ERR_INVALID, "vcom / velocity asked for, but v is NULL");
+    if (batch == 0 || (!out->com && !out->vcom && !out->placement && !out->velocity)) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const TermsDev& T = s->terms;
+    const bool frames = out->placement || out->velocity;
+    const ObserveDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_idxq, T.i_idxv, T.i_anc, T.d_place, T.d_inertia,
+                       frames ? s->n_obs : 0, s->obs_body, s->obs_place};
+    const int blocks = (batch + kObservePerBlock - 1) / kObservePerBlock;
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const ObserveArgs<TI> a{D, static_cast<const TI*>(q), (out->vcom || out->velocity) ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out->com),
+                                static_cast<TI*>(out->vcom), static_cast<TI*>(out->placement), static_cast<TI*>(out->velocity), batch};
+        hipLaunchKernelGGL(observe_kernel<TI>, dim3(blocks), dim3(kObserveThreads), observe_lds_bytes(D.n_frames), static_cast<hipStream_t>(stream), a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+int wbcqp_observe_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "observables struct is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nf = (size_t)s->n_obs;
+    Arr up[2] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * s->terms.nv * es, 0}};
+    Arr dn[4] = {{-1, out->com, B * 3 * es, 0}, {-1, out->vcom, B * 3 * es, 0}, {-1, out->placement, B * nf * 12 * es, 0}, {-1, out->velocity, B * nf * 6 * es, 0}};
+    WB_TRY(stage_begin(h, lay(up, 2), lay(dn, 4), false));
+    WB_TRY(stage_up(h, h->stage_in.dev, up, 2, 0, Xfer::blocking));
+    char* din = static_cast<char*>(h->stage_in.dev);
+    char* dout = static_cast<char*>(h->stage_out.dev);
+    const wbcqp_observables d = {out->com ? dout + dn[0].off : nullptr, out->vcom ? dout + dn[1].off : nullptr, out->placement ? dout + dn[2].off : nullptr,
+                                 out->velocity ? dout + dn[3].off : nullptr};
+    WB_TRY(wbcqp_observe(h, slot, batch, q ? din + up[0].off : nullptr, v ? din + up[1].off : nullptr, &d, nullptr));
+    HIP_TRY(h, hipDeviceSynchronize());
+    return stage_down(h, dout, dn, 4, 0, Xfer::blocking);
 }
 
 int wbcqp_problem_data(wbcqp_handle* h, int slot, int batch, const wbcqp_state* st, const wbcqp_inputs* rows, void* stream)

@@ -7,6 +7,7 @@
 #include "wbcqp_dense.hpp"
 #include "wbcqp_small.hpp"
 #include "wbcqp_costs.hpp"
+#include "wbcqp_observe.hpp"
 
 #include "../../include/wbcqp.h"
 
@@ -45,6 +46,13 @@ struct Slot {
     std::vector<double> tree;   // ... the tree as numbers (sizes, parents, joint types, placements, inertias, gravity): the slots of a mix must agree on it
     TermsDev terms{};
     std::vector<void*> model_allocs;
+    // wbcqp_observe: the model's whole frame table (host copies: only task frames reach the device with the model) and the frames chosen by
+    // wbcqp_set_observed_frames, on the device; dropped with the model
+    std::vector<int> frame_body_h;
+    std::vector<double> frame_place_h;
+    int n_obs = 0;
+    int* obs_body = nullptr;
+    double* obs_place = nullptr;
 };
 
 struct Staging {
@@ -291,12 +299,24 @@ int upload(wbcqp_handle* h, Slot& s, const T* src, size_t count, const T** dst)
     return WBCQP_OK;
 }
 
+void release_observed(Slot& s)
+{
+    if (s.obs_body) (void)hipFree(s.obs_body);
+    if (s.obs_place) (void)hipFree(s.obs_place);
+    s.obs_body = nullptr;
+    s.obs_place = nullptr;
+    s.n_obs = 0;
+}
+
 void release_model(Slot& s)
 {
     for (void* p : s.model_allocs) (void)hipFree(p);
     s.model_allocs.clear();
     s.has_model = false;
     s.tree.clear();
+    s.frame_body_h.clear();
+    s.frame_place_h.clear();
+    release_observed(s);
 }
 
 void release(Slot& s)

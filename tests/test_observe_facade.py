@@ -1,0 +1,64 @@
+"""Where the robots are, through the C++ facade (inria_wbc_amd/csrc/host): Controller::com_now, model_frame_pos and model_frame_vel on a
+model-driven controller (wbcqp_observe_host behind ModelSource), and their refusal on a FileSource."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FRAMES = ["leg_left_6_joint", "gripper_right_joint", "base_link"]
+
+
+@pytest.fixture(scope="module")
+def host_build(built_lib):
+    from inria_wbc_amd import build
+    return build.build_host()
+
+
+@pytest.mark.gpu
+def test_com_now_and_model_frames_after_move_com(host_build, tmp_path):
+    """20 ticks of humanoid::move_com (the squat) on 4 Talos instances: com_now has left com() (the CoM at q0), equals RobotWrapper::com of
+    the controller's current q to 1e-10, model_frame_pos equals RobotWrapper::framePosition (the program checks both), and everything
+    written equals the numpy statement on the same state."""
+    from inria_wbc_amd import model as mdl, observe
+    B, out = 4, str(tmp_path / "obs.bin")
+    r = subprocess.run([host_build["observe_facade_test"], os.path.join(ROOT, "configs/talos/pos_tracker_model.yaml"),
+                        os.path.join(ROOT, "configs/talos/squat.yaml"), "20", str(B), out] + FRAMES, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = dict(ln.split(": ", 1) for ln in r.stdout.splitlines() if ": " in ln)
+    assert lines["instances"] == str(B)
+    assert float(lines["max |com_now - com()|"]) > 1e-9  # (20 ms into a 2 s min-jerk move the reference itself has gone 2e-6 m)
+    assert float(lines["max |com_now - RobotWrapper::com(q)|"]) <= 1e-10
+    assert float(lines["max |model_frame_pos - RobotWrapper::framePosition(q)|"]) <= 1e-10
+    # asked twice in a tick: one trip to the device (counted in the problem source); after qp_step_back and after a new problem source the
+    # accessors answer for the state the controller then holds
+    assert lines["cached"] == "1 unknown frame refused: 1 then still answering: 1", r.stdout
+    assert float(lines["max |com_now, model_frame_pos after qp_step_back - RobotWrapper at the restored q|"]) <= 1e-10
+    assert float(lines["max |com_now after qp_step_back - com_now before it|"]) > 1e-9
+    assert float(lines["max |com_now after a new problem source - com()|"]) <= 1e-10
+    m = mdl.talos_like()
+    a = np.fromfile(out, dtype=np.float64)
+    sizes = [B * m.nq, B * m.nv, B * 3, B * 3] + [B * 12, B * 6] * len(FRAMES)
+    assert a.size == sum(sizes)
+    parts = np.split(a, np.cumsum(sizes)[:-1])
+    q, v = parts[0].reshape(B, m.nq), parts[1].reshape(B, m.nv)
+    want = observe.observe(m, q, v, observe.frame_ids(m, FRAMES))
+    bar = lambda got, w: np.abs(got - w).max() <= 1e-10 * max(1.0, np.abs(w).max())  # noqa: E731
+    assert bar(parts[2].reshape(B, 3), want["com"]) and bar(parts[3].reshape(B, 3), want["vcom"])
+    assert np.abs(want["vcom"]).max() > 1e-6  # the squat is under way
+    for k in range(len(FRAMES)):
+        assert bar(parts[4 + 2 * k].reshape(B, 12), want["placement"][:, k]), FRAMES[k]
+        assert bar(parts[5 + 2 * k].reshape(B, 6), want["velocity"][:, k]), FRAMES[k]
+
+
+@pytest.mark.gpu
+def test_file_source_refuses_the_accessors(host_build, tmp_path):
+    from tools import dump_batch
+    from inria_wbc_amd import structure, synth
+    st = structure.talos_structure()
+    path = str(tmp_path / "b.bin")
+    dump_batch.dump(path, st, synth.generate(st, 2, synth.SEED_BASE["talos"]))
+    r = subprocess.run([host_build["observe_facade_test"], "--file-source", os.path.join(ROOT, "configs/talos/pos_tracker.yaml"), path],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "refused: 3 of 3" in r.stdout, r.stdout + r.stderr
