@@ -53,7 +53,9 @@ extern "C" {
  *        the device, per-tick results of a roll-out); wbcqp_program, wbcqp_track, wbcqp_segment, wbcqp_check_program, wbcqp_reference_samples,
  *        wbcqp_rollout_program and wbcqp_rollout_mixed_program (the references of a roll-out generated on the device from a reference program);
  *        wbcqp_observables, wbcqp_set_observed_frames, wbcqp_observe and wbcqp_observe_host (centre of mass and world placements / velocities of
- *        chosen model frames from (q, v) on the device); wbcqp_set_model now keeps the model's whole frame table on the host
+ *        chosen model frames from (q, v) on the device); wbcqp_set_model now keeps the model's whole frame table on the host;
+ *        wbcqp_sphere_model, wbcqp_collisions, wbcqp_set_collision_spheres, wbcqp_check_collisions and wbcqp_check_collisions_host (self-collision
+ *        of a robot's sphere model from q on the device)
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -622,6 +624,51 @@ int wbcqp_set_observed_frames(wbcqp_handle* handle, int slot, int n_frames, cons
 int wbcqp_observe(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream);
 /* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done. */
 int wbcqp_observe_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out);
+
+/* ---- Does a robot's sphere model touch itself ----
+ * The reference's CollisionCheck::is_colliding (src/safety/collision_check.cpp:27-87), which its controller runs on the solver's own model after every
+ * solve (controller.cpp:309-312): every link carries a few spheres, the links are grouped into MEMBERS (arm_left, torso, ...), and the robot collides
+ * with itself when two spheres of DIFFERENT members overlap.  One wavefront per instance (collide_kernel, csrc/wbcqp_collide.hpp) on the kinematics of
+ * wbcqp_observe.  To the letter of the reference:
+ *     world centre   R_body centre + p_body, with the true-world placement of the body's joint frame (oMi[frame.parent] there)
+ *     a hit          |c_a - c_b| < (double)(d_a * 0.5f + d_b * 0.5f): the threshold is ONE float addition, the comparison strict and in double
+ *     first_pair     the pair the reference's loops meet first.  It walks members in std::map order (sorted by name) a, then b != a, then i over a's
+ *                    spheres, then j over b's, so the first hit has the smallest (a, b, i, j) with a < b -- NOT the smallest pair of table indices:
+ *                    member b ranks before sphere i.  Sorting the members by name before numbering them is the caller's job.
+ * Per instance, each output optional:
+ *     colliding  1 / 0          first_pair  [2] table indices of that pair, -1 -1 without a hit
+ *     n_pairs    unordered cross-member pairs in collision
+ *     clearance  min over cross-member pairs of distance - threshold (negative: penetration depth of the worst pair); +inf with fewer than two members
+ *     centres    [n_spheres][3] world centres (the reference's spherical_members())
+ * Integer sums and minima and one double minimum, no atomics: the same bits from run to run and at whatever index or batch size a row arrives (F32
+ * handles read q as float, compute in double, write clearance and centres as float).  Like wbcqp_observe the call takes any [rows][nq] array: on a
+ * trace's q array (batch = n_rec * batch) it checks every recorded tick in one launch, and any slot of a mix serves. */
+#define WBCQP_MAX_SPHERES 256
+#define WBCQP_MAX_MEMBERS 16
+typedef struct {
+    int32_t n_spheres;       /* 0 .. WBCQP_MAX_SPHERES; 0 drops the table */
+    const int32_t* body;     /* [n_spheres] body (joint) whose joint frame carries the sphere: oMi[frame.parent] in the reference */
+    const int32_t* member;   /* [n_spheres] 0 .. WBCQP_MAX_MEMBERS-1, NON-DECREASING: spheres sorted by member, file order inside a member */
+    const double* centre;    /* [n_spheres][3] in the body's joint frame */
+    const float* diameter;   /* [n_spheres] -- a DIAMETER, and a float, as the reference reads it */
+} wbcqp_sphere_model;        /* HOST arrays, copied by wbcqp_set_collision_spheres */
+typedef struct {
+    int32_t* colliding;  /* [batch]    1 / 0 */
+    int32_t* first_pair; /* [batch][2] table indices of the pair the reference's loops meet first, -1 -1 without a hit */
+    int32_t* n_pairs;    /* [batch]    unordered cross-member pairs in collision */
+    void* clearance;     /* [batch]    min over cross-member pairs of dist - threshold (handle's dtype); +inf with < 2 members */
+    void* centres;       /* [batch][n_spheres][3] world centres (handle's dtype) */
+} wbcqp_collisions;      /* each may be NULL: not computed */
+/* The slot's sphere table, uploaded once.  The slot needs a model; a later wbcqp_set_structure or wbcqp_set_model on the slot drops the table, as it
+ * drops the model.  WBCQP_ERR_INVALID (and the table before stays) for a slot without a model, n_spheres outside 0 .. WBCQP_MAX_SPHERES, a body outside
+ * the tree, a member outside 0 .. WBCQP_MAX_MEMBERS-1, a decreasing member array, a non-finite centre, a diameter that is non-finite or <= 0. */
+int wbcqp_set_collision_spheres(wbcqp_handle* handle, int slot, const wbcqp_sphere_model* spheres);
+/* q [batch][nq] and the outputs are DEVICE pointers (q, clearance, centres of the handle's dtype); nothing is copied from the host.  Asynchronous on
+ * `stream`, ordered like wbcqp_observe.  Refused with WBCQP_ERR_INVALID before anything is launched: a slot without a model, a slot without a sphere
+ * table, batch < 0.  batch == 0: WBCQP_OK, nothing launched. */
+int wbcqp_check_collisions(wbcqp_handle* handle, int slot, int batch, const void* q, const wbcqp_collisions* out, void* stream);
+/* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done. */
+int wbcqp_check_collisions_host(wbcqp_handle* handle, int slot, int batch, const void* q, const wbcqp_collisions* out);
 
 /* ---- References generated on the device from a reference program ----
  * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the

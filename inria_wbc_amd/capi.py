@@ -31,8 +31,10 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout",
            "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced",
            "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program",
-           "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host")
+           "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host",
+           "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host")
 OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe writes (wbcqp_observables); per instance 3, 3, n_frames x 12, n_frames x 6
+COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
 
@@ -160,6 +162,14 @@ class CObservables(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in OBSERVABLES]
 
 
+class CSphereModel(C.Structure):
+    _fields_ = [("n_spheres", C.c_int32), ("body", c_i32_p), ("member", c_i32_p), ("centre", c_f64_p), ("diameter", C.POINTER(C.c_float))]
+
+
+class CCollisions(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in COLLISIONS]
+
+
 def load_library(path: Optional[str] = None):
     """Loads libwbcqp.so -- after torch, when torch is installed: the library links libamdhip64.so.7, and a process in which it comes FIRST gets
     /opt/rocm's HIP runtime while a later `import torch` brings torch's bundled one.  Two runtimes on one GPU work, but the first one then answers
@@ -217,6 +227,9 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_set_observed_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
     lib.wbcqp_observe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p]
     lib.wbcqp_observe_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables)]
+    lib.wbcqp_set_collision_spheres.argtypes = [C.c_void_p, C.c_int, C.POINTER(CSphereModel)]
+    lib.wbcqp_check_collisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions), C.c_void_p]
+    lib.wbcqp_check_collisions_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions)]
     _lib = lib
     return lib
 
@@ -400,6 +413,7 @@ class Handle:
         self._h = C.c_void_p()
         self._structs: Dict[int, Structure] = {}
         self._observed: Dict[int, int] = {}  # slot -> number of frames selected by set_observed_frames
+        self._spheres: Dict[int, int] = {}  # slot -> number of spheres uploaded by set_collision_spheres
         desc = CDesc(device, dtype, flags)
         rc = self.lib.wbcqp_create(C.byref(desc), C.byref(self._h))
         if rc != WBCQP_OK:
@@ -425,6 +439,7 @@ class Handle:
         self._check(self.lib.wbcqp_set_structure(self._h, slot, C.byref(sb.c)))
         self._structs[slot] = st
         self._observed.pop(slot, None)  # (the library drops the selection with the model)
+        self._spheres.pop(slot, None)
 
     # ---- device-pointer path (torch tensors are only carriers of device memory) ----
     def _pack(self, slot: int, batch: int, inputs, outputs):
@@ -464,6 +479,7 @@ class Handle:
         mb = ModelBuffers(model, tm)
         self._check(self.lib.wbcqp_set_model(self._h, slot, C.byref(mb.model), C.byref(mb.taskmap)))
         self._observed.pop(slot, None)
+        self._spheres.pop(slot, None)
         self._models = getattr(self, "_models", {})
         self._models[slot] = (model, tm)
 
@@ -498,6 +514,38 @@ class Handle:
                 res["velocity"] = np.zeros((B, nf, 6), self.np_dtype)
         out = CObservables(*[res[k].ctypes.data if k in res else None for k in OBSERVABLES])
         self._check(self.lib.wbcqp_observe_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out)))
+        return res
+
+    def set_collision_spheres(self, slot: int, table):
+        """The slot's sphere model (wbcqp_set_collision_spheres): a collision.SphereTable (collision.sphere_table builds one from the reference's
+        collision file), or None / an empty table to drop it."""
+        n = 0 if table is None else int(table.n_spheres)
+        if n == 0:
+            sm = CSphereModel(0, None, None, None, None)
+        else:
+            keep = (np.ascontiguousarray(table.body, dtype=np.int32), np.ascontiguousarray(table.member, dtype=np.int32),
+                    np.ascontiguousarray(table.centre, dtype=np.float64), np.ascontiguousarray(table.diameter, dtype=np.float32))
+            sm = CSphereModel(n, keep[0].ctypes.data_as(c_i32_p), keep[1].ctypes.data_as(c_i32_p), keep[2].ctypes.data_as(c_f64_p),
+                              keep[3].ctypes.data_as(C.POINTER(C.c_float)))
+        self._check(self.lib.wbcqp_set_collision_spheres(self._h, slot, C.byref(sm)))
+        self._spheres[slot] = n
+
+    def check_collisions(self, slot: int, batch: int, q, colliding=None, first_pair=None, n_pairs=None, clearance=None, centres=None, stream: int = 0):
+        """Self-collision of `batch` states on device tensors (wbcqp_check_collisions): q [batch, nq]; outputs, each optional: colliding [batch],
+        first_pair [batch, 2], n_pairs [batch] (int32), clearance [batch], centres [batch, n_spheres, 3] (the handle's dtype)."""
+        out = CCollisions(self._ptr(colliding), self._ptr(first_pair), self._ptr(n_pairs), self._ptr(clearance), self._ptr(centres))
+        self._check(self.lib.wbcqp_check_collisions(self._h, slot, int(batch), self._ptr(q), C.byref(out), C.c_void_p(stream)))
+
+    def check_collisions_host(self, slot: int, q: np.ndarray) -> Dict[str, np.ndarray]:
+        """wbcqp_check_collisions_host: the five outputs as numpy arrays.  Like observe_host, `centres` is sized from what THIS Handle's
+        set_collision_spheres last uploaded on the slot."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B = q.shape[0]
+        ns = self._spheres.get(slot, 0)
+        res = {"colliding": np.zeros(B, np.int32), "first_pair": np.zeros((B, 2), np.int32), "n_pairs": np.zeros(B, np.int32),
+               "clearance": np.zeros(B, self.np_dtype), "centres": np.zeros((B, ns, 3), self.np_dtype)}
+        out = CCollisions(*[res[k].ctypes.data if res[k].size else None for k in COLLISIONS])
+        self._check(self.lib.wbcqp_check_collisions_host(self._h, slot, B, q.ctypes.data, C.byref(out)))
         return res
 
     def problem_data(self, slot: int, batch: int, state: Dict[str, "object"], rows: Dict[str, "object"], stream: int = 0):

@@ -97,6 +97,15 @@ namespace inria_wbc {
             {
                 IWBC_ERROR("this problem source has no model: com_now / model_frame_pos / model_frame_vel need a model-driven source (CONTROLLER.model)");
             }
+            // whether the source holds a kinematic model (what observe() and check_collisions() need)
+            virtual bool has_model() const { return false; }
+            // self-collision of the sphere model in the collision file `file` (the reference's members: {member: {link: [[x, y, z, d], ...]}}) at
+            // the states q: colliding (B: 1 / 0), first_pair (2 B: table indices of the pair the reference's loops meet first, -1 -1 without a hit)
+            // and, per table entry, its (member, place inside the member) -- wbcqp_check_collisions_host.  Only a source that holds a model can tell
+            virtual void check_collisions(const MatrixXd&, const std::string&, VectorXi&, VectorXi&, std::vector<std::pair<std::string, int>>&)
+            {
+                IWBC_ERROR("this problem source has no model: check_model_collisions needs a model-driven source (CONTROLLER.model)");
+            }
         };
 
         class Controller {
@@ -111,6 +120,12 @@ namespace inria_wbc {
                 // controller.cpp:63,72 (the reference requires both keys; here they default to what a model without mimic joints has)
                 fb_joint_name_ = c["floating_base_joint_name"] ? c["floating_base_joint_name"].as<std::string>() : std::string("root_joint");
                 if (c["mimic_dof_names"]) mimic_dof_names_ = c["mimic_dof_names"].as<std::vector<std::string>>();
+                // check collisions in the solver's own model (controller.cpp:89-99; the reference requires the key, here absent means false)
+                check_model_collisions_ = c["check_model_collisions"] ? c["check_model_collisions"].as<bool>() : false;
+                if (check_model_collisions_) {
+                    auto collision_path = IWBC_CHECK(c["collision_path"].as<std::string>());
+                    collision_file_ = collision_path.size() && collision_path[0] == '/' ? collision_path : base_path_ + "/" + collision_path;
+                }
                 t_ = 0.0;
             }
             Controller(const Controller&) = delete;
@@ -172,10 +187,12 @@ namespace inria_wbc {
             // (controller.cpp:262-281): ndofs = nv entries; a floating base is [position(3), angle * axis(3)] in q and six
             // leading zeros in tau.  filter_mimics (default true, as in the reference, controller.cpp:369-397) drops the columns of
             // the joints named in CONTROLLER.mimic_dof_names: slice_vec(x, non_mimic_indexes_) per instance.
-            MatrixXd tau(bool filter_mimics = true) const { return filter_mimics ? filter_cmd(tau_dart_) : tau_dart_; }
-            MatrixXd ddq(bool filter_mimics = true) const { return filter_mimics ? filter_cmd(a_tsid_) : a_tsid_; }
-            MatrixXd dq(bool filter_mimics = true) const { return filter_mimics ? filter_cmd(v_tsid_) : v_tsid_; }
-            MatrixXd q(bool filter_mimics = true) const { return filter_mimics ? filter_cmd(q_solver_) : q_solver_; }
+            // With check_model_collisions these four are the COMMANDS: the rows of an instance whose model has collided stay at the last values
+            // sent, while q_solver() and q_tsid() keep following the solver (controller.cpp:263-282); without it they are the solver's state.
+            MatrixXd tau(bool filter_mimics = true) const { return _cmd(_latched() ? tau_sent_ : tau_dart_, filter_mimics); }
+            MatrixXd ddq(bool filter_mimics = true) const { return _cmd(_latched() ? ddq_sent_ : a_tsid_, filter_mimics); }
+            MatrixXd dq(bool filter_mimics = true) const { return _cmd(_latched() ? dq_sent_ : v_tsid_, filter_mimics); }
+            MatrixXd q(bool filter_mimics = true) const { return _cmd(_latched() ? q_sent_ : q_solver_, filter_mimics); }
             MatrixXd q_solver(bool filter_mimics = true) const { return filter_mimics ? filter_cmd(q_solver_) : q_solver_; }
             // controller.cpp:245: momentum_ = momentumJacobian(data).bottomRows(3) * dq -- the angular momentum about the CoM of the
             // state the last tick was solved at, one row per instance (zero until a tick has run on a model-driven source)
@@ -254,9 +271,36 @@ namespace inria_wbc {
             // B x 6: linear (3), angular (3) velocity of the frame in its own axes (tsid RobotWrapper::frameVelocity)
             MatrixXd model_frame_vel(const std::string& frame) const { return _observed_block(obs_vel_, _ensure_observed(&frame), 6); }
 
+            // The reference's self-collision check of the solver's own model (CONTROLLER.check_model_collisions, collision_path;
+            // controller.hpp:148-150, collision_check.cpp), per instance, for the controller's CURRENT state: computed on the device
+            // (wbcqp_check_collisions_host) and kept with the state like the observables above, so a tick or qp_step_back() refreshes it.
+            // Without check_model_collisions nothing collides.
+            bool check_model_collisions() const { return check_model_collisions_; }
+            const VectorXi& is_model_colliding() const
+            {
+                _ensure_collisions();
+                return col_flags_;
+            }
+            // ((member, i), (member, j)) of the pair the reference's loops meet first; two empty names and -1 for an instance without a hit
+            using CollisionIndex = std::pair<std::pair<std::string, int>, std::pair<std::string, int>>;
+            std::vector<CollisionIndex> collision_index() const
+            {
+                _ensure_collisions();
+                std::vector<CollisionIndex> out(col_flags_.size(), CollisionIndex{{std::string(), -1}, {std::string(), -1}});
+                for (size_t i = 0; i < out.size(); ++i)
+                    if (col_flags_[i]) out[i] = {col_names_[col_pairs_[2 * i]], col_names_[col_pairs_[2 * i + 1]]};
+                return out;
+            }
+            // 1 while an instance's commands are sent, 0 once its model has collided (the reference's send_cmd_); all 1 without the check
+            std::vector<int> send_cmd() const { return send_cmd_.empty() ? std::vector<int>(batch_, 1) : send_cmd_; }
+
             void set_problem_source(const std::shared_ptr<ProblemSource>& src)
             {
                 IWBC_ASSERT(src, "Invalid problem source");
+                if (check_model_collisions_ && !src->has_model())
+                    IWBC_ERROR("check_model_collisions is set, but this problem source has no model: the check needs a model-driven source (CONTROLLER.model)");
+                send_cmd_.clear();
+                col_source_ = nullptr;
                 source_ = src;
                 batch_ = src->batch();
                 _reset();
@@ -380,7 +424,62 @@ namespace inria_wbc {
                         for (int m = 0; m < 12; ++m) f(i, m) = x_[(size_t)i * n + nv + 12 * c + m];
                     activated_contacts_forces_[st.contacts()[c].name] = f;
                 }
+                if (check_model_collisions_) _latch();
             }
+
+            // controller.cpp:263-282,309-312 per instance: the commands follow the solver while send_cmd_ holds; then the new state is checked, and
+            // an instance that collides while its q_ is not all zero (within 1e-3, Eigen's isZero) stops sending from the next tick on
+            void _latch()
+            {
+                const int B = batch_;
+                if ((int)send_cmd_.size() != B) {
+                    send_cmd_.assign(B, 1);
+                    q_sent_ = MatrixXd(B, q_solver_.cols);
+                    dq_sent_ = MatrixXd(B, v_tsid_.cols);
+                    ddq_sent_ = MatrixXd(B, a_tsid_.cols);
+                    tau_sent_ = MatrixXd(B, tau_dart_.cols);
+                }
+                for (int i = 0; i < B; ++i) {
+                    if (!send_cmd_[i]) continue;
+                    std::copy(q_solver_.row(i), q_solver_.row(i) + q_solver_.cols, q_sent_.row(i));
+                    std::copy(v_tsid_.row(i), v_tsid_.row(i) + v_tsid_.cols, dq_sent_.row(i));
+                    std::copy(a_tsid_.row(i), a_tsid_.row(i) + a_tsid_.cols, ddq_sent_.row(i));
+                    std::copy(tau_dart_.row(i), tau_dart_.row(i) + tau_dart_.cols, tau_sent_.row(i));
+                }
+                _ensure_collisions();
+                for (int i = 0; i < B; ++i) {
+                    if (!col_flags_[i]) continue;
+                    bool zero = true;
+                    for (int j = 0; j < q_sent_.cols; ++j) zero = zero && std::fabs(q_sent_(i, j)) <= 1e-3;
+                    if (!zero) send_cmd_[i] = 0;
+                }
+            }
+            MatrixXd _cmd(const MatrixXd& m, bool filter_mimics) const { return filter_mimics ? filter_cmd(m) : m; }
+            bool _latched() const { return check_model_collisions_ && !send_cmd_.empty(); } // (before the first tick: the solver's state, as without the check)
+
+            // the collision answer of the current state, kept with the state and the source it was made for (the pattern of _ensure_observed)
+            void _ensure_collisions() const
+            {
+                auto self = const_cast<Controller*>(this);
+                if (!check_model_collisions_) {
+                    self->col_flags_.assign(batch_, 0);
+                    return;
+                }
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (col_source_ == source_.get() && col_q_.rows == q_tsid_.rows && col_q_.data == q_tsid_.data) return;
+                self->col_source_ = nullptr;
+                self->source_->check_collisions(q_tsid_, collision_file_, self->col_flags_, self->col_pairs_, self->col_names_);
+                self->col_q_ = q_tsid_;
+                self->col_source_ = source_.get();
+            }
+            bool check_model_collisions_ = false;
+            std::string collision_file_;
+            std::vector<int> send_cmd_; // per instance; empty until the first tick with the check on
+            MatrixXd q_sent_, dq_sent_, ddq_sent_, tau_sent_;
+            VectorXi col_flags_, col_pairs_;
+            std::vector<std::pair<std::string, int>> col_names_;
+            MatrixXd col_q_;                             // the state the answer above was computed at
+            const ProblemSource* col_source_ = nullptr; // ... and by which source (null: nothing kept)
 
             bool verbose_ = false;
             double t_ = 0.0, dt_ = 0.001;

@@ -44,6 +44,7 @@ namespace inria_wbc {
             }
             int batch() const override { return batch_; }
             bool handles_references() const override { return true; }
+            bool has_model() const override { return true; }
 
             void bind(wbcqp_handle* h, int slot, const tasks::TaskStack& stack, double dt) override
             {
@@ -182,6 +183,7 @@ namespace inria_wbc {
                 tm.dt = dt;
                 tm.nref = nref_;
                 if (wbcqp_set_model(h, slot, &md, &tm) != WBCQP_OK) IWBC_ERROR("wbcqp_set_model failed: ", wbcqp_last_error(h));
+                spheres_.erase(slot); // (the library drops the sphere table with the model)
                 auto c0 = robot_->com(q0_.data());
                 com_pos_ = MatrixXd(batch_, 3);
                 com_vel_ = MatrixXd(batch_, 3);
@@ -195,6 +197,66 @@ namespace inria_wbc {
                 if (cur_ && bounds_.count(slot) && cur_ == &bounds_[slot]) cur_ = nullptr;
                 bounds_.erase(slot);
                 observed_.erase(slot); // (the library drops the selection with the model)
+                spheres_.erase(slot);
+            }
+
+            // wbcqp_check_collisions_host on the slot in use.  The table is built from the collision file when the slot has none for that file:
+            // members sorted by name (the reference's std::map), links in file order, numbers read as float; a link is looked up in the model's
+            // frames (the sphere rides on the frame's parent joint), a name X_link the frames do not hold is the link joint X_joint moves, and a
+            // name that resolves to nothing is skipped, as the reference's loop over model.frames skips it (collision_check.cpp:58-87)
+            void check_collisions(const MatrixXd& q, const std::string& file, VectorXi& colliding, VectorXi& first_pair,
+                                  std::vector<std::pair<std::string, int>>& names) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq(), "one state row per instance");
+                auto known = spheres_.find(slot_);
+                if (known == spheres_.end() || known->second.first != file) {
+                    yaml::Node members = IWBC_CHECK(yaml::LoadFile(file)["members"]);
+                    std::vector<std::string> order;
+                    for (const auto& m : members) order.push_back(m.first);
+                    std::sort(order.begin(), order.end());
+                    IWBC_ASSERT((int)order.size() <= WBCQP_MAX_MEMBERS, "collisions yaml : at most ", WBCQP_MAX_MEMBERS, " members");
+                    const wbcqp_model md = robot_->c_model();
+                    const auto& joints = robot_->joint_names();
+                    std::vector<int32_t> body, member;
+                    std::vector<double> centre;
+                    std::vector<float> diameter;
+                    std::vector<std::pair<std::string, int>> table;
+                    for (size_t k = 0; k < order.size(); ++k) {
+                        int place = 0;
+                        for (const auto& link : members[order[k]]) {
+                            int b = -1;
+                            if (robot_->existFrame(link.first))
+                                b = md.frame_body[robot_->getFrameId(link.first)];
+                            else if (link.first.size() > 5 && link.first.compare(link.first.size() - 5, 5, "_link") == 0) {
+                                auto it = std::find(joints.begin(), joints.end(), link.first.substr(0, link.first.size() - 5) + "_joint");
+                                if (it != joints.end()) b = (int)std::distance(joints.begin(), it);
+                            }
+                            if (b < 0) continue;
+                            for (const auto& sphere : link.second.as<std::vector<std::vector<float>>>()) {
+                                if (sphere.size() != 4) IWBC_ERROR("collisions yaml : sphere data should be an float array of dim 4");
+                                body.push_back(b);
+                                member.push_back((int32_t)k);
+                                for (int d = 0; d < 3; ++d) centre.push_back((double)sphere[d]);
+                                diameter.push_back(sphere[3]);
+                                table.emplace_back(order[k], place++);
+                            }
+                        }
+                    }
+                    IWBC_ASSERT(!body.empty() && (int)body.size() <= WBCQP_MAX_SPHERES, "collisions yaml : ", body.size(), " spheres on this model, 1 .. ",
+                                WBCQP_MAX_SPHERES, " are possible");
+                    wbcqp_sphere_model sm = {(int32_t)body.size(), body.data(), member.data(), centre.data(), diameter.data()};
+                    if (wbcqp_set_collision_spheres(handle_, slot_, &sm) != WBCQP_OK)
+                        IWBC_ERROR("wbcqp_set_collision_spheres failed: ", wbcqp_last_error(handle_));
+                    spheres_[slot_] = std::make_pair(file, table);
+                    known = spheres_.find(slot_);
+                }
+                names = known->second.second;
+                colliding.assign(batch_, 0);
+                first_pair.assign((size_t)2 * batch_, -1);
+                wbcqp_collisions out = {colliding.data(), first_pair.data(), nullptr, nullptr, nullptr};
+                if (wbcqp_check_collisions_host(handle_, slot_, batch_, q.data.data(), &out) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_check_collisions_host failed: ", wbcqp_last_error(handle_));
             }
 
             // wbcqp_observe_host on the slot in use; the selection of frames goes to the device when it changes, not per call
@@ -342,6 +404,8 @@ namespace inria_wbc {
             wbcqp_handle* handle_ = nullptr;
             std::map<int, Bound> bounds_;
             std::map<int, std::vector<std::string>> observed_; // slot -> the frames selected on it (wbcqp_set_observed_frames)
+            // slot -> the collision file whose table it holds (wbcqp_set_collision_spheres) and every table entry's (member, place in the member)
+            std::map<int, std::pair<std::string, std::vector<std::pair<std::string, int>>>> spheres_;
             Bound* cur_ = nullptr;
             std::map<std::string, std::vector<double>> named_;
             MatrixXd com_pos_, com_vel_;

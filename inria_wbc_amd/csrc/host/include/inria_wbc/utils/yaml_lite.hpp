@@ -1,5 +1,6 @@
 // Minimal reader for the YAML subset inria_wbc's configuration files use (nested block maps, scalars, flow
-// sequences like [0, 0, -0.2] or [[0, 0, -0.2]], '#' comments).  yaml-cpp is not available in this build, so the
+// sequences like [0, 0, -0.2] or [[0, 0, -0.2]], '#' comments).  yaml-cpp is not available in this build.
+// A flow sequence may continue over several lines (etc/talos/collisions/talos_collisions.yaml): lines are joined while brackets are open.  The
 // facade keeps the reference's key names (CONTROLLER / BEHAVIOR trees, tasks.yaml entries) and reads them with this.
 // Node mimics the part of YAML::Node the reference touches: operator[], as<T>(), explicit bool, ordered map
 // iteration (pos_tracker.cpp:161-189 relies on file order), in-memory patching (test_all_robots.cpp:160-164).
@@ -217,9 +218,25 @@ namespace inria_wbc {
             std::vector<Line> lines;
             std::istringstream is(text);
             std::string raw;
+            int open = 0; // bracket depth of the last line's flow value: above zero, the value continues on the next line
+            auto brackets = [](const std::string& t) { // (brackets inside quotes are text)
+                int d = 0;
+                bool in_s = false, in_d = false;
+                for (char ch : t) {
+                    if (ch == '\'' && !in_d) in_s = !in_s;
+                    if (ch == '"' && !in_s) in_d = !in_d;
+                    if (!in_s && !in_d) d += (ch == '[') - (ch == ']');
+                }
+                return d;
+            };
             while (std::getline(is, raw)) {
                 std::string s = strip_comment(raw);
                 if (trim(s).empty()) continue;
+                if (open > 0) {
+                    lines.back().value += " " + trim(s);
+                    open += brackets(s);
+                    continue;
+                }
                 int indent = 0;
                 while (indent < (int)s.size() && s[indent] == ' ') ++indent;
                 std::string body = trim(s);
@@ -240,7 +257,9 @@ namespace inria_wbc {
                 l.value = trim(body.substr(colon + 1));
                 l.has_value = !l.value.empty();
                 lines.push_back(l);
+                open = (!l.value.empty() && l.value[0] == '[') ? brackets(l.value) : 0; // only a value that IS a flow sequence can continue
             }
+            if (open > 0) throw std::runtime_error("yaml: unterminated flow sequence: " + lines.back().value);
             Node root;
             root.d_->kind = Node::Map;
             std::vector<std::pair<int, Node>> stack; // (indent of the keys in this map, map node)

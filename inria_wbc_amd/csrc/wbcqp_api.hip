@@ -658,6 +658,104 @@ int wbcqp_observe_host(wbcqp_handle* h, int slot, int batch, const void* q, cons
     return stage_down(h, dout, dn, 4, 0, Xfer::blocking);
 }
 
+int wbcqp_set_collision_spheres(wbcqp_handle* h, int slot, const wbcqp_sphere_model* sm)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (!sm) return fail(h, WBCQP_ERR_INVALID, "sphere model is NULL");
+    const int n = sm->n_spheres;
+    if (n < 0 || n > WBCQP_MAX_SPHERES) return fail(h, WBCQP_ERR_INVALID, "n_spheres must be in [0, 256]");
+    if (n > 0 && (!sm->body || !sm->member || !sm->centre || !sm->diameter)) return fail(h, WBCQP_ERR_INVALID, "body / member / centre / diameter is NULL");
+    // one allocation: centre [n][3] doubles, then body, tag (member << 8 | place inside the member) and half-diameter, 4 bytes each
+    std::vector<double> store(((size_t)n * (24 + 12) + 7) / 8); // (doubles: the block's alignment is the centres')
+    char* blob = reinterpret_cast<char*>(store.data());
+    const size_t blob_bytes = (size_t)n * (24 + 12);
+    double* centre = store.data();
+    int* body = reinterpret_cast<int*>(blob + (size_t)24 * n);
+    int* tag = body + n;
+    float* half = reinterpret_cast<float*>(tag + n);
+    for (int i = 0, place = 0; i < n; ++i) {
+        if (sm->body[i] < 0 || sm->body[i] >= s->terms.nb) return fail(h, WBCQP_ERR_INVALID, "a sphere's body is outside the slot's tree");
+        if (sm->member[i] < 0 || sm->member[i] >= WBCQP_MAX_MEMBERS) return fail(h, WBCQP_ERR_INVALID, "a sphere's member must be in [0, 16)");
+        if (i > 0 && sm->member[i] < sm->member[i - 1]) return fail(h, WBCQP_ERR_INVALID, "member must be non-decreasing (spheres sorted by member)");
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(sm->centre[3 * i + k])) return fail(h, WBCQP_ERR_INVALID, "a sphere's centre is not finite");
+        if (!std::isfinite(sm->diameter[i]) || !(sm->diameter[i] > 0.0f)) return fail(h, WBCQP_ERR_INVALID, "a sphere's diameter must be finite and > 0");
+        place = (i > 0 && sm->member[i] == sm->member[i - 1]) ? place + 1 : 0;
+        body[i] = sm->body[i];
+        tag[i] = (sm->member[i] << 8) | place;
+        half[i] = sm->diameter[i] / 2; // a float division, as the reference's sphere.second / 2
+        std::copy(sm->centre + 3 * i, sm->centre + 3 * i + 3, centre + 3 * i);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    void* fresh = nullptr; // the new table is complete on the device before the one before goes
+    if (n > 0) {
+        HIP_TRY(h, hipMalloc(&fresh, blob_bytes));
+        if (hipMemcpy(fresh, blob, blob_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(h, WBCQP_ERR_HIP, "copying the sphere table to the device failed");
+        }
+    }
+    release_spheres(*s); // (hipFree waits for whatever still reads the previous table)
+    if (n == 0) return WBCQP_OK;
+    s->spheres_alloc = fresh;
+    char* d = static_cast<char*>(s->spheres_alloc);
+    const int* dbody = reinterpret_cast<const int*>(d + (size_t)24 * n);
+    s->spheres = CollideDev{n, dbody, dbody + n, reinterpret_cast<const double*>(d), reinterpret_cast<const float*>(dbody + 2 * n)};
+    return WBCQP_OK;
+}
+
+int wbcqp_check_collisions(wbcqp_handle* h, int slot, int batch, const void* q, const wbcqp_collisions* out, void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (s->spheres.n_spheres == 0) return fail(h, WBCQP_ERR_INVALID, "slot has no sphere table (wbcqp_set_collision_spheres)");
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "collisions struct is NULL");
+    if (batch == 0 || (!out->colliding && !out->first_pair && !out->n_pairs && !out->clearance && !out->centres)) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const TermsDev& T = s->terms;
+    const ObserveDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_idxq, T.i_idxv, T.i_anc, T.d_place, T.d_inertia, 0, nullptr, nullptr};
+    const int blocks = (batch + kObservePerBlock - 1) / kObservePerBlock;
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const CollideArgs<TI> a{D, s->spheres, static_cast<const TI*>(q), out->colliding, out->first_pair, out->n_pairs, static_cast<TI*>(out->clearance),
+                                static_cast<TI*>(out->centres), batch};
+        hipLaunchKernelGGL(collide_kernel<TI>, dim3(blocks), dim3(kObserveThreads), collide_lds_bytes(s->spheres.n_spheres), static_cast<hipStream_t>(stream), a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+int wbcqp_check_collisions_host(wbcqp_handle* h, int slot, int batch, const void* q, const wbcqp_collisions* out)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (s->spheres.n_spheres == 0) return fail(h, WBCQP_ERR_INVALID, "slot has no sphere table (wbcqp_set_collision_spheres)");
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "collisions struct is NULL");
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, ns = (size_t)s->spheres.n_spheres;
+    Arr up[1] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}};
+    Arr dn[5] = {{-1, out->colliding, B * 4, 0}, {-1, out->first_pair, B * 8, 0}, {-1, out->n_pairs, B * 4, 0}, {-1, out->clearance, B * es, 0},
+                 {-1, out->centres, B * ns * 3 * es, 0}};
+    WB_TRY(stage_begin(h, lay(up, 1), lay(dn, 5), false));
+    WB_TRY(stage_up(h, h->stage_in.dev, up, 1, 0, Xfer::blocking));
+    char* din = static_cast<char*>(h->stage_in.dev);
+    char* dout = static_cast<char*>(h->stage_out.dev);
+    const wbcqp_collisions d = {out->colliding ? reinterpret_cast<int32_t*>(dout + dn[0].off) : nullptr,
+                                out->first_pair ? reinterpret_cast<int32_t*>(dout + dn[1].off) : nullptr,
+                                out->n_pairs ? reinterpret_cast<int32_t*>(dout + dn[2].off) : nullptr, out->clearance ? dout + dn[3].off : nullptr,
+                                out->centres ? dout + dn[4].off : nullptr};
+    WB_TRY(wbcqp_check_collisions(h, slot, batch, q ? din + up[0].off : nullptr, &d, nullptr));
+    HIP_TRY(h, hipDeviceSynchronize());
+    return stage_down(h, dout, dn, 5, 0, Xfer::blocking);
+}
+
 int wbcqp_problem_data(wbcqp_handle* h, int slot, int batch, const wbcqp_state* st, const wbcqp_inputs* rows, void* stream)
 {
     if (!h) return WBCQP_ERR_INVALID;

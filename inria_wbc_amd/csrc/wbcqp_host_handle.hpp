@@ -8,6 +8,7 @@
 #include "wbcqp_small.hpp"
 #include "wbcqp_costs.hpp"
 #include "wbcqp_observe.hpp"
+#include "wbcqp_collide.hpp"
 
 #include "../../include/wbcqp.h"
 
@@ -53,6 +54,9 @@ struct Slot {
     int n_obs = 0;
     int* obs_body = nullptr;
     double* obs_place = nullptr;
+    // wbcqp_check_collisions: the sphere table of wbcqp_set_collision_spheres, one device allocation; dropped with the model
+    CollideDev spheres{};
+    void* spheres_alloc = nullptr;
 };
 
 struct Staging {
@@ -308,6 +312,13 @@ void release_observed(Slot& s)
     s.n_obs = 0;
 }
 
+void release_spheres(Slot& s)
+{
+    if (s.spheres_alloc) (void)hipFree(s.spheres_alloc);
+    s.spheres_alloc = nullptr;
+    s.spheres = CollideDev{};
+}
+
 void release_model(Slot& s)
 {
     for (void* p : s.model_allocs) (void)hipFree(p);
@@ -317,6 +328,7 @@ void release_model(Slot& s)
     s.frame_body_h.clear();
     s.frame_place_h.clear();
     release_observed(s);
+    release_spheres(s);
 }
 
 void release(Slot& s)

@@ -105,6 +105,20 @@ __device__ __forceinline__ ValIdx wave_argmin(ValIdx a)
     const int r2 = __builtin_amdgcn_readlane(i, 32), r3 = __builtin_amdgcn_readlane(i, 48);
     return ValIdx{m, min(min(r0, r1), min(r2, r3))};
 }
+// all-lanes minimum within one wave (the value pass of wave_argmin)
+__device__ __forceinline__ double wave_min(double v)
+{
+    WBCQP_ROW_REDUCE(v, op_min)
+    return fmin(fmin(bcast_lane(v, 0), bcast_lane(v, 16)), fmin(bcast_lane(v, 32), bcast_lane(v, 48)));
+}
+__device__ __forceinline__ int wave_sum_int(int v)
+{
+    v += dpp_movi<0xB1>(v);
+    v += dpp_movi<0x4E>(v);
+    v += dpp_movi<0x141>(v);
+    v += dpp_movi<0x140>(v);
+    return (__builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16)) + (__builtin_amdgcn_readlane(v, 32) + __builtin_amdgcn_readlane(v, 48));
+}
 __device__ __forceinline__ int wave_max_int(int v)
 {
     v = max(v, dpp_movi<0xB1>(v));
