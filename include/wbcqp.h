@@ -55,7 +55,8 @@ extern "C" {
  *        wbcqp_observables, wbcqp_set_observed_frames, wbcqp_observe and wbcqp_observe_host (centre of mass and world placements / velocities of
  *        chosen model frames from (q, v) on the device); wbcqp_set_model now keeps the model's whole frame table on the host;
  *        wbcqp_sphere_model, wbcqp_collisions, wbcqp_set_collision_spheres, wbcqp_check_collisions and wbcqp_check_collisions_host (self-collision
- *        of a robot's sphere model from q on the device)
+ *        of a robot's sphere model from q on the device); wbcqp_set_wrench_frames, wbcqp_inverse_dynamics and wbcqp_inverse_dynamics_host (the joint
+ *        torques of a motion under external wrenches at model frames, on the device)
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -669,6 +670,39 @@ int wbcqp_set_collision_spheres(wbcqp_handle* handle, int slot, const wbcqp_sphe
 int wbcqp_check_collisions(wbcqp_handle* handle, int slot, int batch, const void* q, const wbcqp_collisions* out, void* stream);
 /* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done. */
 int wbcqp_check_collisions_host(wbcqp_handle* handle, int slot, int batch, const void* q, const wbcqp_collisions* out);
+
+/* ---- Which joint torques a motion needs, under wrenches at frames ----
+ * The reference's inria_wbc::utils::RobotModel (src/utils/robot_model.cpp): update() followed by pinocchio::rnea, nonLinearEffects,
+ * computeGeneralizedGravity, and compute_rnea_double_support (:138-229), the model-side torque that measured joint torques are compared with.
+ * One wavefront per instance (rnea_kernel, csrc/wbcqp_rnea.hpp): a recursive Newton-Euler pass in the rows kernel's frame, world-aligned with its origin
+ * at the floating base -- the base's translation q[0..2] is never read, so the result does not lose digits far from the world's origin.
+ *     tau [batch][nv] = M(q) a + nle(q, v) - sum_k J_k(q)' w_k      (all nv rows: a floating base's six come first, in pinocchio's convention)
+ *       q [batch][nq]; v [batch][nv] or NULL (zero); a: row i at a + i * lda, nv entries, or NULL (zero); lda >= nv
+ *       wrench [batch][n_frames][6] or NULL (none): linear (3), angular (3) in the frame's OWN axes -- pinocchio::Force against the LOCAL frame
+ *       Jacobian J_k of the k-th selected frame (wbcqp_set_wrench_frames)
+ * v == NULL and a == NULL: generalized gravity; a == NULL alone: nonLinearEffects.  lda exists so that the x of a tick or of a trace (rows ldx long, dv
+ * first) is passed as `a` without a copy.  No atomics, every sum in a fixed order, and an instance's result depends on its own rows alone: the same bits
+ * from run to run and at whatever index or batch size the rows arrive (F32 handles read float, compute in double, write float).  Two frames on one body
+ * are subtracted in the order of the selection.
+ * Like wbcqp_observe the call takes any arrays of rows: with batch = n_rec * batch on a trace's arrays one call covers every recorded tick.  Mind that
+ * wbcqp_trace.q and .v are the state AFTER the recorded tick while .x (and .tau) belong to the state BEFORE it: auditing a trace pairs entry r's x
+ * with entry r - 1's q, v (entry 0's with the roll-out's initial state).  For a solved tick, inverse dynamics of (q, v, dv = x[..nv], w_c = T_c f_c at the
+ * contact frames, T_c the structure's force generator) is zero on a floating base's six rows and the decoded tau on the actuated rows, up to the
+ * solver's equality residual. */
+#define WBCQP_MAX_WRENCH_FRAMES 8
+/* Where the wrenches of wbcqp_inverse_dynamics act: indices into wbcqp_model's frame tables (frames: HOST [n_frames], 0 .. 8, repeats allowed), uploaded
+ * once.  The slot needs a model; a later wbcqp_set_structure or wbcqp_set_model on the slot drops the selection, as it drops the observed frames.
+ * WBCQP_ERR_INVALID (and the selection before stays) for a slot without a model, n_frames outside 0 .. WBCQP_MAX_WRENCH_FRAMES, a frame index outside
+ * the model. */
+int wbcqp_set_wrench_frames(wbcqp_handle* handle, int slot, int n_frames, const int32_t* frames);
+/* DEVICE pointers of the handle's dtype, asynchronous on `stream`, ordered like wbcqp_observe; nothing is copied from the host.  Refused with
+ * WBCQP_ERR_INVALID before anything is launched: a slot without a model, batch < 0, q or tau NULL, lda < nv with a given, wrench given while no frames
+ * are selected.  batch == 0: WBCQP_OK, nothing launched. */
+int wbcqp_inverse_dynamics(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
+                           void* tau, void* stream);
+/* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done.  `a` is read up to its last row's nv-th entry. */
+int wbcqp_inverse_dynamics_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
+                                void* tau);
 
 /* ---- References generated on the device from a reference program ----
  * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the

@@ -32,7 +32,8 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced",
            "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program",
            "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host",
-           "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host")
+           "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host",
+           "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host")
 OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe writes (wbcqp_observables); per instance 3, 3, n_frames x 12, n_frames x 6
 COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
@@ -230,6 +231,9 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_set_collision_spheres.argtypes = [C.c_void_p, C.c_int, C.POINTER(CSphereModel)]
     lib.wbcqp_check_collisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions), C.c_void_p]
     lib.wbcqp_check_collisions_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions)]
+    lib.wbcqp_set_wrench_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
+    lib.wbcqp_inverse_dynamics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wbcqp_inverse_dynamics_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
 
@@ -414,6 +418,7 @@ class Handle:
         self._structs: Dict[int, Structure] = {}
         self._observed: Dict[int, int] = {}  # slot -> number of frames selected by set_observed_frames
         self._spheres: Dict[int, int] = {}  # slot -> number of spheres uploaded by set_collision_spheres
+        self._wrench_frames: Dict[int, int] = {}  # slot -> number of frames selected by set_wrench_frames
         desc = CDesc(device, dtype, flags)
         rc = self.lib.wbcqp_create(C.byref(desc), C.byref(self._h))
         if rc != WBCQP_OK:
@@ -440,6 +445,7 @@ class Handle:
         self._structs[slot] = st
         self._observed.pop(slot, None)  # (the library drops the selection with the model)
         self._spheres.pop(slot, None)
+        self._wrench_frames.pop(slot, None)
 
     # ---- device-pointer path (torch tensors are only carriers of device memory) ----
     def _pack(self, slot: int, batch: int, inputs, outputs):
@@ -480,6 +486,7 @@ class Handle:
         self._check(self.lib.wbcqp_set_model(self._h, slot, C.byref(mb.model), C.byref(mb.taskmap)))
         self._observed.pop(slot, None)
         self._spheres.pop(slot, None)
+        self._wrench_frames.pop(slot, None)
         self._models = getattr(self, "_models", {})
         self._models[slot] = (model, tm)
 
@@ -515,6 +522,36 @@ class Handle:
         out = CObservables(*[res[k].ctypes.data if k in res else None for k in OBSERVABLES])
         self._check(self.lib.wbcqp_observe_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out)))
         return res
+
+    def set_wrench_frames(self, slot: int, frames: Sequence[int]):
+        """Where the wrenches of inverse_dynamics act: indices into the model's frame table (observe.frame_ids turns names into them), repeats
+        allowed, at most 8 (wbcqp_set_wrench_frames)."""
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        self._check(self.lib.wbcqp_set_wrench_frames(self._h, slot, int(fr.size), fr.ctypes.data_as(c_i32_p)))
+        self._wrench_frames[slot] = int(fr.size)
+
+    def inverse_dynamics(self, slot: int, batch: int, q, tau, v=None, a=None, lda: int = 0, wrench=None, stream: int = 0):
+        """tau = M(q) a + nle(q, v) - sum_k J_k' w_k of `batch` states on device tensors (wbcqp_inverse_dynamics): q [batch, nq], tau [batch, nv];
+        v [batch, nv] or None (zero); a or None (zero): row i starts lda elements after row i - 1 (lda = 0: a.shape[-1]), so a tick's x serves;
+        wrench [batch, n_frames, 6] or None: linear, angular in the own axes of the frames of set_wrench_frames."""
+        if a is not None and lda == 0:
+            lda = int(a.shape[-1])
+        ptr = lambda t: t.data_ptr() if t is not None else None  # (an empty tensor stays a given one: the library says what is wrong with it)
+        self._check(self.lib.wbcqp_inverse_dynamics(self._h, slot, int(batch), ptr(q), ptr(v), ptr(a), int(lda), ptr(wrench), ptr(tau),
+                                                    C.c_void_p(stream)))
+
+    def inverse_dynamics_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, a: Optional[np.ndarray] = None,
+                              wrench: Optional[np.ndarray] = None) -> np.ndarray:
+        """wbcqp_inverse_dynamics_host: tau [B, nv].  a [B, lda] with lda >= nv: its first nv columns are the accelerations (a tick's x as it is)."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B = q.shape[0]
+        nv = self._models[slot][0].nv
+        v, a, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, a, wrench))
+        tau = np.zeros((B, nv), self.np_dtype)
+        dat = lambda t: t.ctypes.data if t is not None else None
+        self._check(self.lib.wbcqp_inverse_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(a), int(a.shape[-1]) if a is not None else 0,
+                                                         dat(wrench), tau.ctypes.data))
+        return tau
 
     def set_collision_spheres(self, slot: int, table):
         """The slot's sphere model (wbcqp_set_collision_spheres): a collision.SphereTable (collision.sphere_table builds one from the reference's

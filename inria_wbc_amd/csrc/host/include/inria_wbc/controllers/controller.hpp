@@ -97,6 +97,19 @@ namespace inria_wbc {
             {
                 IWBC_ERROR("this problem source has no model: com_now / model_frame_pos / model_frame_vel need a model-driven source (CONTROLLER.model)");
             }
+            // tau (B x nv) = M(q) a + nle(q, v) - sum_k J_k' w_k for the n named model frames, wrenches B x 6 n (linear, angular in each frame's own
+            // axes; n <= 8) -- wbcqp_inverse_dynamics_host.  Only a source that holds a model can tell
+            virtual void inverse_dynamics(const MatrixXd&, const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, const MatrixXd&, MatrixXd&)
+            {
+                IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
+            }
+            // the foot's own mass added to a measured wrench (robot_model.cpp:171-186 of the reference), per instance, at the states q: force -= m g
+            // with m the mass of the body that carries ft_frame, torque += (ankle - sole) x force with the world positions of that body's joint
+            // frame and of sole_frame.  Only a source that holds a model can tell
+            virtual void add_foot_mass(const MatrixXd&, const std::string&, const std::string&, MatrixXd&, MatrixXd&) const
+            {
+                IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
+            }
             // whether the source holds a kinematic model (what observe() and check_collisions() need)
             virtual bool has_model() const { return false; }
             // self-collision of the sphere model in the collision file `file` (the reference's members: {member: {link: [[x, y, z, d], ...]}}) at
@@ -270,6 +283,48 @@ namespace inria_wbc {
             MatrixXd model_frame_pos(const std::string& frame) const { return _observed_block(obs_place_, _ensure_observed(&frame), 12); }
             // B x 6: linear (3), angular (3) velocity of the frame in its own axes (tsid RobotWrapper::frameVelocity)
             MatrixXd model_frame_vel(const std::string& frame) const { return _observed_block(obs_vel_, _ensure_observed(&frame), 6); }
+
+            // The model-side torques of the current motion under measured foot wrenches, B x nv (a floating base's six rows first): the reference's
+            // RobotModel::compute_rnea_double_support (robot_model.cpp:138-229), per instance, for the controller's current q_tsid(), dq(false) and
+            // the last tick's ddq -- rnea(q, v, a) - J_left' w_left - J_right' w_right with the LOCAL Jacobians of the two frames, computed on the
+            // device (wbcqp_inverse_dynamics_host).  sensor_data holds lf_force, rf_force, lf_torque, rf_torque: B x 3 each, or three numbers
+            // for every instance alike.  add_foot_mass: the wrench is first corrected by the foot's own weight and applied at the sole frame.
+            MatrixXd rnea_double_support(const SensorData& sensor_data, bool add_foot_mass, const std::string& left_ft_frame, const std::string& right_ft_frame,
+                                         const std::string& left_sole_frame, const std::string& right_sole_frame) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (!source_->has_model())
+                    IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
+                if ((sensor_data.find("lf_force") == sensor_data.end()) || (sensor_data.find("rf_force") == sensor_data.end()) ||
+                    (sensor_data.find("lf_torque") == sensor_data.end()) || (sensor_data.find("rf_torque") == sensor_data.end()))
+                    throw IWBC_EXCEPTION("when FT is missing in fext_map"); // robot_model.cpp:161-163
+                const int B = batch_, nv = v_tsid_.cols;
+                auto per_instance = [&](const std::string& key) {
+                    const MatrixXd& m = sensor_data.at(key);
+                    IWBC_ASSERT((m.rows == B && m.cols == 3) || m.data.size() == 3, key, " holds three numbers, or B x 3");
+                    MatrixXd o(B, 3);
+                    for (int i = 0; i < B; ++i)
+                        for (int d = 0; d < 3; ++d) o(i, d) = m.data.size() == 3 ? m.data[d] : m(i, d);
+                    return o;
+                };
+                MatrixXd force[2] = {per_instance("lf_force"), per_instance("rf_force")}, torque[2] = {per_instance("lf_torque"), per_instance("rf_torque")};
+                std::vector<std::string> frames = {left_ft_frame, right_ft_frame};
+                if (add_foot_mass) {
+                    source_->add_foot_mass(q_tsid_, left_ft_frame, left_sole_frame, force[0], torque[0]);
+                    source_->add_foot_mass(q_tsid_, right_ft_frame, right_sole_frame, force[1], torque[1]);
+                    frames = {left_sole_frame, right_sole_frame};
+                }
+                MatrixXd w(B, 12), a(B, nv), tau;
+                for (int i = 0; i < B; ++i)
+                    for (int k = 0; k < 2; ++k)
+                        for (int d = 0; d < 3; ++d) {
+                            w(i, 6 * k + d) = force[k](i, d);
+                            w(i, 6 * k + 3 + d) = torque[k](i, d);
+                        }
+                if (a_tsid_.rows == B && a_tsid_.cols == nv) a = a_tsid_; // (before the first tick: no acceleration yet)
+                source_->inverse_dynamics(q_tsid_, v_tsid_, a, frames, w, tau);
+                return tau;
+            }
 
             // The reference's self-collision check of the solver's own model (CONTROLLER.check_model_collisions, collision_path;
             // controller.hpp:148-150, collision_check.cpp), per instance, for the controller's CURRENT state: computed on the device

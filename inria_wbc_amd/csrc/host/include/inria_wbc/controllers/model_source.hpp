@@ -184,6 +184,7 @@ namespace inria_wbc {
                 tm.nref = nref_;
                 if (wbcqp_set_model(h, slot, &md, &tm) != WBCQP_OK) IWBC_ERROR("wbcqp_set_model failed: ", wbcqp_last_error(h));
                 spheres_.erase(slot); // (the library drops the sphere table with the model)
+                wrench_frames_.erase(slot);
                 auto c0 = robot_->com(q0_.data());
                 com_pos_ = MatrixXd(batch_, 3);
                 com_vel_ = MatrixXd(batch_, 3);
@@ -198,6 +199,7 @@ namespace inria_wbc {
                 bounds_.erase(slot);
                 observed_.erase(slot); // (the library drops the selection with the model)
                 spheres_.erase(slot);
+                wrench_frames_.erase(slot);
             }
 
             // wbcqp_check_collisions_host on the slot in use.  The table is built from the collision file when the slot has none for that file:
@@ -282,6 +284,48 @@ namespace inria_wbc {
                 wbcqp_observables out = {com.data.data(), vcom.data.data(), n ? place.data.data() : nullptr, n ? vel.data.data() : nullptr};
                 if (wbcqp_observe_host(handle_, slot_, batch_, q.data.data(), v.data.data(), &out) != WBCQP_OK)
                     IWBC_ERROR("wbcqp_observe_host failed: ", wbcqp_last_error(handle_));
+            }
+
+            // wbcqp_inverse_dynamics_host on the slot in use; the selection of frames goes to the device when it changes, not per call
+            void inverse_dynamics(const MatrixXd& q, const MatrixXd& v, const MatrixXd& a, const std::vector<std::string>& frames, const MatrixXd& wrenches,
+                                  MatrixXd& tau) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                const int n = (int)frames.size(), nv = robot_->nv();
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq() && v.rows == batch_ && v.cols == nv && a.rows == batch_ && a.cols >= nv,
+                            "one state row per instance");
+                IWBC_ASSERT(n <= WBCQP_MAX_WRENCH_FRAMES, "at most ", WBCQP_MAX_WRENCH_FRAMES, " wrench frames");
+                IWBC_ASSERT(n == 0 || (wrenches.rows == batch_ && wrenches.cols == 6 * n), "six numbers per frame and instance");
+                auto known = wrench_frames_.find(slot_);
+                if (known == wrench_frames_.end() || known->second != frames) {
+                    std::vector<int32_t> ids;
+                    for (const auto& f : frames) ids.push_back(robot_->getFrameId(f));
+                    if (wbcqp_set_wrench_frames(handle_, slot_, n, ids.data()) != WBCQP_OK)
+                        IWBC_ERROR("wbcqp_set_wrench_frames failed: ", wbcqp_last_error(handle_));
+                    wrench_frames_[slot_] = frames;
+                }
+                tau = MatrixXd(batch_, nv);
+                if (wbcqp_inverse_dynamics_host(handle_, slot_, batch_, q.data.data(), v.data.data(), a.data.data(), a.cols, n ? wrenches.data.data() : nullptr,
+                                                tau.data.data()) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_inverse_dynamics_host failed: ", wbcqp_last_error(handle_));
+            }
+            void add_foot_mass(const MatrixXd& q, const std::string& ft_frame, const std::string& sole_frame, MatrixXd& force, MatrixXd& torque) const override
+            {
+                if (!robot_->existFrame(ft_frame)) IWBC_ERROR("Frame name ", ft_frame, "is not in model"); // robot_model.cpp:173-176
+                if (!robot_->existFrame(sole_frame)) IWBC_ERROR("Frame name ", sole_frame, "is not in model");
+                const int ft = robot_->getFrameId(ft_frame), sole = robot_->getFrameId(sole_frame);
+                const wbcqp_model md = robot_->c_model();
+                const int body = md.frame_body[ft];
+                const float mass_to_add = (float)md.inertia[10 * body]; // (a float there too)
+                for (int i = 0; i < batch_; ++i) {
+                    const auto ankle = robot_->bodyPlacements(q.row(i))[body].p;
+                    const auto s = robot_->framePosition(q.row(i), sole).p;
+                    for (int d = 0; d < 3; ++d) force(i, d) -= mass_to_add * md.gravity[d];
+                    const double r[3] = {ankle[0] - s[0], ankle[1] - s[1], ankle[2] - s[2]};
+                    torque(i, 0) += r[1] * force(i, 2) - r[2] * force(i, 1);
+                    torque(i, 1) += r[2] * force(i, 0) - r[0] * force(i, 2);
+                    torque(i, 2) += r[0] * force(i, 1) - r[1] * force(i, 0);
+                }
             }
 
             void compute(double, const MatrixXd& q, const MatrixXd& v, const tasks::TaskStack& stack, const wbcqp_layout& L, TickInputs& in) override
@@ -404,6 +448,7 @@ namespace inria_wbc {
             wbcqp_handle* handle_ = nullptr;
             std::map<int, Bound> bounds_;
             std::map<int, std::vector<std::string>> observed_; // slot -> the frames selected on it (wbcqp_set_observed_frames)
+            std::map<int, std::vector<std::string>> wrench_frames_; // ... and the frames its wrenches act at (wbcqp_set_wrench_frames)
             // slot -> the collision file whose table it holds (wbcqp_set_collision_spheres) and every table entry's (member, place in the member)
             std::map<int, std::pair<std::string, std::vector<std::pair<std::string, int>>>> spheres_;
             Bound* cur_ = nullptr;

@@ -13,6 +13,7 @@
 #include "wbcqp_host_launch.hpp"
 #include "wbcqp_host_program.hpp"
 #include "wbcqp_host_rollout.hpp"
+#include "wbcqp_host_dynamics.hpp"
 
 namespace {
 
@@ -754,6 +755,74 @@ int wbcqp_check_collisions_host(wbcqp_handle* h, int slot, int batch, const void
     WB_TRY(wbcqp_check_collisions(h, slot, batch, q ? din + up[0].off : nullptr, &d, nullptr));
     HIP_TRY(h, hipDeviceSynchronize());
     return stage_down(h, dout, dn, 5, 0, Xfer::blocking);
+}
+
+int wbcqp_set_wrench_frames(wbcqp_handle* h, int slot, int n_frames, const int32_t* frames)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (n_frames < 0 || n_frames > WBCQP_MAX_WRENCH_FRAMES) return fail(h, WBCQP_ERR_INVALID, "n_frames must be in [0, 8]");
+    if (n_frames > 0 && !frames) return fail(h, WBCQP_ERR_INVALID, "frames is NULL");
+    static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
+    const int nframe = (int)s->frame_body_h.size();
+    // one allocation: placement [n][12] doubles, then body [n]
+    std::vector<double> store((size_t)12 * n_frames + ((size_t)n_frames + 1) / 2);
+    int* body = reinterpret_cast<int*>(store.data() + (size_t)12 * n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        if (frames[f] < 0 || frames[f] >= nframe) return fail(h, WBCQP_ERR_INVALID, "a wrench frame does not exist in the slot's model");
+        body[f] = s->frame_body_h[frames[f]];
+        std::copy(s->frame_place_h.begin() + (size_t)12 * frames[f], s->frame_place_h.begin() + (size_t)12 * frames[f] + 12, store.begin() + (size_t)12 * f);
+    }
+    HIP_TRY(h, hipSetDevice(h->device));
+    void* fresh = nullptr; // the new selection is complete on the device before the one before goes
+    if (n_frames > 0) {
+        HIP_TRY(h, hipMalloc(&fresh, store.size() * sizeof(double)));
+        if (hipMemcpy(fresh, store.data(), store.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(fresh);
+            return fail(h, WBCQP_ERR_HIP, "copying the wrench frames to the device failed");
+        }
+    }
+    release_wrench_frames(*s); // (hipFree waits for whatever still reads the previous selection)
+    if (n_frames == 0) return WBCQP_OK;
+    s->wrench_alloc = fresh;
+    s->wrench_place = static_cast<const double*>(fresh);
+    s->wrench_body = reinterpret_cast<const int*>(s->wrench_place + (size_t)12 * n_frames);
+    s->n_wrench = n_frames;
+    return WBCQP_OK;
+}
+
+int wbcqp_inverse_dynamics(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench, void* tau,
+                           void* stream)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* s = nullptr;
+    WB_TRY(check_inverse_dynamics(h, slot, batch, q, a, lda, wrench, tau, &s));
+    if (batch == 0) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_inverse_dynamics(h, *s, batch, q, v, a, lda, wrench, tau, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_inverse_dynamics_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench, void* tau)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* s = nullptr;
+    WB_TRY(check_inverse_dynamics(h, slot, batch, q, a, lda, wrench, tau, &s));
+    if (batch == 0) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv;
+    // (a: rows lda apart, the last one nv long -- nothing behind it is the caller's to give)
+    Arr up[4] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * nv * es, 0},
+                 {-1, const_cast<void*>(a), ((B - 1) * (size_t)(a ? lda : 0) + nv) * es, 0}, {-1, const_cast<void*>(wrench), B * s->n_wrench * 6 * es, 0}};
+    Arr dn[1] = {{-1, tau, B * nv * es, 0}};
+    WB_TRY(stage_begin(h, lay(up, 4), lay(dn, 1), false));
+    WB_TRY(stage_up(h, h->stage_in.dev, up, 4, 0, Xfer::blocking));
+    char* din = static_cast<char*>(h->stage_in.dev);
+    char* dout = static_cast<char*>(h->stage_out.dev);
+    WB_TRY(launch_inverse_dynamics(h, *s, batch, din + up[0].off, v ? din + up[1].off : nullptr, a ? din + up[2].off : nullptr, lda,
+                                   wrench ? din + up[3].off : nullptr, dout + dn[0].off, nullptr));
+    HIP_TRY(h, hipDeviceSynchronize());
+    return stage_down(h, dout, dn, 1, 0, Xfer::blocking);
 }
 
 int wbcqp_problem_data(wbcqp_handle* h, int slot, int batch, const wbcqp_state* st, const wbcqp_inputs* rows, void* stream)

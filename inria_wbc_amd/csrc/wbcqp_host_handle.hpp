@@ -9,6 +9,7 @@
 #include "wbcqp_costs.hpp"
 #include "wbcqp_observe.hpp"
 #include "wbcqp_collide.hpp"
+#include "wbcqp_rnea.hpp"
 
 #include "../../include/wbcqp.h"
 
@@ -57,6 +58,11 @@ struct Slot {
     // wbcqp_check_collisions: the sphere table of wbcqp_set_collision_spheres, one device allocation; dropped with the model
     CollideDev spheres{};
     void* spheres_alloc = nullptr;
+    // wbcqp_inverse_dynamics: the frames chosen by wbcqp_set_wrench_frames (body and placement of each), one device allocation; dropped with the model
+    int n_wrench = 0;
+    const int* wrench_body = nullptr;
+    const double* wrench_place = nullptr;
+    void* wrench_alloc = nullptr;
 };
 
 struct Staging {
@@ -319,6 +325,15 @@ void release_spheres(Slot& s)
     s.spheres = CollideDev{};
 }
 
+void release_wrench_frames(Slot& s)
+{
+    if (s.wrench_alloc) (void)hipFree(s.wrench_alloc);
+    s.wrench_alloc = nullptr;
+    s.wrench_body = nullptr;
+    s.wrench_place = nullptr;
+    s.n_wrench = 0;
+}
+
 void release_model(Slot& s)
 {
     for (void* p : s.model_allocs) (void)hipFree(p);
@@ -329,6 +344,7 @@ void release_model(Slot& s)
     s.frame_place_h.clear();
     release_observed(s);
     release_spheres(s);
+    release_wrench_frames(s);
 }
 
 void release(Slot& s)

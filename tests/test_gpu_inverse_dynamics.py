@@ -1,0 +1,425 @@
+"""Inverse dynamics on the device (wbcqp_inverse_dynamics, csrc/wbcqp_rnea.hpp): tau = M(q) a + nle(q, v) - sum_k J_k' w_k against
+oracle/rbd_oracle.c (rnea, and the LOCAL frame Jacobians of rbd_terms) through the C ABI.
+
+Bar: TOL_ROWS of tests/test_gpu_terms.py (two formulations in double: one common frame and prefix sums on the device, pinocchio-style local
+recursions in the oracle), relative to max(1, the array's largest entry); 1e-6 for an F32 handle, as that file has it.  The shapes are the
+ones at which the kernel can go wrong: one body, the lane limit (64 bodies on a fixed base; a floating base at ITS limit, 59 bodies = nv 64 --
+wbcqp_set_structure refuses nv > 64), a pure chain (every doubling round), a star (every subtree one lane), batches that are no multiple of
+the four instances of a workgroup.
+
+The audit identity (a solved tick's inverse dynamics is zero on the base rows and the decoded tau on the actuated rows) is held to AUDIT_TOL
+of tests/test_inverse_dynamics_host.py: ten times the worst residual measured there with the oracle's own tick (7.65e-11 over 64 states)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from inria_wbc_amd import capi, refprog, structure
+from inria_wbc_amd import model as mdl
+from tests.test_inverse_dynamics_host import AUDIT_TOL, audit_residual, contact_wrenches, talos_audit_case
+
+pytestmark = pytest.mark.gpu
+
+TOL_ROWS = 1e-10
+TOL_F32 = 1e-6
+BATCHES = (1, 3, 5, 67)
+NMAX = max(BATCHES)
+GUARD = 16  # elements behind the output buffer that must stay untouched
+PAD = 13    # lda = nv + PAD in the padded mode
+
+
+def _torch():
+    import torch
+    return torch, torch.device("cuda", 0)
+
+
+def _minimal(m):
+    """The smallest stack a slot accepts for `m`: one SE(3) task on frame 0 (inverse dynamics needs the tree, not the tasks)."""
+    st = structure._mk("rnea_" + m.name, m.nv, m.na, [], [("a", 3, 1.0)], None, [], False, False, [])
+    return st, mdl.build_taskmap(m, st, [dict(name="a", type="se3", tracked=m.frame_names[0], kp=10.0, mask="111000")])
+
+
+def _tree(seed, nb, fb, shape=None):
+    def f():
+        m = mdl.random_tree(seed, nb, fb, nframe=12)
+        if shape == "chain":  # depth nb - 1: every doubling round moves something
+            m.parent = np.arange(-1, nb - 1, dtype=np.int32)
+        if shape == "star":   # every body but the root is a leaf: every subtree but the root's is one lane
+            m.parent = np.array([-1] + [0] * (nb - 1), dtype=np.int32)
+        m.frame_body[0], m.frame_body[1] = 0, nb - 1  # a frame on body 0, a frame on the last body
+        m.frame_body[3] = m.frame_body[2]             # two frames on one body
+        m.validate()
+        return (m,) + _minimal(m)
+    return f
+
+
+CASES = {"one_body_fixed": _tree(61, 1, False), "tree_64_fixed_lane_limit": _tree(62, 64, False), "tree_59_floating_nv_limit": _tree(63, 59, True),
+         "chain_62": _tree(64, 62, False, "chain"), "star_17_floating": _tree(65, 17, True, "star"), "tree_24_floating": _tree(66, 24, True)}
+
+
+def _talos():
+    m = mdl.talos_like()
+    st = structure.talos_structure()
+    return m, st, mdl.build_taskmap(m, st, mdl.talos_stack())
+
+
+def _states(m, tm, n, seed):
+    s = mdl.sample_states(m, tm, n, seed, q_noise=0.3, v_noise=0.5)  # the noise tests/test_gpu_terms.py uses for trees
+    a = 2.0 * np.random.default_rng(seed + 1).standard_normal((n, m.nv))
+    return s["q"], s["v"], a
+
+
+def _selections(m):
+    """none, one frame, all eight slots with repeats, two frames on one body, a frame on body 0 and one on the last body."""
+    eight = np.random.default_rng(7).integers(0, m.nframe, 8)
+    eight[5] = eight[2]
+    return {"none": [], "one": [m.nframe // 2], "eight_with_repeats": eight.tolist(), "two_on_one_body": [2, 3], "first_and_last_body": [0, 1]}
+
+
+class Oracle:
+    """rnea for the four (v, a) modes and the local Jacobians of every frame, once per case; any selection of frames is formed from them."""
+
+    def __init__(self, m, q, v, a):
+        from oracle import rbd
+        om = rbd.OracleModel(m)
+        z = np.zeros(m.nv)
+        n = q.shape[0]
+        self.base = {"full": np.stack([rbd.rnea(om, q[i], v[i], a[i]) for i in range(n)]),
+                     "a_null": np.stack([rbd.rnea(om, q[i], v[i], z) for i in range(n)]),
+                     "v_a_null": np.stack([rbd.rnea(om, q[i], z, z) for i in range(n)]),
+                     "v_null": np.stack([rbd.rnea(om, q[i], z, a[i]) for i in range(n)])}
+        self.base["lda_padded"] = self.base["full"]
+        self.Jl = np.stack([rbd.rbd_terms(om, q[i], v[i])["Jl"] for i in range(n)])  # [n, nframe, 6, nv]
+
+    def tau(self, mode, frames, wrench):
+        out = self.base[mode].copy()
+        for k, f in enumerate(frames):
+            out -= np.einsum("bij,bi->bj", self.Jl[:, f], wrench[:, k])
+        return out
+
+
+MODES = ("full", "a_null", "v_a_null", "v_null", "lda_padded")
+
+
+def _run(h, slot, B, nv, q, v, a, wrench, mode, torch, dev, td=None):
+    """One launch on device tensors -> tau [B, nv] as numpy; every element is written, nothing behind the end is touched.  a: [N, nv + PAD]
+    with NaN in the padding; the modes pass it whole (lda = nv + PAD), as a contiguous copy of its first nv columns (lda = nv), or not at all."""
+    td = td or torch.float64
+    whole = torch.full((B * nv + GUARD,), float("nan"), dtype=td, device=dev)
+    vv = None if mode in ("v_a_null", "v_null") else v[:B].contiguous()
+    if mode in ("a_null", "v_a_null"):
+        aa, lda = None, 0
+    elif mode == "lda_padded":
+        aa, lda = a[:B], nv + PAD
+    else:
+        aa, lda = a[:B, :nv].contiguous(), nv
+    h.inverse_dynamics(slot, B, q[:B].contiguous(), whole[:B * nv], v=vv, a=aa, lda=lda, wrench=None if wrench is None else wrench[:B].contiguous(),
+                       stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    out = whole.cpu().numpy()
+    assert np.isnan(out[B * nv:]).all(), "written past the end"
+    assert np.isfinite(out[:B * nv]).all(), "an element was not written"
+    return out[:B * nv].reshape(B, nv)
+
+
+def _rel(got, want):
+    return float(np.abs(got - want).max() / max(1.0, np.abs(want).max()))
+
+
+def _padded(a, torch, dev, td=None):
+    n, nv = a.shape
+    wide = np.full((n, nv + PAD), np.nan)
+    wide[:, :nv] = a
+    t = torch.from_numpy(wide).to(dev)
+    return t if td is None else t.to(td)
+
+
+@pytest.fixture(scope="module")
+def handle():
+    h = capi.Handle(0, capi.F64)
+    yield h
+    h.close()
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_inverse_dynamics_parity(handle, name):
+    torch, dev = _torch()
+    m, st, tm = CASES[name]()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    qn, vn, an = _states(m, tm, NMAX, 81_000)
+    ora = Oracle(m, qn, vn, an)
+    q, v, a = torch.from_numpy(qn).to(dev), torch.from_numpy(vn).to(dev), _padded(an, torch, dev)
+    worst = {}
+    for sel, frames in _selections(m).items():
+        handle.set_wrench_frames(3, frames)
+        wn = 50.0 * np.random.default_rng(82_000 + len(frames)).standard_normal((NMAX, len(frames), 6))
+        w = torch.from_numpy(wn).to(dev) if frames else None
+        for mode in MODES:
+            want = ora.tau(mode, frames, wn)
+            big = None
+            for B in BATCHES[::-1]:
+                got = _run(handle, 3, B, m.nv, q, v, a, w, mode, torch, dev)
+                e = _rel(got, want[:B])
+                worst[mode] = max(worst.get(mode, 0.0), e)
+                assert e <= TOL_ROWS, (name, sel, mode, B, e)
+                if big is None:
+                    big = got
+                assert np.array_equal(got, big[:B]), (name, sel, mode, B, "the same rows in a smaller batch: other bits")
+            if mode == "lda_padded":  # the padding is never read: the bits of lda = nv
+                assert np.array_equal(big, _run(handle, 3, NMAX, m.nv, q, v, a, w, "full", torch, dev)), (name, sel)
+    print("inverse dynamics parity, worst per mode, %-26s %s (|tau| up to %.3g)" % (name, "  ".join("%s %.1e" % kv for kv in worst.items()),
+                                                                                   np.abs(ora.base["full"]).max()))
+
+
+def test_far_from_the_origin_costs_no_digits(handle):
+    """A base at |p| = 1e3 (where tests/test_gpu_terms.py loosens its bar to 1e-7): the translation is never read, so the result has the bits of
+    the same state at the origin."""
+    torch, dev = _torch()
+    m, st, tm = _talos()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    frames = [m.frame("leg_left_6_joint"), m.frame("leg_right_6_joint")]
+    handle.set_wrench_frames(3, frames)
+    qn, vn, an = _states(m, tm, 5, 83_000)
+    wn = 300.0 * np.random.default_rng(83_500).standard_normal((5, 2, 6))
+    far = qn.copy()
+    far[:, :3] += np.array([600.0, -700.0, 400.0])
+    v, a, w = torch.from_numpy(vn).to(dev), _padded(an, torch, dev), torch.from_numpy(wn).to(dev)
+    near = _run(handle, 3, 5, m.nv, torch.from_numpy(qn).to(dev), v, a, w, "full", torch, dev)
+    assert np.array_equal(near, _run(handle, 3, 5, m.nv, torch.from_numpy(far).to(dev), v, a, w, "full", torch, dev))
+    assert _rel(near, Oracle(m, far, vn, an).tau("full", frames, wn)) <= TOL_ROWS
+    host = handle.inverse_dynamics_host(3, qn, vn, an, wn)  # the host-pointer entry point: the same kernel, the same bits
+    assert np.array_equal(host, near)
+    wide = np.concatenate([an, np.full((5, PAD), np.nan)], axis=1)
+    assert np.array_equal(handle.inverse_dynamics_host(3, qn, vn, wide, wn), near)
+
+
+def test_same_bits_on_two_launches_and_at_any_place_in_a_batch(handle):
+    torch, dev = _torch()
+    m, st, tm = CASES["tree_24_floating"]()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    frames = _selections(m)["eight_with_repeats"]
+    handle.set_wrench_frames(3, frames)
+    qn, vn, an = _states(m, tm, NMAX, 84_000)
+    wn = 50.0 * np.random.default_rng(84_500).standard_normal((NMAX, 8, 6))
+    q, v, a, w = torch.from_numpy(qn).to(dev), torch.from_numpy(vn).to(dev), _padded(an, torch, dev), torch.from_numpy(wn).to(dev)
+    x = _run(handle, 3, NMAX, m.nv, q, v, a, w, "full", torch, dev)
+    y = _run(handle, 3, NMAX, m.nv, q, v, a, w, "full", torch, dev)
+    z = _run(handle, 3, 6, m.nv, q[10:16], v[10:16], a[10:16], w[10:16], "full", torch, dev)  # rows 10 .. 15 as a batch of their own: other waves, other workgroups
+    assert np.array_equal(x, y) and np.array_equal(x[10:16], z)
+
+
+def test_f32_handle_rounds_the_f64_result(handle):
+    torch, dev = _torch()
+    m, st, tm = _talos()
+    frames = [m.frame("leg_left_6_joint"), m.frame("gripper_right_joint"), m.frame("leg_left_6_joint")]
+    qn, vn, an = _states(m, tm, 9, 85_000)
+    wn = 50.0 * np.random.default_rng(85_500).standard_normal((9, 3, 6))
+    q32, v32, a32, w32 = (t.astype(np.float32) for t in (qn, vn, an, wn))
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    handle.set_wrench_frames(3, frames)
+    want = handle.inverse_dynamics_host(3, *(t.astype(np.float64) for t in (q32, v32, a32, w32)))
+    h32 = capi.Handle(0, capi.F32)
+    try:
+        h32.set_structure(0, st)
+        h32.set_model(0, m, tm)
+        h32.set_wrench_frames(0, frames)
+        up = lambda t: torch.from_numpy(t).to(dev)  # noqa: E731
+        got = _run(h32, 0, 9, m.nv, up(q32), up(v32), _padded(a32.astype(np.float64), torch, dev, torch.float32), up(w32), "lda_padded", torch, dev,
+                   td=torch.float32)
+        host = h32.inverse_dynamics_host(0, q32, v32, a32, w32)
+    finally:
+        h32.close()
+    assert got.dtype == np.float32 and np.array_equal(got, host)
+    assert np.array_equal(got, want.astype(np.float32))  # float in, double inside, float out: the F64 result, rounded
+    ora = Oracle(m, q32.astype(np.float64), v32.astype(np.float64), a32.astype(np.float64)).tau("full", frames, w32.astype(np.float64))
+    assert _rel(got.astype(np.float64), ora) <= TOL_F32
+
+
+def test_nothing_else_moves(handle):
+    m, st, tm = _talos()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    B = 6
+    s = mdl.sample_states(m, tm, B, 86_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
+    tlb, tub, w = np.tile(-m.tau_max, (B, 1)), np.tile(m.tau_max, (B, 1)), np.tile(st.default_weights, (B, 1))
+    handle.set_observed_frames(3, [1, 4, 9])
+    rows0 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
+    tick0 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
+    obs0 = handle.observe_host(3, s["q"], s["v"])
+    handle.set_wrench_frames(3, list(range(8)))
+    handle.inverse_dynamics_host(3, s["q"], s["v"], tick0["x"], np.ones((B, 8, 6)))
+    rows1 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
+    tick1 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
+    obs1 = handle.observe_host(3, s["q"], s["v"])
+    for before, after in ((rows0, rows1), (tick0, tick1), (obs0, obs1)):
+        for k in before:
+            assert np.array_equal(before[k], after[k]), k
+    assert (tick0["status"] == 0).all()
+
+
+def test_refusals_come_before_any_launch():
+    torch, dev = _torch()
+    m, st, tm = _talos()
+    h = capi.Handle(0, capi.F64)
+    try:
+        B, nv = 4, m.nv
+        qn, vn, an = _states(m, tm, B, 87_000)
+        wn = np.ones((B, 2, 6))
+        q, v, a, w = (torch.from_numpy(t).to(dev) for t in (qn, vn, an, wn))
+        tau = torch.full((B * nv + GUARD,), float("nan"), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream().cuda_stream
+
+        def refused(call):
+            with pytest.raises(capi.WbcqpError) as e:
+                call()
+            assert e.value.code == 1, e.value  # WBCQP_ERR_INVALID
+            assert (h.lib.wbcqp_last_error(h._h) or b"").decode().strip(), "no message in wbcqp_last_error"
+
+        def raw_set(slot, n, arr):
+            h._check(h.lib.wbcqp_set_wrench_frames(h._h, slot, n, arr.ctypes.data_as(capi.c_i32_p) if arr is not None else None))
+
+        def raw(slot, batch, qp, vp, ap, lda, wp, tp):
+            h._check(h.lib.wbcqp_inverse_dynamics(h._h, slot, batch, qp, vp, ap, lda, wp, tp, C.c_void_p(stream)))
+
+        P = lambda t: t.data_ptr()  # noqa: E731
+        # a slot without a model: no structure at all, then a structure alone
+        refused(lambda: h.set_wrench_frames(9, [0]))
+        refused(lambda: raw(9, B, P(q), P(v), P(a), nv, None, P(tau)))
+        h.set_structure(0, st)
+        refused(lambda: h.set_wrench_frames(0, [0]))
+        refused(lambda: raw(0, B, P(q), P(v), P(a), nv, None, P(tau)))
+        h.set_model(0, m, tm)
+        # a wrench while no frames are selected (never selected, and an empty selection)
+        refused(lambda: raw(0, B, P(q), P(v), P(a), nv, P(w), P(tau)))
+        h.set_wrench_frames(0, [])
+        refused(lambda: raw(0, B, P(q), P(v), P(a), nv, P(w), P(tau)))
+        # frame indices outside the model, n_frames outside 0 .. 8
+        refused(lambda: h.set_wrench_frames(0, [0, m.nframe]))
+        refused(lambda: h.set_wrench_frames(0, [-1]))
+        refused(lambda: raw_set(0, 9, np.zeros(9, np.int32)))
+        refused(lambda: raw_set(0, -1, np.zeros(1, np.int32)))
+        h.set_wrench_frames(0, [3, 5])
+        refused(lambda: h.set_wrench_frames(0, [0, m.nframe]))  # (a refused selection leaves the one before in place: checked below)
+        # batch < 0, q or tau NULL, lda < nv with a given
+        refused(lambda: raw(0, -1, P(q), P(v), P(a), nv, P(w), P(tau)))
+        refused(lambda: raw(0, B, None, P(v), P(a), nv, P(w), P(tau)))
+        refused(lambda: raw(0, B, P(q), P(v), P(a), nv, P(w), None))
+        refused(lambda: raw(0, B, P(q), P(v), P(a), nv - 1, P(w), P(tau)))
+        refused(lambda: h.inverse_dynamics_host(0, qn, vn, an[:, :nv - 1], wn))
+        raw(0, 0, P(q), P(v), P(a), nv, P(w), P(tau))  # batch == 0: WBCQP_OK, nothing launched
+        raw(0, 0, P(q), None, None, 0, None, P(tau))
+        torch.cuda.synchronize()
+        assert torch.isnan(tau).all().item(), "a refused call wrote something"
+        raw(0, B, P(q), P(v), None, 0, P(w), P(tau))  # lda is not looked at without a; and the selection [3, 5] still stands
+        torch.cuda.synchronize()
+        got = tau.cpu().numpy()
+        assert np.isnan(got[B * nv:]).all()
+        assert _rel(got[:B * nv].reshape(B, nv), Oracle(m, qn, vn, an).tau("a_null", [3, 5], wn)) <= TOL_ROWS
+    finally:
+        h.close()
+
+
+def test_set_structure_and_set_model_drop_the_selection():
+    torch, dev = _torch()
+    m, st, tm = CASES["tree_24_floating"]()
+    h = capi.Handle(0, capi.F64)
+    try:
+        qn, vn, an = _states(m, tm, 3, 88_000)
+        wn = np.ones((3, 2, 6))
+        h.set_structure(0, st)
+        h.set_model(0, m, tm)
+        h.set_wrench_frames(0, [1, 2])
+        with_w = h.inverse_dynamics_host(0, qn, vn, an, wn)
+        for again in ("structure", "model"):
+            if again == "structure":
+                h.set_structure(0, st)
+            h.set_model(0, m, tm)
+            buf = torch.full((3 * m.nv,), float("nan"), dtype=torch.float64, device=dev)
+            with pytest.raises(capi.WbcqpError) as e:
+                h.inverse_dynamics(0, 3, torch.from_numpy(qn).to(dev), buf, wrench=torch.from_numpy(wn).to(dev))
+            assert e.value.code == 1 and "no frames" in str(e.value)
+            torch.cuda.synchronize()
+            assert torch.isnan(buf).all().item()
+            assert not np.array_equal(h.inverse_dynamics_host(0, qn, vn, an), with_w)  # without wrenches no selection is needed
+            h.set_wrench_frames(0, [1, 2])
+            assert np.array_equal(h.inverse_dynamics_host(0, qn, vn, an, wn), with_w)
+    finally:
+        h.close()
+
+
+def test_audit_identity_through_a_tick(handle):
+    """wbcqp_tick_host on 16 Talos instances, then inverse dynamics with a = x (lda = n) and the QP's own contact wrenches: zero on the base rows,
+    the decoded tau on the actuated rows, at the bar measured with the oracle's tick (tests/test_inverse_dynamics_host.py)."""
+    B = 16
+    m, st, tm, s, lim = talos_audit_case(B, 89_000)
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    tick = handle.tick_host(3, s["q"], s["v"], s["ref"], lim["tlb"], lim["tub"], lim["w"], tm.dt)
+    ok = tick["status"] == 0
+    assert ok.all()
+    handle.set_wrench_frames(3, tm.contact_frame)
+    assert tick["x"].shape[1] == st.n > st.nv
+    tau_id = handle.inverse_dynamics_host(3, s["q"], s["v"], tick["x"], contact_wrenches(st, tick["x"]))
+    res = audit_residual(st, tau_id, tick["tau"][:, :st.na])
+    print("audit identity through wbcqp_tick_host, %d instances: worst residual %.3e (bar %.2e)" % (B, res.max(), AUDIT_TOL))
+    assert res.max() <= AUDIT_TOL
+
+
+def test_audit_of_a_traced_squat():
+    """A traced squat (batch 8, 12 ticks, stride 1): one call over n_rec * batch rows is tick-by-tick calls bit for bit, and entry r's x goes
+    with entry r - 1's state (entry 0's with the initial state): paired so, the audit identity holds on every recorded tick."""
+    torch, dev = _torch()
+    B, K = 8, 12
+    m, st, tm = _talos()
+    s = mdl.sample_states(m, tm, B, 97_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
+    com = next(b for b in tm.blocks if b.kind == mdl.T_COM)
+    prog = refprog.move_com_program(tm.nref, com.ref, m.com(m.q0), [[0.0, 0.0, -0.2]], "001", tm.dt, 2.0, loop=True, absolute=False)
+    up = lambda t: torch.from_numpy(np.ascontiguousarray(t)).to(dev)  # noqa: E731
+    lim = dict(w=up(np.tile(st.default_weights, (B, 1))), tlb=up(np.tile(-m.tau_max, (B, 1))), tub=up(np.tile(m.tau_max, (B, 1))))
+    q0, v0 = up(s["q"]), up(s["v"])
+    h = capi.Handle(0, capi.F64)
+    try:
+        h.set_structure(0, st)
+        h.set_model(0, m, tm)
+        h.set_wrench_frames(0, tm.contact_frame)
+        stream = torch.cuda.current_stream().cuda_stream
+        ref = h.reference_samples(prog, up(s["ref"]), -37 * np.arange(B), 0, K, torch.zeros(K, B, tm.nref, dtype=torch.float64, device=dev), stream=stream)
+        f = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)  # noqa: E731
+        out = dict(x=f(B, st.n), tau=f(B, st.na), status=torch.full((B,), -99, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev))
+        trace = dict(q=f(K, B, m.nq), v=f(K, B, m.nv), x=f(K, B, st.n), tau=f(K, B, st.na), status=torch.full((K, B), -99, dtype=torch.int32, device=dev))
+        h.rollout_traced(0, B, K, dict(q=q0, v=v0, ref=ref), lim, out, f(B, m.nq), f(B, m.nv), tm.dt, trace=trace, stride=1, stream=stream)
+        torch.cuda.synchronize()
+        assert (trace["status"] == 0).all().item()
+        # entry r's x belongs to the state BEFORE tick r: entry r - 1's q, v
+        qb = torch.cat([q0[None], trace["q"][:-1]]).contiguous()
+        vb = torch.cat([v0[None], trace["v"][:-1]]).contiguous()
+        T = up(np.asarray(st.force_gen()).reshape(st.nc, 6, 12))
+        w = torch.einsum("cij,rbcj->rbci", T, trace["x"][..., st.nv:].reshape(K, B, st.nc, 12)).contiguous()
+        whole = _run_lda(h, 0, K * B, m.nv, qb.reshape(K * B, -1), vb.reshape(K * B, -1), trace["x"].reshape(K * B, -1), st.n, w.reshape(K * B, st.nc, 6), torch, dev)
+        for r in range(K):
+            tick = _run_lda(h, 0, B, m.nv, qb[r], vb[r], trace["x"][r], st.n, w[r], torch, dev)
+            assert np.array_equal(whole[r * B:(r + 1) * B], tick), r
+        res = audit_residual(st, whole, trace["tau"].reshape(K * B, -1).cpu().numpy())
+        print("audit identity over a traced squat (12 x 8 ticks): worst residual %.3e (bar %.2e)" % (res.max(), AUDIT_TOL))
+        assert res.max() <= AUDIT_TOL
+        # paired with the state AFTER the tick (the trace's own entry) the identity does not hold: the pairing matters
+        wrong = _run_lda(h, 0, K * B, m.nv, trace["q"].reshape(K * B, -1), trace["v"].reshape(K * B, -1), trace["x"].reshape(K * B, -1), st.n,
+                         w.reshape(K * B, st.nc, 6), torch, dev)
+        assert audit_residual(st, wrong, trace["tau"].reshape(K * B, -1).cpu().numpy()).max() > 1e3 * AUDIT_TOL
+    finally:
+        h.close()
+
+
+def _run_lda(h, slot, B, nv, q, v, x, ldx, w, torch, dev):
+    """tau [B, nv] with a tick's x [B, ldx] passed as `a`, lda = ldx: NaN-prefilled, guarded."""
+    whole = torch.full((B * nv + GUARD,), float("nan"), dtype=torch.float64, device=dev)
+    h.inverse_dynamics(slot, B, q.contiguous(), whole[:B * nv], v=v.contiguous(), a=x.contiguous(), lda=ldx, wrench=w.contiguous(),
+                       stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    out = whole.cpu().numpy()
+    assert np.isnan(out[B * nv:]).all() and np.isfinite(out[:B * nv]).all()
+    return out[:B * nv].reshape(B, nv)
