@@ -184,9 +184,18 @@ __device__ __forceinline__ V3 log3(const double* R)
                 (R[3] > R[1] ? 1.0 : -1.0) * (t2 > 0.0 ? sqrt(t2) : 0.0)};
     }
     // theta / (2 sin theta): 2 sin(theta) is the length of the antisymmetric part itself (one square root where sin() is ~150
-    // instructions; the two agree to rounding on (1.2e-4, pi - 1e-2))
+    // instructions).  theta from acos() carries the rounding of the trace divided by sin(theta): an absolute error of eps / theta, which
+    // the oracle's theta / sin(theta) cancels (both ends of its quotient move together) and a quotient by the exactly known |w| does
+    // not -- 1e-11 at theta = 1.3e-4, times Kp.  So below theta = 1e-2 the quotient comes from s = |w| / 2 = sin(theta) alone:
+    // asin(s) / s = 1 + s^2/6 + 3 s^4/40 + 15 s^6/336 + 105 s^8/3456 (next term 2e-22 there), no angle at all; above it the error of
+    // acos() is under 1e-14 relative.  (tests/test_gpu_task_laws.py holds both to the exact logarithm.)
     const V3 w = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-    const double t = (theta > 1.220703125e-4) ? theta / sqrt(dot(w, w)) : 0.5;
+    const double ww = dot(w, w), s2 = 0.25 * ww;
+    double t;
+    if (!(theta > 1.220703125e-4)) t = 0.5;
+    else if (s2 < 1e-4 && tr > 1.0)
+        t = fma(s2, fma(s2, fma(s2, fma(s2, 105.0 / 3456.0, 15.0 / 336.0), 3.0 / 40.0), 1.0 / 6.0), 1.0) * 0.5;
+    else t = theta / sqrt(ww);
     return {t * w.x, t * w.y, t * w.z};
 }
 
