@@ -416,9 +416,8 @@ class Handle:
         self.device = device
         self._h = C.c_void_p()
         self._structs: Dict[int, Structure] = {}
-        self._observed: Dict[int, int] = {}  # slot -> number of frames selected by set_observed_frames
-        self._spheres: Dict[int, int] = {}  # slot -> number of spheres uploaded by set_collision_spheres
-        self._wrench_frames: Dict[int, int] = {}  # slot -> number of frames selected by set_wrench_frames
+        # slot -> the structure's companions the library cannot be asked for: "model" (model, task map), the numbers of "observed" frames, "spheres", "wrench" frames
+        self._companions: Dict[int, dict] = {}
         desc = CDesc(device, dtype, flags)
         rc = self.lib.wbcqp_create(C.byref(desc), C.byref(self._h))
         if rc != WBCQP_OK:
@@ -443,9 +442,13 @@ class Handle:
         sb = StructureBuffers(st)
         self._check(self.lib.wbcqp_set_structure(self._h, slot, C.byref(sb.c)))
         self._structs[slot] = st
-        self._observed.pop(slot, None)  # (the library drops the selection with the model)
-        self._spheres.pop(slot, None)
-        self._wrench_frames.pop(slot, None)
+        self._companions_of(slot, reset=True)
+
+    def _companions_of(self, slot: int, reset: bool = False) -> dict:
+        """The slot's record; reset: a fresh one (the library drops the model, the selections of frames and the sphere table with the structure or the model)."""
+        if reset or slot not in self._companions:
+            self._companions[slot] = {"model": None, "observed": 0, "spheres": 0, "wrench": 0}
+        return self._companions[slot]
 
     # ---- device-pointer path (torch tensors are only carriers of device memory) ----
     def _pack(self, slot: int, batch: int, inputs, outputs):
@@ -484,18 +487,17 @@ class Handle:
         """Binds a kinematic tree and its task bindings to a slot that holds the matching structure (wbcqp_set_model)."""
         mb = ModelBuffers(model, tm)
         self._check(self.lib.wbcqp_set_model(self._h, slot, C.byref(mb.model), C.byref(mb.taskmap)))
-        self._observed.pop(slot, None)
-        self._spheres.pop(slot, None)
-        self._wrench_frames.pop(slot, None)
-        self._models = getattr(self, "_models", {})
-        self._models[slot] = (model, tm)
+        self._companions_of(slot, reset=True)["model"] = (model, tm)
+
+    def _select_frames(self, slot: int, frames: Sequence[int], setter, what: str):
+        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
+        self._check(setter(self._h, slot, int(fr.size), fr.ctypes.data_as(c_i32_p)))
+        self._companions_of(slot)[what] = int(fr.size)
 
     def set_observed_frames(self, slot: int, frames: Sequence[int]):
         """Which frames of the slot's model wbcqp_observe reports: indices into the model's frame table (observe.frame_ids turns names into
         them), repeats allowed, at most 64 (wbcqp_set_observed_frames)."""
-        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
-        self._check(self.lib.wbcqp_set_observed_frames(self._h, slot, int(fr.size), fr.ctypes.data_as(c_i32_p)))
-        self._observed[slot] = int(fr.size)
+        self._select_frames(slot, frames, self.lib.wbcqp_set_observed_frames, "observed")
 
     def observe(self, slot: int, batch: int, q, v=None, com=None, vcom=None, placement=None, velocity=None, stream: int = 0):
         """CoM and frame poses of `batch` states on device tensors (wbcqp_observe): q [batch, nq], v [batch, nv] (None when neither vcom nor
@@ -510,7 +512,7 @@ class Handle:
         wrapper of the same handle) is not seen here -- such callers size their own buffers and use observe()."""
         q = np.ascontiguousarray(q, dtype=self.np_dtype)
         B = q.shape[0]
-        nf = self._observed.get(slot, 0)
+        nf = self._companions_of(slot)["observed"]
         res = {"com": np.zeros((B, 3), self.np_dtype)}
         if nf:
             res["placement"] = np.zeros((B, nf, 12), self.np_dtype)
@@ -526,9 +528,7 @@ class Handle:
     def set_wrench_frames(self, slot: int, frames: Sequence[int]):
         """Where the wrenches of inverse_dynamics act: indices into the model's frame table (observe.frame_ids turns names into them), repeats
         allowed, at most 8 (wbcqp_set_wrench_frames)."""
-        fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
-        self._check(self.lib.wbcqp_set_wrench_frames(self._h, slot, int(fr.size), fr.ctypes.data_as(c_i32_p)))
-        self._wrench_frames[slot] = int(fr.size)
+        self._select_frames(slot, frames, self.lib.wbcqp_set_wrench_frames, "wrench")
 
     def inverse_dynamics(self, slot: int, batch: int, q, tau, v=None, a=None, lda: int = 0, wrench=None, stream: int = 0):
         """tau = M(q) a + nle(q, v) - sum_k J_k' w_k of `batch` states on device tensors (wbcqp_inverse_dynamics): q [batch, nq], tau [batch, nv];
@@ -545,7 +545,7 @@ class Handle:
         """wbcqp_inverse_dynamics_host: tau [B, nv].  a [B, lda] with lda >= nv: its first nv columns are the accelerations (a tick's x as it is)."""
         q = np.ascontiguousarray(q, dtype=self.np_dtype)
         B = q.shape[0]
-        nv = self._models[slot][0].nv
+        nv = self._companions_of(slot)["model"][0].nv
         v, a, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, a, wrench))
         tau = np.zeros((B, nv), self.np_dtype)
         dat = lambda t: t.ctypes.data if t is not None else None
@@ -565,7 +565,7 @@ class Handle:
             sm = CSphereModel(n, keep[0].ctypes.data_as(c_i32_p), keep[1].ctypes.data_as(c_i32_p), keep[2].ctypes.data_as(c_f64_p),
                               keep[3].ctypes.data_as(C.POINTER(C.c_float)))
         self._check(self.lib.wbcqp_set_collision_spheres(self._h, slot, C.byref(sm)))
-        self._spheres[slot] = n
+        self._companions_of(slot)["spheres"] = n
 
     def check_collisions(self, slot: int, batch: int, q, colliding=None, first_pair=None, n_pairs=None, clearance=None, centres=None, stream: int = 0):
         """Self-collision of `batch` states on device tensors (wbcqp_check_collisions): q [batch, nq]; outputs, each optional: colliding [batch],
@@ -578,7 +578,7 @@ class Handle:
         set_collision_spheres last uploaded on the slot."""
         q = np.ascontiguousarray(q, dtype=self.np_dtype)
         B = q.shape[0]
-        ns = self._spheres.get(slot, 0)
+        ns = self._companions_of(slot)["spheres"]
         res = {"colliding": np.zeros(B, np.int32), "first_pair": np.zeros((B, 2), np.int32), "n_pairs": np.zeros(B, np.int32),
                "clearance": np.zeros(B, self.np_dtype), "centres": np.zeros((B, ns, 3), self.np_dtype)}
         out = CCollisions(*[res[k].ctypes.data if res[k].size else None for k in COLLISIONS])

@@ -121,6 +121,18 @@ namespace inria_wbc {
             }
         };
 
+        // "computed at this (source, q, v)": an answer a controller keeps WITH the state and the source it was made for, so whatever moves the
+        // state or replaces the source makes the next question fetch again (v null: the answer does not depend on it)
+        struct ComputedAt {
+            const ProblemSource* source = nullptr; // null: nothing kept
+            MatrixXd q, v;
+            bool current(const ProblemSource* s, const MatrixXd& qn, const MatrixXd* vn) const
+            {
+                return source && source == s && q.rows == qn.rows && q.data == qn.data && (!vn || v.data == vn->data);
+            }
+            void set(const ProblemSource* s, const MatrixXd& qn, const MatrixXd* vn) { source = s; q = qn; if (vn) v = *vn; }
+        };
+
         class Controller {
         public:
             explicit Controller(const yaml::Node& config)
@@ -355,7 +367,7 @@ namespace inria_wbc {
                 if (check_model_collisions_ && !src->has_model())
                     IWBC_ERROR("check_model_collisions is set, but this problem source has no model: the check needs a model-driven source (CONTROLLER.model)");
                 send_cmd_.clear();
-                col_source_ = nullptr;
+                col_at_ = ComputedAt{};
                 source_ = src;
                 batch_ = src->batch();
                 _reset();
@@ -521,11 +533,10 @@ namespace inria_wbc {
                     return;
                 }
                 IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (col_source_ == source_.get() && col_q_.rows == q_tsid_.rows && col_q_.data == q_tsid_.data) return;
-                self->col_source_ = nullptr;
+                if (col_at_.current(source_.get(), q_tsid_, nullptr)) return;
+                self->col_at_ = ComputedAt{};
                 self->source_->check_collisions(q_tsid_, collision_file_, self->col_flags_, self->col_pairs_, self->col_names_);
-                self->col_q_ = q_tsid_;
-                self->col_source_ = source_.get();
+                self->col_at_.set(source_.get(), q_tsid_, nullptr);
             }
             bool check_model_collisions_ = false;
             std::string collision_file_;
@@ -533,8 +544,7 @@ namespace inria_wbc {
             MatrixXd q_sent_, dq_sent_, ddq_sent_, tau_sent_;
             VectorXi col_flags_, col_pairs_;
             std::vector<std::pair<std::string, int>> col_names_;
-            MatrixXd col_q_;                             // the state the answer above was computed at
-            const ProblemSource* col_source_ = nullptr; // ... and by which source (null: nothing kept)
+            ComputedAt col_at_; // the state (q alone) and the source the answer above was made for
 
             bool verbose_ = false;
             double t_ = 0.0, dt_ = 0.001;
@@ -580,10 +590,8 @@ namespace inria_wbc {
                         added = true;
                     }
                 }
-                const bool current = !added && obs_source_ == source_.get() && obs_q_.rows == q_tsid_.rows && obs_q_.data == q_tsid_.data &&
-                                     obs_v_.data == v_tsid_.data;
-                if (!current) {
-                    self->obs_source_ = nullptr;
+                if (added || !obs_at_.current(source_.get(), q_tsid_, &v_tsid_)) {
+                    self->obs_at_ = ComputedAt{};
                     try {
                         self->source_->observe(q_tsid_, v_tsid_, obs_names_, self->obs_com_, self->obs_vcom_, self->obs_place_, self->obs_vel_);
                     }
@@ -591,9 +599,7 @@ namespace inria_wbc {
                         if (added) self->obs_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
                         throw;
                     }
-                    self->obs_q_ = q_tsid_;
-                    self->obs_v_ = v_tsid_;
-                    self->obs_source_ = source_.get();
+                    self->obs_at_.set(source_.get(), q_tsid_, &v_tsid_);
                 }
                 return at;
             }
@@ -605,8 +611,7 @@ namespace inria_wbc {
             }
             std::vector<std::string> obs_names_;
             MatrixXd obs_com_, obs_vcom_, obs_place_, obs_vel_;
-            MatrixXd obs_q_, obs_v_;                     // the state the four above were computed at
-            const ProblemSource* obs_source_ = nullptr; // ... and by which source (null: nothing kept)
+            ComputedAt obs_at_; // the state and the source the four above were made for
 
             std::shared_ptr<ProblemSource> source_;
             TickInputs in_;

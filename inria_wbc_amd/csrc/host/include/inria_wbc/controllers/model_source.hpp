@@ -183,8 +183,7 @@ namespace inria_wbc {
                 tm.dt = dt;
                 tm.nref = nref_;
                 if (wbcqp_set_model(h, slot, &md, &tm) != WBCQP_OK) IWBC_ERROR("wbcqp_set_model failed: ", wbcqp_last_error(h));
-                spheres_.erase(slot); // (the library drops the sphere table with the model)
-                wrench_frames_.erase(slot);
+                drop_query_tables(slot);
                 auto c0 = robot_->com(q0_.data());
                 com_pos_ = MatrixXd(batch_, 3);
                 com_vel_ = MatrixXd(batch_, 3);
@@ -197,9 +196,7 @@ namespace inria_wbc {
             {
                 if (cur_ && bounds_.count(slot) && cur_ == &bounds_[slot]) cur_ = nullptr;
                 bounds_.erase(slot);
-                observed_.erase(slot); // (the library drops the selection with the model)
-                spheres_.erase(slot);
-                wrench_frames_.erase(slot);
+                drop_query_tables(slot);
             }
 
             // wbcqp_check_collisions_host on the slot in use.  The table is built from the collision file when the slot has none for that file:
@@ -268,14 +265,7 @@ namespace inria_wbc {
                 IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
                 IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq() && v.rows == batch_ && v.cols == robot_->nv(), "one state row per instance");
                 IWBC_ASSERT((int)frames.size() <= WBCQP_MAX_OBSERVED, "at most ", WBCQP_MAX_OBSERVED, " frames can be observed");
-                auto known = observed_.find(slot_);
-                if (known == observed_.end() || known->second != frames) {
-                    std::vector<int32_t> ids;
-                    for (const auto& f : frames) ids.push_back(robot_->getFrameId(f));
-                    if (wbcqp_set_observed_frames(handle_, slot_, (int)ids.size(), ids.data()) != WBCQP_OK)
-                        IWBC_ERROR("wbcqp_set_observed_frames failed: ", wbcqp_last_error(handle_));
-                    observed_[slot_] = frames;
-                }
+                select_frames(observed_, frames, wbcqp_set_observed_frames, "wbcqp_set_observed_frames");
                 const int n = (int)frames.size();
                 com = MatrixXd(batch_, 3);
                 vcom = MatrixXd(batch_, 3);
@@ -296,14 +286,7 @@ namespace inria_wbc {
                             "one state row per instance");
                 IWBC_ASSERT(n <= WBCQP_MAX_WRENCH_FRAMES, "at most ", WBCQP_MAX_WRENCH_FRAMES, " wrench frames");
                 IWBC_ASSERT(n == 0 || (wrenches.rows == batch_ && wrenches.cols == 6 * n), "six numbers per frame and instance");
-                auto known = wrench_frames_.find(slot_);
-                if (known == wrench_frames_.end() || known->second != frames) {
-                    std::vector<int32_t> ids;
-                    for (const auto& f : frames) ids.push_back(robot_->getFrameId(f));
-                    if (wbcqp_set_wrench_frames(handle_, slot_, n, ids.data()) != WBCQP_OK)
-                        IWBC_ERROR("wbcqp_set_wrench_frames failed: ", wbcqp_last_error(handle_));
-                    wrench_frames_[slot_] = frames;
-                }
+                select_frames(wrench_frames_, frames, wbcqp_set_wrench_frames, "wbcqp_set_wrench_frames");
                 tau = MatrixXd(batch_, nv);
                 if (wbcqp_inverse_dynamics_host(handle_, slot_, batch_, q.data.data(), v.data.data(), a.data.data(), a.cols, n ? wrenches.data.data() : nullptr,
                                                 tau.data.data()) != WBCQP_OK)
@@ -416,6 +399,25 @@ namespace inria_wbc {
             int nref() const { return cur_ ? cur_->nref_ : 0; }
 
         private:
+            using FrameNames = std::map<int, std::vector<std::string>>; // slot -> the frames selected on it
+            // the selection of frames goes to the slot in use when it differs from the one the slot holds
+            void select_frames(FrameNames& held, const std::vector<std::string>& frames, int (*setter)(wbcqp_handle*, int, int, const int32_t*), const char* setter_name)
+            {
+                auto known = held.find(slot_);
+                if (known != held.end() && known->second == frames) return;
+                std::vector<int32_t> ids;
+                for (const auto& f : frames) ids.push_back(robot_->getFrameId(f));
+                if (setter(handle_, slot_, (int)ids.size(), ids.data()) != WBCQP_OK) IWBC_ERROR(setter_name, " failed: ", wbcqp_last_error(handle_));
+                held[slot_] = frames;
+            }
+            // the library drops the selections of frames and the sphere table with the model
+            void drop_query_tables(int slot)
+            {
+                observed_.erase(slot);
+                spheres_.erase(slot);
+                wrench_frames_.erase(slot);
+            }
+
             void store(const std::string& name, int off, const std::vector<double>& r)
             {
                 IWBC_ASSERT(cur_, "ModelSource is not bound to a solver");
@@ -447,8 +449,7 @@ namespace inria_wbc {
             std::vector<double> q0_, posture_user_;
             wbcqp_handle* handle_ = nullptr;
             std::map<int, Bound> bounds_;
-            std::map<int, std::vector<std::string>> observed_; // slot -> the frames selected on it (wbcqp_set_observed_frames)
-            std::map<int, std::vector<std::string>> wrench_frames_; // ... and the frames its wrenches act at (wbcqp_set_wrench_frames)
+            FrameNames observed_, wrench_frames_; // wbcqp_set_observed_frames, wbcqp_set_wrench_frames
             // slot -> the collision file whose table it holds (wbcqp_set_collision_spheres) and every table entry's (member, place in the member)
             std::map<int, std::pair<std::string, std::vector<std::pair<std::string, int>>>> spheres_;
             Bound* cur_ = nullptr;

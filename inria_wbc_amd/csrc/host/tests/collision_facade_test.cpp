@@ -7,41 +7,11 @@
 //       writes, as doubles: the checked controller's final q_tsid (B x nq) and its is_model_colliding (B)
 //   collision_facade_test --file-source <controller.yaml> <collisions.yaml> <batch.bin>
 //       check_model_collisions on a source without a model must be refused, in words that say so
-#include <cmath>
-#include <fstream>
-#include <iostream>
-
-#include <inria_wbc/behaviors/humanoid/move_com.hpp>
-#include <inria_wbc/controllers/file_source.hpp>
-#include <inria_wbc/controllers/model_source.hpp>
-#include <inria_wbc/controllers/pos_tracker.hpp>
-
-using namespace inria_wbc;
-using controllers::MatrixXd;
-
-static std::shared_ptr<controllers::Controller> make_controller(const std::string& path, int batch, const std::string& collisions)
-{
-    yaml::Node c_config = IWBC_CHECK(yaml::LoadFile(path));
-    c_config["CONTROLLER"].set("base_path", path.substr(0, path.find_last_of('/')));
-    if (batch > 0) c_config["CONTROLLER"].set("batch", std::to_string(batch));
-    if (!collisions.empty()) {
-        c_config["CONTROLLER"].set("check_model_collisions", "true");
-        c_config["CONTROLLER"].set("collision_path", collisions);
-    }
-    return controllers::Factory::instance().create(IWBC_CHECK(c_config["CONTROLLER"]["name"].as<std::string>()), c_config);
-}
+#include "model_query_facade.hpp"
 
 static int file_source_mode(char** argv)
 {
-    bool refused = false;
-    try {
-        auto controller = make_controller(argv[2], 0, argv[3]);
-        controller->set_problem_source(std::make_shared<controllers::FileSource>(argv[4]));
-    }
-    catch (std::exception& e) {
-        refused = std::string(e.what()).find("no model") != std::string::npos;
-        std::cout << "message: " << e.what() << std::endl;
-    }
+    const bool refused = refused_without_model([&] { make_controller(argv[2], 0, argv[3])->set_problem_source(std::make_shared<controllers::FileSource>(argv[4])); }, true);
     std::cout << "refused: " << refused << std::endl;
     return refused ? 0 : 1;
 }
@@ -77,7 +47,7 @@ int main(int argc, char** argv)
         const int n_ticks = std::atoi(argv[4]), B = std::atoi(argv[5]), k = std::atoi(argv[6]);
         const double roll = std::atof(argv[7]);
         yaml::Node b_config = IWBC_CHECK(yaml::LoadFile(argv[2]));
-        std::shared_ptr<controllers::Controller> ctl[2] = {make_controller(argv[1], B, argv[3]), make_controller(argv[1], B, "")};
+        std::shared_ptr<controllers::Controller> ctl[2] = {make_controller(argv[1], B, argv[3]), make_controller(argv[1], B)};
         std::vector<Tick> rec[2];
         std::vector<std::vector<int>> flags;
         MatrixXd q_start, zero_v;

@@ -6,29 +6,12 @@
 //       a sensor map with a key missing.  Prints the deviations.
 //   inverse_dynamics_facade_test --file-source <controller.yaml> <batch.bin>
 //       a controller on a FileSource must refuse (it has no model)
-#include <cmath>
-#include <iostream>
-
-#include <inria_wbc/behaviors/humanoid/move_com.hpp>
-#include <inria_wbc/controllers/file_source.hpp>
-#include <inria_wbc/controllers/model_source.hpp>
-#include <inria_wbc/controllers/pos_tracker.hpp>
-
-using namespace inria_wbc;
-using controllers::MatrixXd;
+#include "model_query_facade.hpp"
 
 static const char* kLeft = "leg_left_6_joint";
 static const char* kRight = "leg_right_6_joint";
 static const char* kLeftSole = "left_sole_under_test";
 static const char* kRightSole = "right_sole_under_test";
-
-static std::shared_ptr<controllers::Controller> make_controller(const std::string& path, int batch)
-{
-    yaml::Node c_config = IWBC_CHECK(yaml::LoadFile(path));
-    c_config["CONTROLLER"].set("base_path", path.substr(0, path.find_last_of('/')));
-    if (batch > 0) c_config["CONTROLLER"].set("batch", std::to_string(batch));
-    return controllers::Factory::instance().create(IWBC_CHECK(c_config["CONTROLLER"]["name"].as<std::string>()), c_config);
-}
 
 static controllers::SensorData zero_sensors()
 {
@@ -41,11 +24,8 @@ static int file_source_mode(char** argv)
 {
     auto controller = make_controller(argv[2], 0);
     controller->set_problem_source(std::make_shared<controllers::FileSource>(argv[3]));
-    int refused = 0;
-    try { controller->rnea_double_support(zero_sensors(), false, kLeft, kRight, kLeftSole, kRightSole); }
-    catch (std::exception& e) { refused += std::string(e.what()).find("no model") != std::string::npos; }
-    try { controller->rnea_double_support(zero_sensors(), true, kLeft, kRight, kLeftSole, kRightSole); }
-    catch (std::exception& e) { refused += std::string(e.what()).find("no model") != std::string::npos; }
+    const int refused = refused_without_model([&] { controller->rnea_double_support(zero_sensors(), false, kLeft, kRight, kLeftSole, kRightSole); }) +
+                        refused_without_model([&] { controller->rnea_double_support(zero_sensors(), true, kLeft, kRight, kLeftSole, kRightSole); });
     std::cout << "refused: " << refused << " of 2" << std::endl;
     return refused == 2 ? 0 : 1;
 }
@@ -71,9 +51,7 @@ int main(int argc, char** argv)
         // two sole frames under the ankles (the reference's robots carry them in their URDF), then a source that uploads the model with them
         pt->robot()->addFrame(kLeftSole, kLeft, {{0.01, 0.0, -0.107}});
         pt->robot()->addFrame(kRightSole, kRight, {{0.01, 0.0, -0.107}});
-        yaml::Node cc = IWBC_CHECK(yaml::LoadFile(argv[1]));
-        auto source = std::make_shared<controllers::ModelSource>(pt->robot(), controller->batch_size(),
-                                                                 pt->robot()->referenceConfigurations().at(IWBC_CHECK(cc["CONTROLLER"]["ref_config"].as<std::string>())));
+        auto source = make_source<controllers::ModelSource>(*pt, argv[1]);
         controller->set_problem_source(source);
         yaml::Node b_config = IWBC_CHECK(yaml::LoadFile(argv[2]));
         auto behavior = behaviors::Factory::instance().create(IWBC_CHECK(b_config["BEHAVIOR"]["name"].as<std::string>()), controller, b_config);

@@ -5,16 +5,7 @@
 //       com_now pos and vel (B x 3 each), then per frame model_frame_pos (B x 12) and model_frame_vel (B x 6)
 //   observe_facade_test --file-source <controller.yaml> <batch.bin>
 //       a controller on a FileSource must refuse the three accessors (it has no model)
-#include <cmath>
-#include <fstream>
-#include <iostream>
-
-#include <inria_wbc/behaviors/humanoid/move_com.hpp>
-#include <inria_wbc/controllers/file_source.hpp>
-#include <inria_wbc/controllers/model_source.hpp>
-#include <inria_wbc/controllers/pos_tracker.hpp>
-
-using namespace inria_wbc;
+#include "model_query_facade.hpp"
 
 // the controller's own kind of source, counting the trips to the device the accessors cause
 struct CountingSource : controllers::ModelSource {
@@ -28,23 +19,13 @@ struct CountingSource : controllers::ModelSource {
     }
 };
 
-static std::shared_ptr<controllers::Controller> make_controller(const std::string& path, int batch)
-{
-    yaml::Node c_config = IWBC_CHECK(yaml::LoadFile(path));
-    c_config["CONTROLLER"].set("base_path", path.substr(0, path.find_last_of('/')));
-    if (batch > 0) c_config["CONTROLLER"].set("batch", std::to_string(batch));
-    return controllers::Factory::instance().create(IWBC_CHECK(c_config["CONTROLLER"]["name"].as<std::string>()), c_config);
-}
-
 static int file_source_mode(char** argv)
 {
     auto controller = make_controller(argv[2], 0);
     controller->set_problem_source(std::make_shared<controllers::FileSource>(argv[3]));
-    int refused = 0;
     controllers::MatrixXd a, b;
-    try { controller->com_now(a, b); } catch (std::exception& e) { refused += std::string(e.what()).find("no model") != std::string::npos; }
-    try { controller->model_frame_pos("leg_left_6_joint"); } catch (std::exception& e) { refused += std::string(e.what()).find("no model") != std::string::npos; }
-    try { controller->model_frame_vel("leg_left_6_joint"); } catch (std::exception& e) { refused += std::string(e.what()).find("no model") != std::string::npos; }
+    const int refused = refused_without_model([&] { controller->com_now(a, b); }) + refused_without_model([&] { controller->model_frame_pos("leg_left_6_joint"); }) +
+                        refused_without_model([&] { controller->model_frame_vel("leg_left_6_joint"); });
     std::cout << "refused: " << refused << " of 3" << std::endl;
     return refused == 3 ? 0 : 1;
 }
@@ -60,9 +41,7 @@ int main(int argc, char** argv)
         auto controller = make_controller(argv[1], std::atoi(argv[4]));
         auto pt = std::dynamic_pointer_cast<controllers::PosTracker>(controller);
         IWBC_ASSERT(pt && pt->robot(), "the controller must be a PosTracker with a model");
-        yaml::Node cc = IWBC_CHECK(yaml::LoadFile(argv[1]));
-        auto counting = std::make_shared<CountingSource>(pt->robot(), controller->batch_size(),
-                                                         pt->robot()->referenceConfigurations().at(IWBC_CHECK(cc["CONTROLLER"]["ref_config"].as<std::string>())));
+        auto counting = make_source<CountingSource>(*pt, argv[1]);
         controller->set_problem_source(counting);
         yaml::Node b_config = IWBC_CHECK(yaml::LoadFile(argv[2]));
         auto behavior = behaviors::Factory::instance().create(IWBC_CHECK(b_config["BEHAVIOR"]["name"].as<std::string>()), controller, b_config);
@@ -130,7 +109,7 @@ int main(int argc, char** argv)
         }
         const bool refetched = counting->calls == calls_tick + 1;
         // a controller put back to its start (a new problem source: _reset) answers for q0 again
-        auto fresh = std::make_shared<CountingSource>(pt->robot(), B, pt->robot()->referenceConfigurations().at(IWBC_CHECK(cc["CONTROLLER"]["ref_config"].as<std::string>())));
+        auto fresh = make_source<CountingSource>(*pt, argv[1]);
         controller->set_problem_source(fresh);
         controllers::MatrixXd c_reset, v_reset;
         controller->com_now(c_reset, v_reset);

@@ -7,13 +7,13 @@
 //
 // This file holds the exported entry points; the host code behind them is in the wbcqp_host_*.hpp headers, included here and nowhere else (the library
 // stays ONE translation unit): the handle, the description of a call's arrays and the staging (handle), structure -> sizes and LDS layouts (derive),
-// arguments -> kernel launches (launch), reference programs (program), the loops over ticks (rollout).
+// arguments -> kernel launches (launch), reference programs (program), the loops over ticks (rollout), the model queries on a fleet's states (queries).
 #include "wbcqp_host_handle.hpp"
 #include "wbcqp_host_derive.hpp"
 #include "wbcqp_host_launch.hpp"
 #include "wbcqp_host_program.hpp"
 #include "wbcqp_host_rollout.hpp"
-#include "wbcqp_host_dynamics.hpp"
+#include "wbcqp_host_queries.hpp"
 
 namespace {
 
@@ -506,21 +506,15 @@ int wbcqp_integrate_host(wbcqp_handle* h, int batch, int nv, int floating_base, 
     if (batch == 0) return WBCQP_OK;
     if (!q || !dq || !x || !q_next || !v_next) return fail(h, WBCQP_ERR_INVALID, "q / dq / x / q_next / v_next is NULL");
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t es = (h->dtype == WBCQP_F64) ? 8 : 4;
+    const size_t es = elem_size(h);
     const int nq = floating_base ? nv + 1 : nv;
     const size_t nqb = (size_t)batch * nq * es, nvb = (size_t)batch * nv * es;
     Arr up[4] = {{F_q, const_cast<void*>(q), nqb, 0}, {F_v, const_cast<void*>(dq), nvb, 0}, {F_x, const_cast<void*>(x), (size_t)batch * ldx * es, 0},
                  {F_status, const_cast<int32_t*>(status), (size_t)batch * 4, 0}};
     Arr dn[3] = {{F_qn, q_next, nqb, 0}, {F_vn, v_next, nvb, 0}, {F_qs, q_solver, nvb, 0}};
-    WB_TRY(stage_begin(h, lay(up, 4), lay(dn, 3), false));
-    WB_TRY(stage_up(h, h->stage_in.dev, up, 4, 0, Xfer::blocking));
-    char* din = static_cast<char*>(h->stage_in.dev);
-    char* dout = static_cast<char*>(h->stage_out.dev);
-    WB_TRY(wbcqp_integrate(h, batch, nv, floating_base, dt, din + up[0].off, din + up[1].off, din + up[2].off, ldx,
-                           status ? reinterpret_cast<const int32_t*>(din + up[3].off) : nullptr, dout + dn[0].off, dout + dn[1].off,
-                           q_solver ? dout + dn[2].off : nullptr, nullptr));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return stage_down(h, dout, dn, 3, 0, Xfer::blocking);
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return wbcqp_integrate(h, batch, nv, floating_base, dt, u[0], u[1], u[2], ldx, static_cast<const int32_t*>(u[3]), d[0], d[1], d[2], nullptr);
+    });
 }
 
 int wbcqp_check_model(const wbcqp_structure* st, const wbcqp_model* md, const wbcqp_taskmap* tm, int32_t* lds_bytes)
@@ -585,244 +579,88 @@ int wbcqp_set_model(wbcqp_handle* h, int slot, const wbcqp_model* md, const wbcq
 
 int wbcqp_set_observed_frames(wbcqp_handle* h, int slot, int n_frames, const int32_t* frames)
 {
-    if (!h) return WBCQP_ERR_INVALID;
-    Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (n_frames < 0 || n_frames > WBCQP_MAX_OBSERVED) return fail(h, WBCQP_ERR_INVALID, "n_frames must be in [0, 64]");
-    if (n_frames > 0 && !frames) return fail(h, WBCQP_ERR_INVALID, "frames is NULL");
-    const int nframe = (int)s->frame_body_h.size();
-    std::vector<int> body(n_frames);
-    std::vector<double> place((size_t)12 * n_frames);
-    for (int f = 0; f < n_frames; ++f) {
-        if (frames[f] < 0 || frames[f] >= nframe) return fail(h, WBCQP_ERR_INVALID, "an observed frame does not exist in the slot's model");
-        body[f] = s->frame_body_h[frames[f]];
-        std::copy(s->frame_place_h.begin() + (size_t)12 * frames[f], s->frame_place_h.begin() + (size_t)12 * frames[f] + 12, place.begin() + (size_t)12 * f);
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    release_observed(*s); // (hipFree waits for whatever still reads the previous selection)
-    if (n_frames == 0) return WBCQP_OK;
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s->obs_body), body.size() * sizeof(int)));
-    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&s->obs_place), place.size() * sizeof(double)));
-    HIP_TRY(h, hipMemcpy(s->obs_body, body.data(), body.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(h, hipMemcpy(s->obs_place, place.data(), place.size() * sizeof(double), hipMemcpyHostToDevice));
-    s->n_obs = n_frames;
-    return WBCQP_OK;
+    return set_frame_selection(h, slot, &Slot::observed, n_frames, frames, WBCQP_MAX_OBSERVED, "an observed frame", "the observed frames");
 }
 
 int wbcqp_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream)
 {
-    if (!h) return WBCQP_ERR_INVALID;
-    const Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
-    if (!out) return fail(h, WBCQP_ERR_INVALID, "observables struct is NULL");
-    if ((out->placement || out->velocity) && s->n_obs == 0)
-        return fail(h, WBCQP_ERR_INVALID, "placement / velocity asked for, but no frames are selected (wbcqp_set_observed_frames)");
-    if ((out->vcom || out->velocity) && !v) return fail(h, WBCQP_ERR_INVALID, "vcom / velocity asked for, but v is NULL");
-    if (batch == 0 || (!out->com && !out->vcom && !out->placement && !out->velocity)) return WBCQP_OK;
-    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    const Slot* s = nullptr;
+    WB_TRY(check_observe(h, slot, batch, q, v, out, &s));
+    if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const TermsDev& T = s->terms;
-    const bool frames = out->placement || out->velocity;
-    const ObserveDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_idxq, T.i_idxv, T.i_anc, T.d_place, T.d_inertia,
-                       frames ? s->n_obs : 0, s->obs_body, s->obs_place};
-    const int blocks = (batch + kObservePerBlock - 1) / kObservePerBlock;
-    return with_dtype(h, [&](auto tag) -> int {
-        using TI = WB_TI(tag);
-        const ObserveArgs<TI> a{D, static_cast<const TI*>(q), (out->vcom || out->velocity) ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out->com),
-                                static_cast<TI*>(out->vcom), static_cast<TI*>(out->placement), static_cast<TI*>(out->velocity), batch};
-        hipLaunchKernelGGL(observe_kernel<TI>, dim3(blocks), dim3(kObserveThreads), observe_lds_bytes(D.n_frames), static_cast<hipStream_t>(stream), a);
-        HIP_TRY(h, hipGetLastError());
-        return WBCQP_OK;
-    });
+    return launch_observe(h, *s, batch, q, v, *out, static_cast<hipStream_t>(stream));
 }
 
 int wbcqp_observe_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out)
 {
-    if (!h) return WBCQP_ERR_INVALID;
-    const Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
-    if (!out) return fail(h, WBCQP_ERR_INVALID, "observables struct is NULL");
+    const Slot* s = nullptr;
+    WB_TRY(check_observe(h, slot, batch, q, v, out, &s));
+    if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const size_t es = elem_size(h), B = (size_t)batch, nf = (size_t)s->n_obs;
+    const size_t es = elem_size(h), B = (size_t)batch, nf = (size_t)s->observed.n;
     Arr up[2] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * s->terms.nv * es, 0}};
     Arr dn[4] = {{-1, out->com, B * 3 * es, 0}, {-1, out->vcom, B * 3 * es, 0}, {-1, out->placement, B * nf * 12 * es, 0}, {-1, out->velocity, B * nf * 6 * es, 0}};
-    WB_TRY(stage_begin(h, lay(up, 2), lay(dn, 4), false));
-    WB_TRY(stage_up(h, h->stage_in.dev, up, 2, 0, Xfer::blocking));
-    char* din = static_cast<char*>(h->stage_in.dev);
-    char* dout = static_cast<char*>(h->stage_out.dev);
-    const wbcqp_observables d = {out->com ? dout + dn[0].off : nullptr, out->vcom ? dout + dn[1].off : nullptr, out->placement ? dout + dn[2].off : nullptr,
-                                 out->velocity ? dout + dn[3].off : nullptr};
-    WB_TRY(wbcqp_observe(h, slot, batch, q ? din + up[0].off : nullptr, v ? din + up[1].off : nullptr, &d, nullptr));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return stage_down(h, dout, dn, 4, 0, Xfer::blocking);
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_observe(h, *s, batch, u[0], u[1], wbcqp_observables{d[0], d[1], d[2], d[3]}, nullptr);
+    });
 }
 
-int wbcqp_set_collision_spheres(wbcqp_handle* h, int slot, const wbcqp_sphere_model* sm)
-{
-    if (!h) return WBCQP_ERR_INVALID;
-    Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (!sm) return fail(h, WBCQP_ERR_INVALID, "sphere model is NULL");
-    const int n = sm->n_spheres;
-    if (n < 0 || n > WBCQP_MAX_SPHERES) return fail(h, WBCQP_ERR_INVALID, "n_spheres must be in [0, 256]");
-    if (n > 0 && (!sm->body || !sm->member || !sm->centre || !sm->diameter)) return fail(h, WBCQP_ERR_INVALID, "body / member / centre / diameter is NULL");
-    // one allocation: centre [n][3] doubles, then body, tag (member << 8 | place inside the member) and half-diameter, 4 bytes each
-    std::vector<double> store(((size_t)n * (24 + 12) + 7) / 8); // (doubles: the block's alignment is the centres')
-    char* blob = reinterpret_cast<char*>(store.data());
-    const size_t blob_bytes = (size_t)n * (24 + 12);
-    double* centre = store.data();
-    int* body = reinterpret_cast<int*>(blob + (size_t)24 * n);
-    int* tag = body + n;
-    float* half = reinterpret_cast<float*>(tag + n);
-    for (int i = 0, place = 0; i < n; ++i) {
-        if (sm->body[i] < 0 || sm->body[i] >= s->terms.nb) return fail(h, WBCQP_ERR_INVALID, "a sphere's body is outside the slot's tree");
-        if (sm->member[i] < 0 || sm->member[i] >= WBCQP_MAX_MEMBERS) return fail(h, WBCQP_ERR_INVALID, "a sphere's member must be in [0, 16)");
-        if (i > 0 && sm->member[i] < sm->member[i - 1]) return fail(h, WBCQP_ERR_INVALID, "member must be non-decreasing (spheres sorted by member)");
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(sm->centre[3 * i + k])) return fail(h, WBCQP_ERR_INVALID, "a sphere's centre is not finite");
-        if (!std::isfinite(sm->diameter[i]) || !(sm->diameter[i] > 0.0f)) return fail(h, WBCQP_ERR_INVALID, "a sphere's diameter must be finite and > 0");
-        place = (i > 0 && sm->member[i] == sm->member[i - 1]) ? place + 1 : 0;
-        body[i] = sm->body[i];
-        tag[i] = (sm->member[i] << 8) | place;
-        half[i] = sm->diameter[i] / 2; // a float division, as the reference's sphere.second / 2
-        std::copy(sm->centre + 3 * i, sm->centre + 3 * i + 3, centre + 3 * i);
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    void* fresh = nullptr; // the new table is complete on the device before the one before goes
-    if (n > 0) {
-        HIP_TRY(h, hipMalloc(&fresh, blob_bytes));
-        if (hipMemcpy(fresh, blob, blob_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(h, WBCQP_ERR_HIP, "copying the sphere table to the device failed");
-        }
-    }
-    release_spheres(*s); // (hipFree waits for whatever still reads the previous table)
-    if (n == 0) return WBCQP_OK;
-    s->spheres_alloc = fresh;
-    char* d = static_cast<char*>(s->spheres_alloc);
-    const int* dbody = reinterpret_cast<const int*>(d + (size_t)24 * n);
-    s->spheres = CollideDev{n, dbody, dbody + n, reinterpret_cast<const double*>(d), reinterpret_cast<const float*>(dbody + 2 * n)};
-    return WBCQP_OK;
-}
+int wbcqp_set_collision_spheres(wbcqp_handle* h, int slot, const wbcqp_sphere_model* sm) { return set_collision_spheres(h, slot, sm); }
 
 int wbcqp_check_collisions(wbcqp_handle* h, int slot, int batch, const void* q, const wbcqp_collisions* out, void* stream)
 {
-    if (!h) return WBCQP_ERR_INVALID;
-    const Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (s->spheres.n_spheres == 0) return fail(h, WBCQP_ERR_INVALID, "slot has no sphere table (wbcqp_set_collision_spheres)");
-    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
-    if (!out) return fail(h, WBCQP_ERR_INVALID, "collisions struct is NULL");
-    if (batch == 0 || (!out->colliding && !out->first_pair && !out->n_pairs && !out->clearance && !out->centres)) return WBCQP_OK;
-    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    const Slot* s = nullptr;
+    WB_TRY(check_collisions(h, slot, batch, q, out, &s));
+    if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    const TermsDev& T = s->terms;
-    const ObserveDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_idxq, T.i_idxv, T.i_anc, T.d_place, T.d_inertia, 0, nullptr, nullptr};
-    const int blocks = (batch + kObservePerBlock - 1) / kObservePerBlock;
-    return with_dtype(h, [&](auto tag) -> int {
-        using TI = WB_TI(tag);
-        const CollideArgs<TI> a{D, s->spheres, static_cast<const TI*>(q), out->colliding, out->first_pair, out->n_pairs, static_cast<TI*>(out->clearance),
-                                static_cast<TI*>(out->centres), batch};
-        hipLaunchKernelGGL(collide_kernel<TI>, dim3(blocks), dim3(kObserveThreads), collide_lds_bytes(s->spheres.n_spheres), static_cast<hipStream_t>(stream), a);
-        HIP_TRY(h, hipGetLastError());
-        return WBCQP_OK;
-    });
+    return launch_collisions(h, *s, batch, q, *out, static_cast<hipStream_t>(stream));
 }
 
 int wbcqp_check_collisions_host(wbcqp_handle* h, int slot, int batch, const void* q, const wbcqp_collisions* out)
 {
-    if (!h) return WBCQP_ERR_INVALID;
-    const Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (s->spheres.n_spheres == 0) return fail(h, WBCQP_ERR_INVALID, "slot has no sphere table (wbcqp_set_collision_spheres)");
-    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
-    if (!out) return fail(h, WBCQP_ERR_INVALID, "collisions struct is NULL");
+    const Slot* s = nullptr;
+    WB_TRY(check_collisions(h, slot, batch, q, out, &s));
+    if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h), B = (size_t)batch, ns = (size_t)s->spheres.n_spheres;
     Arr up[1] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}};
     Arr dn[5] = {{-1, out->colliding, B * 4, 0}, {-1, out->first_pair, B * 8, 0}, {-1, out->n_pairs, B * 4, 0}, {-1, out->clearance, B * es, 0},
                  {-1, out->centres, B * ns * 3 * es, 0}};
-    WB_TRY(stage_begin(h, lay(up, 1), lay(dn, 5), false));
-    WB_TRY(stage_up(h, h->stage_in.dev, up, 1, 0, Xfer::blocking));
-    char* din = static_cast<char*>(h->stage_in.dev);
-    char* dout = static_cast<char*>(h->stage_out.dev);
-    const wbcqp_collisions d = {out->colliding ? reinterpret_cast<int32_t*>(dout + dn[0].off) : nullptr,
-                                out->first_pair ? reinterpret_cast<int32_t*>(dout + dn[1].off) : nullptr,
-                                out->n_pairs ? reinterpret_cast<int32_t*>(dout + dn[2].off) : nullptr, out->clearance ? dout + dn[3].off : nullptr,
-                                out->centres ? dout + dn[4].off : nullptr};
-    WB_TRY(wbcqp_check_collisions(h, slot, batch, q ? din + up[0].off : nullptr, &d, nullptr));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return stage_down(h, dout, dn, 5, 0, Xfer::blocking);
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        const wbcqp_collisions dev = {static_cast<int32_t*>(d[0]), static_cast<int32_t*>(d[1]), static_cast<int32_t*>(d[2]), d[3], d[4]};
+        return launch_collisions(h, *s, batch, u[0], dev, nullptr);
+    });
 }
 
 int wbcqp_set_wrench_frames(wbcqp_handle* h, int slot, int n_frames, const int32_t* frames)
 {
-    if (!h) return WBCQP_ERR_INVALID;
-    Slot* s = slot_with_model(h, slot);
-    if (!s) return WBCQP_ERR_INVALID;
-    if (n_frames < 0 || n_frames > WBCQP_MAX_WRENCH_FRAMES) return fail(h, WBCQP_ERR_INVALID, "n_frames must be in [0, 8]");
-    if (n_frames > 0 && !frames) return fail(h, WBCQP_ERR_INVALID, "frames is NULL");
-    static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
-    const int nframe = (int)s->frame_body_h.size();
-    // one allocation: placement [n][12] doubles, then body [n]
-    std::vector<double> store((size_t)12 * n_frames + ((size_t)n_frames + 1) / 2);
-    int* body = reinterpret_cast<int*>(store.data() + (size_t)12 * n_frames);
-    for (int f = 0; f < n_frames; ++f) {
-        if (frames[f] < 0 || frames[f] >= nframe) return fail(h, WBCQP_ERR_INVALID, "a wrench frame does not exist in the slot's model");
-        body[f] = s->frame_body_h[frames[f]];
-        std::copy(s->frame_place_h.begin() + (size_t)12 * frames[f], s->frame_place_h.begin() + (size_t)12 * frames[f] + 12, store.begin() + (size_t)12 * f);
-    }
-    HIP_TRY(h, hipSetDevice(h->device));
-    void* fresh = nullptr; // the new selection is complete on the device before the one before goes
-    if (n_frames > 0) {
-        HIP_TRY(h, hipMalloc(&fresh, store.size() * sizeof(double)));
-        if (hipMemcpy(fresh, store.data(), store.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(fresh);
-            return fail(h, WBCQP_ERR_HIP, "copying the wrench frames to the device failed");
-        }
-    }
-    release_wrench_frames(*s); // (hipFree waits for whatever still reads the previous selection)
-    if (n_frames == 0) return WBCQP_OK;
-    s->wrench_alloc = fresh;
-    s->wrench_place = static_cast<const double*>(fresh);
-    s->wrench_body = reinterpret_cast<const int*>(s->wrench_place + (size_t)12 * n_frames);
-    s->n_wrench = n_frames;
-    return WBCQP_OK;
+    return set_frame_selection(h, slot, &Slot::wrench, n_frames, frames, WBCQP_MAX_WRENCH_FRAMES, "a wrench frame", "the wrench frames");
 }
 
 int wbcqp_inverse_dynamics(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench, void* tau,
                            void* stream)
 {
-    if (!h) return WBCQP_ERR_INVALID;
     const Slot* s = nullptr;
     WB_TRY(check_inverse_dynamics(h, slot, batch, q, a, lda, wrench, tau, &s));
-    if (batch == 0) return WBCQP_OK;
+    if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     return launch_inverse_dynamics(h, *s, batch, q, v, a, lda, wrench, tau, static_cast<hipStream_t>(stream));
 }
 
 int wbcqp_inverse_dynamics_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench, void* tau)
 {
-    if (!h) return WBCQP_ERR_INVALID;
     const Slot* s = nullptr;
     WB_TRY(check_inverse_dynamics(h, slot, batch, q, a, lda, wrench, tau, &s));
-    if (batch == 0) return WBCQP_OK;
+    if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv;
     // (a: rows lda apart, the last one nv long -- nothing behind it is the caller's to give)
     Arr up[4] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * nv * es, 0},
-                 {-1, const_cast<void*>(a), ((B - 1) * (size_t)(a ? lda : 0) + nv) * es, 0}, {-1, const_cast<void*>(wrench), B * s->n_wrench * 6 * es, 0}};
+                 {-1, const_cast<void*>(a), ((B - 1) * (size_t)(a ? lda : 0) + nv) * es, 0}, {-1, const_cast<void*>(wrench), B * s->wrench.n * 6 * es, 0}};
     Arr dn[1] = {{-1, tau, B * nv * es, 0}};
-    WB_TRY(stage_begin(h, lay(up, 4), lay(dn, 1), false));
-    WB_TRY(stage_up(h, h->stage_in.dev, up, 4, 0, Xfer::blocking));
-    char* din = static_cast<char*>(h->stage_in.dev);
-    char* dout = static_cast<char*>(h->stage_out.dev);
-    WB_TRY(launch_inverse_dynamics(h, *s, batch, din + up[0].off, v ? din + up[1].off : nullptr, a ? din + up[2].off : nullptr, lda,
-                                   wrench ? din + up[3].off : nullptr, dout + dn[0].off, nullptr));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return stage_down(h, dout, dn, 1, 0, Xfer::blocking);
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_inverse_dynamics(h, *s, batch, u[0], u[1], u[2], lda, u[3], d[0], nullptr);
+    });
 }
 
 int wbcqp_problem_data(wbcqp_handle* h, int slot, int batch, const wbcqp_state* st, const wbcqp_inputs* rows, void* stream)
@@ -860,18 +698,16 @@ int wbcqp_problem_data_host(wbcqp_handle* h, int slot, int batch, const wbcqp_st
     const Io host(rows, nullptr, st);
     constexpr Field kUp[3] = {F_q, F_v, F_ref};
     Arr up[3], dn[kNumRecord + 1];
-    const size_t in_bytes = lay(fb, batch, kUp, 3, host, up), out_bytes = lay(fb, batch, kRecordFields, kNumRecord + 1, host, dn);
-    WB_TRY(stage_begin(h, in_bytes, out_bytes, false));
-    WB_TRY(stage_up(h, h->stage_in.dev, up, 3, 0, Xfer::blocking));
-    Io d;
-    point(d, h->stage_in.dev, up, 3);
-    point(d, h->stage_out.dev, dn, kNumRecord + 1);
-    if (!st->momentum) d.p[F_mom] = nullptr;
-    const wbcqp_state ds = d.state();
-    const wbcqp_inputs dr = d.inputs();
-    WB_TRY(wbcqp_problem_data(h, slot, batch, &ds, &dr, nullptr));
-    HIP_TRY(h, hipDeviceSynchronize());
-    return stage_down(h, h->stage_out.dev, dn, kNumRecord + 1, 0, Xfer::blocking);
+    lay(fb, batch, kUp, 3, host, up);
+    lay(fb, batch, kRecordFields, kNumRecord + 1, host, dn);
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        Io dev;
+        for (int i = 0; i < 3; ++i) dev.p[up[i].f] = u[i];
+        for (int i = 0; i < kNumRecord + 1; ++i) dev.p[dn[i].f] = d[i];
+        const wbcqp_state ds = dev.state();
+        const wbcqp_inputs dr = dev.inputs();
+        return wbcqp_problem_data(h, slot, batch, &ds, &dr, nullptr);
+    });
 }
 
 int wbcqp_tick(wbcqp_handle* h, int slot, int batch, const wbcqp_tick_io* io, void* stream) { return tick_impl(h, slot, batch, io, stream, RollAcc{}); }

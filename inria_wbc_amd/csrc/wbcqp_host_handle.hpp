@@ -31,6 +31,14 @@ namespace {
 
 thread_local std::string g_create_error;
 
+// a selection of model frames on the device, one allocation: placement [n][12], then body [n]
+struct FrameSel {
+    int n = 0;
+    const int* body = nullptr;
+    const double* place = nullptr;
+    void* alloc = nullptr;
+};
+
 struct Slot {
     bool set = false;
     DevStruct host{};           // sizes, LDS layout and device pointers of the tables: travels by value with every launch
@@ -48,21 +56,14 @@ struct Slot {
     std::vector<double> tree;   // ... the tree as numbers (sizes, parents, joint types, placements, inertias, gravity): the slots of a mix must agree on it
     TermsDev terms{};
     std::vector<void*> model_allocs;
-    // wbcqp_observe: the model's whole frame table (host copies: only task frames reach the device with the model) and the frames chosen by
-    // wbcqp_set_observed_frames, on the device; dropped with the model
+    // the model's whole frame table (host copies: only task frames reach the device with the model) and the frames chosen from it, on the device, by
+    // wbcqp_set_observed_frames (wbcqp_observe) and wbcqp_set_wrench_frames (wbcqp_inverse_dynamics); dropped with the model
     std::vector<int> frame_body_h;
     std::vector<double> frame_place_h;
-    int n_obs = 0;
-    int* obs_body = nullptr;
-    double* obs_place = nullptr;
+    FrameSel observed, wrench;
     // wbcqp_check_collisions: the sphere table of wbcqp_set_collision_spheres, one device allocation; dropped with the model
     CollideDev spheres{};
     void* spheres_alloc = nullptr;
-    // wbcqp_inverse_dynamics: the frames chosen by wbcqp_set_wrench_frames (body and placement of each), one device allocation; dropped with the model
-    int n_wrench = 0;
-    const int* wrench_body = nullptr;
-    const double* wrench_place = nullptr;
-    void* wrench_alloc = nullptr;
 };
 
 struct Staging {
@@ -309,13 +310,10 @@ int upload(wbcqp_handle* h, Slot& s, const T* src, size_t count, const T** dst)
     return WBCQP_OK;
 }
 
-void release_observed(Slot& s)
+void release(FrameSel& f)
 {
-    if (s.obs_body) (void)hipFree(s.obs_body);
-    if (s.obs_place) (void)hipFree(s.obs_place);
-    s.obs_body = nullptr;
-    s.obs_place = nullptr;
-    s.n_obs = 0;
+    if (f.alloc) (void)hipFree(f.alloc);
+    f = FrameSel{};
 }
 
 void release_spheres(Slot& s)
@@ -323,15 +321,6 @@ void release_spheres(Slot& s)
     if (s.spheres_alloc) (void)hipFree(s.spheres_alloc);
     s.spheres_alloc = nullptr;
     s.spheres = CollideDev{};
-}
-
-void release_wrench_frames(Slot& s)
-{
-    if (s.wrench_alloc) (void)hipFree(s.wrench_alloc);
-    s.wrench_alloc = nullptr;
-    s.wrench_body = nullptr;
-    s.wrench_place = nullptr;
-    s.n_wrench = 0;
 }
 
 void release_model(Slot& s)
@@ -342,9 +331,9 @@ void release_model(Slot& s)
     s.tree.clear();
     s.frame_body_h.clear();
     s.frame_place_h.clear();
-    release_observed(s);
+    release(s.observed);
     release_spheres(s);
-    release_wrench_frames(s);
+    release(s.wrench);
 }
 
 void release(Slot& s)
@@ -514,6 +503,21 @@ int stage_down(wbcqp_handle* h, const void* dev, const Arr* a, int n, size_t blo
     }
     if (how == Xfer::async && sync) HIP_TRY(h, hipStreamSynchronize(nullptr));
     return WBCQP_OK;
+}
+
+// One staged call of a host-pointer entry point, blocking copies: the arrays of `up` go up, f(u, d) gets the device address of every array of up and of
+// dn (null where the caller's pointer is null) and launches on the null stream, the device is waited for, the arrays of dn come down
+template <int NU, int ND, typename F>
+int staged_call(wbcqp_handle* h, Arr (&up)[NU], Arr (&dn)[ND], F&& f)
+{
+    WB_TRY(stage_begin(h, lay(up, NU), lay(dn, ND), false));
+    WB_TRY(stage_up(h, h->stage_in.dev, up, NU, 0, Xfer::blocking));
+    void *u[NU], *d[ND];
+    for (int i = 0; i < NU; ++i) u[i] = up[i].host ? static_cast<char*>(h->stage_in.dev) + up[i].off : nullptr;
+    for (int i = 0; i < ND; ++i) d[i] = dn[i].host ? static_cast<char*>(h->stage_out.dev) + dn[i].off : nullptr;
+    WB_TRY(f(u, d));
+    HIP_TRY(h, hipDeviceSynchronize());
+    return stage_down(h, h->stage_out.dev, dn, ND, 0, Xfer::blocking);
 }
 
 // ---- the argument checks the entry points share ---------------------------------------------------------------------------------------------------

@@ -1,0 +1,198 @@
+// wbcqp_host_queries.hpp -- host side of the model queries on a fleet's states (wbcqp_api.hip): wbcqp_observe, wbcqp_check_collisions and
+// wbcqp_inverse_dynamics, each with the set-up call that puts its table on the slot.  Per query: ONE check_* that the device-pointer and the
+// host-pointer entry point share (nothing is staged or launched before it has passed) and ONE launch_* of its kernel (csrc/wbcqp_observe.hpp,
+// wbcqp_collide.hpp, wbcqp_rnea.hpp), one wavefront per instance.  Host code only; included by wbcqp_api.hip alone.
+#pragma once
+#include "wbcqp_host_handle.hpp"
+
+namespace {
+
+static_assert(kObservePerBlock == kRneaPerBlock, "the three query kernels hold the same number of instances per workgroup");
+static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
+
+// workgroups for `batch` instances at one wavefront each
+inline int query_blocks(int batch) { return (batch + kObservePerBlock - 1) / kObservePerBlock; }
+
+// the tree of the slot's model as the observe and the collide kernel read it, with `frames` frames of the selection (0: none are read)
+ObserveDev observe_dev(const TermsDev& T, const FrameSel& sel, bool frames)
+{
+    return ObserveDev{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_idxq, T.i_idxv, T.i_anc, T.d_place, T.d_inertia,
+                      frames ? sel.n : 0, sel.body, sel.place};
+}
+
+// ---- the tables of a slot --------------------------------------------------------------------------------------------------------------------------
+// A new table is complete on the device, in an allocation of its own, before the caller lets the one before go (a failure leaves that one in place);
+// bytes == 0: *fresh is null
+int upload_fresh(wbcqp_handle* h, const void* src, size_t bytes, const char* the_table, void** fresh)
+{
+    *fresh = nullptr;
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (bytes == 0) return WBCQP_OK;
+    HIP_TRY(h, hipMalloc(fresh, bytes));
+    if (hipMemcpy(*fresh, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(*fresh);
+        *fresh = nullptr;
+        return fail(h, WBCQP_ERR_HIP, std::string("copying ") + the_table + " to the device failed");
+    }
+    return WBCQP_OK;
+}
+
+// wbcqp_set_observed_frames / wbcqp_set_wrench_frames: frame indices -> (placement, body) of each from the slot's host copy of the model's frame table;
+// n_frames == 0 drops the selection
+int set_frame_selection(wbcqp_handle* h, int slot, FrameSel Slot::*which, int n_frames, const int32_t* frames, int limit, const char* a_frame,
+                        const char* the_frames)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (n_frames < 0 || n_frames > limit) return fail(h, WBCQP_ERR_INVALID, "n_frames must be in [0, " + std::to_string(limit) + "]");
+    if (n_frames > 0 && !frames) return fail(h, WBCQP_ERR_INVALID, "frames is NULL");
+    const int nframe = (int)s->frame_body_h.size();
+    std::vector<double> store((size_t)12 * n_frames + ((size_t)n_frames + 1) / 2);
+    int* body = reinterpret_cast<int*>(store.data() + (size_t)12 * n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        if (frames[f] < 0 || frames[f] >= nframe) return fail(h, WBCQP_ERR_INVALID, std::string(a_frame) + " does not exist in the slot's model");
+        body[f] = s->frame_body_h[frames[f]];
+        std::copy(s->frame_place_h.begin() + (size_t)12 * frames[f], s->frame_place_h.begin() + (size_t)12 * frames[f] + 12, store.begin() + (size_t)12 * f);
+    }
+    void* fresh = nullptr;
+    WB_TRY(upload_fresh(h, store.data(), store.size() * sizeof(double), the_frames, &fresh));
+    FrameSel& sel = s->*which;
+    release(sel); // (hipFree waits for whatever still reads the previous selection)
+    if (n_frames == 0) return WBCQP_OK;
+    const double* place = static_cast<const double*>(fresh);
+    sel = FrameSel{n_frames, reinterpret_cast<const int*>(place + (size_t)12 * n_frames), place, fresh};
+    return WBCQP_OK;
+}
+
+int set_collision_spheres(wbcqp_handle* h, int slot, const wbcqp_sphere_model* sm)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    if (!sm) return fail(h, WBCQP_ERR_INVALID, "sphere model is NULL");
+    const int n = sm->n_spheres;
+    if (n < 0 || n > WBCQP_MAX_SPHERES) return fail(h, WBCQP_ERR_INVALID, "n_spheres must be in [0, 256]");
+    if (n > 0 && (!sm->body || !sm->member || !sm->centre || !sm->diameter)) return fail(h, WBCQP_ERR_INVALID, "body / member / centre / diameter is NULL");
+    // one allocation: centre [n][3] doubles, then body, tag (member << 8 | place inside the member) and half-diameter, 4 bytes each
+    std::vector<double> store(((size_t)n * (24 + 12) + 7) / 8); // (doubles: the block's alignment is the centres')
+    char* blob = reinterpret_cast<char*>(store.data());
+    double* centre = store.data();
+    int* body = reinterpret_cast<int*>(blob + (size_t)24 * n);
+    int* tag = body + n;
+    float* half = reinterpret_cast<float*>(tag + n);
+    for (int i = 0, place = 0; i < n; ++i) {
+        if (sm->body[i] < 0 || sm->body[i] >= s->terms.nb) return fail(h, WBCQP_ERR_INVALID, "a sphere's body is outside the slot's tree");
+        if (sm->member[i] < 0 || sm->member[i] >= WBCQP_MAX_MEMBERS) return fail(h, WBCQP_ERR_INVALID, "a sphere's member must be in [0, 16)");
+        if (i > 0 && sm->member[i] < sm->member[i - 1]) return fail(h, WBCQP_ERR_INVALID, "member must be non-decreasing (spheres sorted by member)");
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(sm->centre[3 * i + k])) return fail(h, WBCQP_ERR_INVALID, "a sphere's centre is not finite");
+        if (!std::isfinite(sm->diameter[i]) || !(sm->diameter[i] > 0.0f)) return fail(h, WBCQP_ERR_INVALID, "a sphere's diameter must be finite and > 0");
+        place = (i > 0 && sm->member[i] == sm->member[i - 1]) ? place + 1 : 0;
+        body[i] = sm->body[i];
+        tag[i] = (sm->member[i] << 8) | place;
+        half[i] = sm->diameter[i] / 2; // a float division, as the reference's sphere.second / 2
+        std::copy(sm->centre + 3 * i, sm->centre + 3 * i + 3, centre + 3 * i);
+    }
+    void* fresh = nullptr;
+    WB_TRY(upload_fresh(h, blob, (size_t)n * (24 + 12), "the sphere table", &fresh));
+    release_spheres(*s); // (hipFree waits for whatever still reads the previous table)
+    if (n == 0) return WBCQP_OK;
+    s->spheres_alloc = fresh;
+    const int* dbody = reinterpret_cast<const int*>(static_cast<char*>(fresh) + (size_t)24 * n);
+    s->spheres = CollideDev{n, dbody, dbody + n, static_cast<const double*>(fresh), reinterpret_cast<const float*>(dbody + 2 * n)};
+    return WBCQP_OK;
+}
+
+// ---- the checks: what the device-pointer and the host-pointer entry point of a query refuse, before anything is staged or launched ----------------
+// *s: the slot, or null where the call is accepted and there is nothing to do (batch == 0, no output asked for)
+int check_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "observables struct is NULL");
+    if ((out->placement || out->velocity) && sl->observed.n == 0)
+        return fail(h, WBCQP_ERR_INVALID, "placement / velocity asked for, but no frames are selected (wbcqp_set_observed_frames)");
+    if ((out->vcom || out->velocity) && !v) return fail(h, WBCQP_ERR_INVALID, "vcom / velocity asked for, but v is NULL");
+    if (batch == 0 || (!out->com && !out->vcom && !out->placement && !out->velocity)) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    *s = sl;
+    return WBCQP_OK;
+}
+
+int check_collisions(wbcqp_handle* h, int slot, int batch, const void* q, const wbcqp_collisions* out, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (sl->spheres.n_spheres == 0) return fail(h, WBCQP_ERR_INVALID, "slot has no sphere table (wbcqp_set_collision_spheres)");
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "collisions struct is NULL");
+    if (batch == 0 || (!out->colliding && !out->first_pair && !out->n_pairs && !out->clearance && !out->centres)) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    *s = sl;
+    return WBCQP_OK;
+}
+
+int check_inverse_dynamics(wbcqp_handle* h, int slot, int batch, const void* q, const void* a, int lda, const void* wrench, const void* tau, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!q || !tau) return fail(h, WBCQP_ERR_INVALID, "q and tau are required");
+    if (a && lda < sl->terms.nv) return fail(h, WBCQP_ERR_INVALID, "lda must be at least nv");
+    if (wrench && sl->wrench.n == 0) return fail(h, WBCQP_ERR_INVALID, "wrench given, but no frames are selected (wbcqp_set_wrench_frames)");
+    if (batch > 0) *s = sl;
+    return WBCQP_OK;
+}
+
+// ---- the launches: batch > 0, arguments checked, the handle's device current ---------------------------------------------------------------------
+int launch_observe(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, const wbcqp_observables& out, hipStream_t stream)
+{
+    const ObserveDev D = observe_dev(s.terms, s.observed, out.placement || out.velocity);
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const ObserveArgs<TI> a{D, static_cast<const TI*>(q), (out.vcom || out.velocity) ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out.com),
+                                static_cast<TI*>(out.vcom), static_cast<TI*>(out.placement), static_cast<TI*>(out.velocity), batch};
+        hipLaunchKernelGGL(observe_kernel<TI>, dim3(query_blocks(batch)), dim3(kObserveThreads), observe_lds_bytes(D.n_frames), stream, a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+int launch_collisions(wbcqp_handle* h, const Slot& s, int batch, const void* q, const wbcqp_collisions& out, hipStream_t stream)
+{
+    const ObserveDev D = observe_dev(s.terms, FrameSel{}, false);
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const CollideArgs<TI> a{D, s.spheres, static_cast<const TI*>(q), out.colliding, out.first_pair, out.n_pairs, static_cast<TI*>(out.clearance),
+                                static_cast<TI*>(out.centres), batch};
+        hipLaunchKernelGGL(collide_kernel<TI>, dim3(query_blocks(batch)), dim3(kObserveThreads), collide_lds_bytes(s.spheres.n_spheres), stream, a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+int launch_inverse_dynamics(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench, void* tau,
+                            hipStream_t stream)
+{
+    const TermsDev& T = s.terms;
+    const RneaDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, {T.g[0], T.g[1], T.g[2]}, T.ipool, T.dpool, T.i_jtype, T.i_last, T.i_idxq, T.i_idxv, T.i_anc,
+                    T.i_bodyof, T.i_kof, T.d_place, T.d_inertia, wrench ? s.wrench.n : 0, s.wrench.body, s.wrench.place};
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const RneaArgs<TI> args{D, static_cast<const TI*>(q), static_cast<const TI*>(v), static_cast<const TI*>(a), static_cast<const TI*>(wrench),
+                                static_cast<TI*>(tau), a ? lda : 0, batch};
+        hipLaunchKernelGGL(rnea_kernel<TI>, dim3(query_blocks(batch)), dim3(kRneaThreads), 0, stream, args);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+} // namespace

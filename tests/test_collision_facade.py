@@ -7,14 +7,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import model_queries as mq
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "talos_collisions.yaml")
 
 
 @pytest.fixture(scope="module")
 def host_build(built_lib):
-    from inria_wbc_amd import build
-    return build.build_host()
+    return mq.host_build()
 
 
 @pytest.mark.gpu
@@ -57,11 +58,5 @@ def test_one_of_eight_robots_collides_and_stops_sending(host_build, tmp_path):
 
 @pytest.mark.gpu
 def test_a_source_without_a_model_is_refused(host_build, tmp_path):
-    from tools import dump_batch
-    from inria_wbc_amd import structure, synth
-    st = structure.talos_structure()
-    path = str(tmp_path / "b.bin")
-    dump_batch.dump(path, st, synth.generate(st, 2, synth.SEED_BASE["talos"]))
-    r = subprocess.run([host_build["collision_facade_test"], "--file-source", os.path.join(ROOT, "configs/talos/pos_tracker.yaml"), FIXTURE, path],
-                       capture_output=True, text=True, timeout=120)
+    r = mq.run_file_source(host_build["collision_facade_test"], tmp_path, FIXTURE)
     assert r.returncode == 0 and "refused: 1" in r.stdout and "check_model_collisions" in r.stdout, r.stdout + r.stderr

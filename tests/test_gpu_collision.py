@@ -7,12 +7,15 @@ TIE = 1e-9 of its threshold in the numpy statement (ten times TOL_ROWS: a centre
 tables and states below are chosen so that NO state is excluded and both outcomes occur; each test asserts that of its own inputs, so the exclusion
 can never hide a failure.  clearance is a difference of two such distances' worth of error: 4 TOL_ROWS."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-from inria_wbc_amd import capi, collision, refprog, structure
+from inria_wbc_amd import capi, collision, structure
 from inria_wbc_amd import model as mdl
+from tests import model_queries as mq
+from tests.model_queries import UNSET, _torch
 from tests.test_collision_host import FIXTURE, ordering_case, random_table
 
 pytestmark = pytest.mark.gpu
@@ -21,19 +24,6 @@ TOL_ROWS = 1e-10
 TIE = 1e-9
 FIELDS = capi.COLLISIONS
 INTS = ("colliding", "first_pair", "n_pairs")
-GUARD = 16  # elements behind every output buffer that must stay untouched
-UNSET = -77
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _minimal(m):
-    """The smallest stack a slot accepts for `m`: one SE(3) task on frame 0 (the check needs the tree, not the tasks)."""
-    st = structure._mk("collide_" + m.name, m.nv, m.na, [], [("a", 3, 1.0)], None, [], False, False, [])
-    return st, mdl.build_taskmap(m, st, [dict(name="a", type="se3", tracked=m.frame_names[0], kp=10.0, mask="111000")])
 
 
 def _states(m, n, seed, noise=0.5):
@@ -64,12 +54,7 @@ def _width(k, ns):
 
 
 def _bufs(B, ns, td, dev, torch, which=FIELDS):
-    out = {}
-    for k in which:
-        n = B * _width(k, ns)
-        whole = torch.full((n + GUARD,), UNSET, dtype=torch.int32, device=dev) if k in INTS else torch.full((n + GUARD,), float("nan"), dtype=td, device=dev)
-        out[k] = (whole, whole[:n])
-    return out
+    return {k: mq.guarded(B * _width(k, ns), torch.int32 if k in INTS else td, dev, torch) for k in which}
 
 
 def _check(h, slot, B, ns, q, dev, torch, which=FIELDS, td=None):
@@ -78,17 +63,8 @@ def _check(h, slot, B, ns, q, dev, torch, which=FIELDS, td=None):
     bufs = _bufs(B, ns, td, dev, torch, which)
     h.check_collisions(slot, B, q[:B].contiguous(), stream=torch.cuda.current_stream().cuda_stream, **{k: b[1] for k, b in bufs.items()})
     torch.cuda.synchronize()
-    res = {}
-    for k, (whole, part) in bufs.items():
-        a, n = whole.cpu().numpy(), part.numel()
-        if k in INTS:
-            assert (a[n:] == UNSET).all(), (k, "written past the end")
-            assert (a[:n] != UNSET).all(), (k, "an element was not written")
-        else:
-            assert np.isnan(a[n:]).all(), (k, "written past the end")
-            assert not np.isnan(a[:n]).any(), (k, "an element was not written")
-        res[k] = a[:n].reshape({"first_pair": (B, 2), "centres": (B, ns, 3)}.get(k, (B,)))
-    return res
+    return {k: mq.read_guarded(whole, part.numel(), k, finite=False).reshape({"first_pair": (B, 2), "centres": (B, ns, 3)}.get(k, (B,)))
+            for k, (whole, part) in bufs.items()}  # (finite=False: a clearance of +inf is an answer)
 
 
 def _agree(got, want, table, what):
@@ -107,13 +83,11 @@ def _agree(got, want, table, what):
 
 @pytest.fixture(scope="module")
 def handle():
-    h = capi.Handle(0, capi.F64)
-    yield h
-    h.close()
+    yield from mq.open_handle()
 
 
 def _bind(h, slot, m):
-    st, tm = _minimal(m)
+    st, tm = mq.minimal(m, "collide_")
     h.set_structure(slot, st)
     h.set_model(slot, m, tm)
     return st, tm
@@ -191,9 +165,7 @@ def test_first_pair_follows_the_reference_loops(handle):
     assert collision.pair_names(t, got["first_pair"][0]) == (("A", 1), ("B", 0))
 
 
-def _talos():
-    m, st = mdl.talos_like(), structure.talos_structure()
-    return m, st, mdl.build_taskmap(m, st, mdl.talos_stack())
+_talos = mq.talos_case
 
 
 def _talos_states(m, tm):
@@ -233,13 +205,8 @@ def test_same_bits_on_two_launches_and_at_any_place_in_a_batch(handle):
     t = random_table(m, 128, 16, 3, dmin=0.005, dmax=0.03)
     handle.set_collision_spheres(3, t)
     q = torch.from_numpy(_states(m, 67, 8200)).to(dev)
-    a = _check(handle, 3, 67, 128, q, dev, torch)
-    b = _check(handle, 3, 67, 128, q, dev, torch)
-    c = _check(handle, 3, 6, 128, q[10:16], dev, torch)  # rows 10 .. 15 as a batch of their own: other waves, other workgroups
-    assert 0 < a["colliding"].sum() < 67
-    for k in FIELDS:
-        assert np.array_equal(a[k], b[k]), k
-        assert np.array_equal(a[k][10:16], c[k]), k
+    a = mq.same_bits_on_two_launches_and_at_any_place_in_a_batch(lambda lo, hi: _check(handle, 3, hi - lo, 128, q[lo:hi], dev, torch), 67)
+    assert set(a) == set(FIELDS) and 0 < a["colliding"].sum() < 67
 
 
 def test_f32_handle(handle):
@@ -292,49 +259,21 @@ def test_each_output_is_optional_and_independent(handle):
 
 
 def test_nothing_else_moves(handle):
-    m, st, tm = _talos()
-    handle.set_structure(3, st)
-    handle.set_model(3, m, tm)
-    B = 6
-    s = mdl.sample_states(m, tm, B, 77_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
-    tlb, tub, w = np.tile(-m.tau_max, (B, 1)), np.tile(m.tau_max, (B, 1)), np.tile(st.default_weights, (B, 1))
-    handle.set_observed_frames(3, [0, 5])
-    rows0 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
-    tick0 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
-    obs0 = handle.observe_host(3, s["q"], s["v"])
-    handle.set_collision_spheres(3, collision.sphere_table(m, FIXTURE))
-    handle.check_collisions_host(3, s["q"])
-    rows1 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
-    tick1 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
-    obs1 = handle.observe_host(3, s["q"], s["v"])  # (the selection of frames stands)
-    for a, b in ((rows0, rows1), (tick0, tick1), (obs0, obs1)):
-        for k in a:
-            assert np.array_equal(a[k], b[k]), k
-    assert (tick0["status"] == 0).all()
+    case = _talos()
+
+    def query(s, tick):
+        handle.set_collision_spheres(3, collision.sphere_table(case[0], FIXTURE))
+        handle.check_collisions_host(3, s["q"])
+
+    mq.nothing_else_moves(handle, case, 77_000, query, observed=[0, 5])
 
 
 def test_a_traced_rollouts_q_in_one_call():
     torch, dev = _torch()
     B, K = 4, 8
-    m, st, tm = _talos()
-    s = mdl.sample_states(m, tm, B, 97_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
-    com = next(b for b in tm.blocks if b.kind == mdl.T_COM)
-    prog = refprog.move_com_program(tm.nref, com.ref, m.com(m.q0), [[0.0, 0.0, -0.2]], "001", tm.dt, 2.0, loop=True, absolute=False)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    lim = dict(w=up(np.tile(st.default_weights, (B, 1))), tlb=up(np.tile(-m.tau_max, (B, 1))), tub=up(np.tile(m.tau_max, (B, 1))))
-    h = capi.Handle(0, capi.F64)
+    t = collision.sphere_table(mdl.talos_like(), FIXTURE)
+    h, m, _, _, trace, _, _ = mq.traced_squat(B, K, 1, lambda h, m, tm: h.set_collision_spheres(0, t))
     try:
-        h.set_structure(0, st)
-        h.set_model(0, m, tm)
-        t = collision.sphere_table(m, FIXTURE)
-        h.set_collision_spheres(0, t)
-        stream = torch.cuda.current_stream().cuda_stream
-        ref = h.reference_samples(prog, up(s["ref"]), -37 * np.arange(B), 0, K, torch.zeros(K, B, tm.nref, dtype=torch.float64, device=dev), stream=stream)
-        f = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)  # noqa: E731
-        out = dict(x=f(B, st.n), tau=f(B, st.na), status=torch.full((B,), -99, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev))
-        trace = dict(q=f(K, B, m.nq), v=f(K, B, m.nv))
-        h.rollout_traced(0, B, K, dict(q=up(s["q"]), v=up(s["v"]), ref=ref), lim, out, f(B, m.nq), f(B, m.nv), tm.dt, trace=trace, stride=1, stream=stream)
-        torch.cuda.synchronize()
         whole = _check(h, 0, K * B, t.n_spheres, trace["q"].reshape(K * B, -1), dev, torch)
         for r in range(K):
             tick = _check(h, 0, B, t.n_spheres, trace["q"][r], dev, torch)
@@ -359,11 +298,7 @@ def test_refusals_come_before_any_launch():
         ptr = {k: b[1].data_ptr() for k, b in bufs.items()}
         stream = torch.cuda.current_stream().cuda_stream
 
-        def refused(call):
-            with pytest.raises(capi.WbcqpError) as e:
-                call()
-            assert e.value.code == 1, e.value  # WBCQP_ERR_INVALID
-            assert (h.lib.wbcqp_last_error(h._h) or b"").decode().strip(), "no message in wbcqp_last_error"
+        refused = functools.partial(mq.refused, h)
 
         def raw_check(slot, batch, qp, **out):
             o = capi.CCollisions(*[out.get(k) for k in FIELDS])
@@ -406,12 +341,41 @@ def test_refusals_come_before_any_launch():
         raw_check(0, 0, q.data_ptr(), **ptr)  # batch == 0: WBCQP_OK, nothing launched
         torch.cuda.synchronize()
         for k, (whole, _) in bufs.items():
-            a = whole.cpu().numpy()
-            assert (a == UNSET).all() if k in INTS else np.isnan(a).all(), (k, "a refused call wrote something")
+            assert mq.unwritten(whole.cpu().numpy()).all(), (k, "a refused call wrote something")
         got = _check(h, 0, B, ns, q, dev, torch)  # and the table still stands
         _agree(got, collision.check(m, t, q.cpu().numpy()), t, "after the refusals")
     finally:
         h.close()
+
+
+def _talos_both(handle, B=4):
+    """Talos on slot 3 of the module's handle (no sphere table yet), its table; B states and prefilled outputs, each as a (device, host) pair."""
+    m, st, tm = _talos()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    t = collision.sphere_table(m, FIXTURE)
+    out = {k: mq.prefilled_both(B * _width(k, t.n_spheres), k in INTS) for k in FIELDS}
+    return t, mq.both(np.ascontiguousarray(_talos_states(m, tm)[:B])), out, mq.Out(capi.CCollisions, **out)
+
+
+def test_host_refusals_are_the_device_refusals(handle):
+    t, q, out, O = _talos_both(handle)
+    mq.host_refusals_match(handle, "check_collisions", [(3, 4, q, O)], out.values())  # a slot without a sphere table: never set,
+    handle.set_collision_spheres(3, t)
+    handle.set_collision_spheres(3, None)
+    mq.host_refusals_match(handle, "check_collisions", [(3, 4, q, O)], out.values())  # and dropped by an empty one
+    handle.set_collision_spheres(3, t)
+    mq.host_refusals_match(handle, "check_collisions", [(3, -1, q, O),    # a negative batch
+                                                        (3, 4, None, O),  # q NULL
+                                                        (3, 4, q, None),  # no struct of outputs
+                                                        (9, 4, q, O)],    # a slot without a model
+                           out.values())
+
+
+def test_batch_zero_through_the_host_entry_point(handle):
+    t, q, out, O = _talos_both(handle)
+    handle.set_collision_spheres(3, t)
+    mq.host_batch_zero(handle, "check_collisions", [(3, 0, q, O), (3, 0, None, O)], out.values())  # (q is not looked at)
 
 
 def test_set_structure_and_set_model_drop_the_table():
@@ -427,17 +391,11 @@ def test_set_structure_and_set_model_drop_the_table():
         h.set_model(0, m, tm)
         h.set_collision_spheres(0, t)
         assert h.check_collisions_host(0, qn)["centres"].shape == (3, 20, 3)
-        for again in ("structure", "model"):
-            if again == "structure":
-                h.set_structure(0, st)
-            h.set_model(0, m, tm)
-            buf = torch.full((3,), UNSET, dtype=torch.int32, device=dev)
-            with pytest.raises(capi.WbcqpError) as e:
-                h.check_collisions(0, 3, torch.from_numpy(qn).to(dev), colliding=buf)
-            assert e.value.code == 1 and "no sphere table" in str(e.value)
-            torch.cuda.synchronize()
-            assert (buf == UNSET).all().item()
+        def and_then():
             h.set_collision_spheres(0, t)
             assert np.array_equal(h.check_collisions_host(0, qn)["colliding"], collision.check(m, t, qn)["colliding"])
+
+        mq.set_structure_and_set_model_drop(h, (m, st, tm), lambda: torch.full((3,), UNSET, dtype=torch.int32, device=dev),
+                                            lambda buf: h.check_collisions(0, 3, torch.from_numpy(qn).to(dev), colliding=buf), "no sphere table", and_then)
     finally:
         h.close()

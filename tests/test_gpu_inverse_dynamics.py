@@ -10,57 +10,34 @@ the four instances of a workgroup.
 The audit identity (a solved tick's inverse dynamics is zero on the base rows and the decoded tau on the actuated rows) is held to AUDIT_TOL
 of tests/test_inverse_dynamics_host.py: ten times the worst residual measured there with the oracle's own tick (7.65e-11 over 64 states)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-from inria_wbc_amd import capi, refprog, structure
+from inria_wbc_amd import capi
 from inria_wbc_amd import model as mdl
+from tests import model_queries as mq
+from tests.model_queries import BATCHES, _torch
 from tests.test_inverse_dynamics_host import AUDIT_TOL, audit_residual, contact_wrenches, talos_audit_case
 
 pytestmark = pytest.mark.gpu
 
 TOL_ROWS = 1e-10
 TOL_F32 = 1e-6
-BATCHES = (1, 3, 5, 67)
 NMAX = max(BATCHES)
-GUARD = 16  # elements behind the output buffer that must stay untouched
 PAD = 13    # lda = nv + PAD in the padded mode
 
 
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _minimal(m):
-    """The smallest stack a slot accepts for `m`: one SE(3) task on frame 0 (inverse dynamics needs the tree, not the tasks)."""
-    st = structure._mk("rnea_" + m.name, m.nv, m.na, [], [("a", 3, 1.0)], None, [], False, False, [])
-    return st, mdl.build_taskmap(m, st, [dict(name="a", type="se3", tracked=m.frame_names[0], kp=10.0, mask="111000")])
-
-
 def _tree(seed, nb, fb, shape=None):
-    def f():
-        m = mdl.random_tree(seed, nb, fb, nframe=12)
-        if shape == "chain":  # depth nb - 1: every doubling round moves something
-            m.parent = np.arange(-1, nb - 1, dtype=np.int32)
-        if shape == "star":   # every body but the root is a leaf: every subtree but the root's is one lane
-            m.parent = np.array([-1] + [0] * (nb - 1), dtype=np.int32)
-        m.frame_body[0], m.frame_body[1] = 0, nb - 1  # a frame on body 0, a frame on the last body
-        m.frame_body[3] = m.frame_body[2]             # two frames on one body
-        m.validate()
-        return (m,) + _minimal(m)
-    return f
+    return mq.tree_case("rnea_", seed, nb, fb, shape, two_on_one_body=True)
 
 
 CASES = {"one_body_fixed": _tree(61, 1, False), "tree_64_fixed_lane_limit": _tree(62, 64, False), "tree_59_floating_nv_limit": _tree(63, 59, True),
          "chain_62": _tree(64, 62, False, "chain"), "star_17_floating": _tree(65, 17, True, "star"), "tree_24_floating": _tree(66, 24, True)}
 
 
-def _talos():
-    m = mdl.talos_like()
-    st = structure.talos_structure()
-    return m, st, mdl.build_taskmap(m, st, mdl.talos_stack())
+_talos = mq.talos_case
 
 
 def _states(m, tm, n, seed):
@@ -105,7 +82,7 @@ def _run(h, slot, B, nv, q, v, a, wrench, mode, torch, dev, td=None):
     """One launch on device tensors -> tau [B, nv] as numpy; every element is written, nothing behind the end is touched.  a: [N, nv + PAD]
     with NaN in the padding; the modes pass it whole (lda = nv + PAD), as a contiguous copy of its first nv columns (lda = nv), or not at all."""
     td = td or torch.float64
-    whole = torch.full((B * nv + GUARD,), float("nan"), dtype=td, device=dev)
+    whole, part = mq.guarded(B * nv, td, dev, torch)
     vv = None if mode in ("v_a_null", "v_null") else v[:B].contiguous()
     if mode in ("a_null", "v_a_null"):
         aa, lda = None, 0
@@ -113,13 +90,10 @@ def _run(h, slot, B, nv, q, v, a, wrench, mode, torch, dev, td=None):
         aa, lda = a[:B], nv + PAD
     else:
         aa, lda = a[:B, :nv].contiguous(), nv
-    h.inverse_dynamics(slot, B, q[:B].contiguous(), whole[:B * nv], v=vv, a=aa, lda=lda, wrench=None if wrench is None else wrench[:B].contiguous(),
+    h.inverse_dynamics(slot, B, q[:B].contiguous(), part, v=vv, a=aa, lda=lda, wrench=None if wrench is None else wrench[:B].contiguous(),
                        stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    out = whole.cpu().numpy()
-    assert np.isnan(out[B * nv:]).all(), "written past the end"
-    assert np.isfinite(out[:B * nv]).all(), "an element was not written"
-    return out[:B * nv].reshape(B, nv)
+    return mq.read_guarded(whole, B * nv, "tau").reshape(B, nv)
 
 
 def _rel(got, want):
@@ -136,9 +110,7 @@ def _padded(a, torch, dev, td=None):
 
 @pytest.fixture(scope="module")
 def handle():
-    h = capi.Handle(0, capi.F64)
-    yield h
-    h.close()
+    yield from mq.open_handle()
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -205,10 +177,8 @@ def test_same_bits_on_two_launches_and_at_any_place_in_a_batch(handle):
     qn, vn, an = _states(m, tm, NMAX, 84_000)
     wn = 50.0 * np.random.default_rng(84_500).standard_normal((NMAX, 8, 6))
     q, v, a, w = torch.from_numpy(qn).to(dev), torch.from_numpy(vn).to(dev), _padded(an, torch, dev), torch.from_numpy(wn).to(dev)
-    x = _run(handle, 3, NMAX, m.nv, q, v, a, w, "full", torch, dev)
-    y = _run(handle, 3, NMAX, m.nv, q, v, a, w, "full", torch, dev)
-    z = _run(handle, 3, 6, m.nv, q[10:16], v[10:16], a[10:16], w[10:16], "full", torch, dev)  # rows 10 .. 15 as a batch of their own: other waves, other workgroups
-    assert np.array_equal(x, y) and np.array_equal(x[10:16], z)
+    mq.same_bits_on_two_launches_and_at_any_place_in_a_batch(
+        lambda lo, hi: {"tau": _run(handle, 3, hi - lo, m.nv, q[lo:hi], v[lo:hi], a[lo:hi], w[lo:hi], "full", torch, dev)}, NMAX)
 
 
 def test_f32_handle_rounds_the_f64_result(handle):
@@ -240,25 +210,11 @@ def test_f32_handle_rounds_the_f64_result(handle):
 
 
 def test_nothing_else_moves(handle):
-    m, st, tm = _talos()
-    handle.set_structure(3, st)
-    handle.set_model(3, m, tm)
-    B = 6
-    s = mdl.sample_states(m, tm, B, 86_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
-    tlb, tub, w = np.tile(-m.tau_max, (B, 1)), np.tile(m.tau_max, (B, 1)), np.tile(st.default_weights, (B, 1))
-    handle.set_observed_frames(3, [1, 4, 9])
-    rows0 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
-    tick0 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
-    obs0 = handle.observe_host(3, s["q"], s["v"])
-    handle.set_wrench_frames(3, list(range(8)))
-    handle.inverse_dynamics_host(3, s["q"], s["v"], tick0["x"], np.ones((B, 8, 6)))
-    rows1 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
-    tick1 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
-    obs1 = handle.observe_host(3, s["q"], s["v"])
-    for before, after in ((rows0, rows1), (tick0, tick1), (obs0, obs1)):
-        for k in before:
-            assert np.array_equal(before[k], after[k]), k
-    assert (tick0["status"] == 0).all()
+    def query(s, tick):
+        handle.set_wrench_frames(3, list(range(8)))
+        handle.inverse_dynamics_host(3, s["q"], s["v"], tick["x"], np.ones((6, 8, 6)))
+
+    mq.nothing_else_moves(handle, _talos(), 86_000, query, observed=[1, 4, 9])
 
 
 def test_refusals_come_before_any_launch():
@@ -270,14 +226,9 @@ def test_refusals_come_before_any_launch():
         qn, vn, an = _states(m, tm, B, 87_000)
         wn = np.ones((B, 2, 6))
         q, v, a, w = (torch.from_numpy(t).to(dev) for t in (qn, vn, an, wn))
-        tau = torch.full((B * nv + GUARD,), float("nan"), dtype=torch.float64, device=dev)
+        tau, _ = mq.guarded(B * nv, torch.float64, dev, torch)
         stream = torch.cuda.current_stream().cuda_stream
-
-        def refused(call):
-            with pytest.raises(capi.WbcqpError) as e:
-                call()
-            assert e.value.code == 1, e.value  # WBCQP_ERR_INVALID
-            assert (h.lib.wbcqp_last_error(h._h) or b"").decode().strip(), "no message in wbcqp_last_error"
+        refused = functools.partial(mq.refused, h)
 
         def raw_set(slot, n, arr):
             h._check(h.lib.wbcqp_set_wrench_frames(h._h, slot, n, arr.ctypes.data_as(capi.c_i32_p) if arr is not None else None))
@@ -323,6 +274,42 @@ def test_refusals_come_before_any_launch():
         h.close()
 
 
+def _talos_both(handle, seed, B=4):
+    """Talos on slot 3 of the module's handle (no wrench frames yet); B states, wrenches at two frames and a prefilled tau, each as a (device, host) pair."""
+    m, st, tm = _talos()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    return (m,) + tuple(mq.both(t) for t in _states(m, tm, B, seed) + (np.ones((B, 2, 6)),)) + (mq.prefilled_both(B * m.nv),)
+
+
+def test_a_refused_selection_keeps_the_one_before(handle):
+    m, (_, qn), (_, vn), (_, an), (_, wn), _ = _talos_both(handle, 87_100)
+
+    def still_stands(frames):
+        assert _rel(handle.inverse_dynamics_host(3, qn, vn, an, wn), Oracle(m, qn, vn, an).tau("full", frames, wn)) <= TOL_ROWS
+
+    mq.a_refused_selection_keeps_the_one_before(handle, "wrench", m.nframe, 8, still_stands)
+
+
+def test_host_refusals_are_the_device_refusals(handle):
+    m, q, v, a, w, tau = _talos_both(handle, 87_200)
+    nv = m.nv
+    mq.host_refusals_match(handle, "inverse_dynamics", [(3, 4, q, v, a, nv, w, tau)], [tau])  # a wrench while no frames are selected
+    handle.set_wrench_frames(3, [3, 5])
+    mq.host_refusals_match(handle, "inverse_dynamics", [(3, -1, q, v, a, nv, w, tau),     # a negative batch
+                                                        (3, 4, None, v, a, nv, w, tau),   # q NULL
+                                                        (3, 4, q, v, a, nv, w, None),     # tau NULL
+                                                        (3, 4, q, v, a, nv - 1, w, tau),  # lda < nv with a given
+                                                        (9, 4, q, v, a, nv, None, tau)],  # a slot without a model
+                           [tau])
+
+
+def test_batch_zero_through_the_host_entry_point(handle):
+    m, q, v, a, w, tau = _talos_both(handle, 87_300)
+    handle.set_wrench_frames(3, [3, 5])
+    mq.host_batch_zero(handle, "inverse_dynamics", [(3, 0, q, v, a, m.nv, w, tau), (3, 0, q, None, None, 0, None, tau)], [tau])
+
+
 def test_set_structure_and_set_model_drop_the_selection():
     torch, dev = _torch()
     m, st, tm = CASES["tree_24_floating"]()
@@ -334,19 +321,14 @@ def test_set_structure_and_set_model_drop_the_selection():
         h.set_model(0, m, tm)
         h.set_wrench_frames(0, [1, 2])
         with_w = h.inverse_dynamics_host(0, qn, vn, an, wn)
-        for again in ("structure", "model"):
-            if again == "structure":
-                h.set_structure(0, st)
-            h.set_model(0, m, tm)
-            buf = torch.full((3 * m.nv,), float("nan"), dtype=torch.float64, device=dev)
-            with pytest.raises(capi.WbcqpError) as e:
-                h.inverse_dynamics(0, 3, torch.from_numpy(qn).to(dev), buf, wrench=torch.from_numpy(wn).to(dev))
-            assert e.value.code == 1 and "no frames" in str(e.value)
-            torch.cuda.synchronize()
-            assert torch.isnan(buf).all().item()
+        def and_then():
             assert not np.array_equal(h.inverse_dynamics_host(0, qn, vn, an), with_w)  # without wrenches no selection is needed
             h.set_wrench_frames(0, [1, 2])
             assert np.array_equal(h.inverse_dynamics_host(0, qn, vn, an, wn), with_w)
+
+        mq.set_structure_and_set_model_drop(h, (m, st, tm), lambda: torch.full((3 * m.nv,), float("nan"), dtype=torch.float64, device=dev),
+                                            lambda buf: h.inverse_dynamics(0, 3, torch.from_numpy(qn).to(dev), buf, wrench=torch.from_numpy(wn).to(dev)),
+                                            "no frames", and_then)
     finally:
         h.close()
 
@@ -374,30 +356,13 @@ def test_audit_of_a_traced_squat():
     with entry r - 1's state (entry 0's with the initial state): paired so, the audit identity holds on every recorded tick."""
     torch, dev = _torch()
     B, K = 8, 12
-    m, st, tm = _talos()
-    s = mdl.sample_states(m, tm, B, 97_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
-    com = next(b for b in tm.blocks if b.kind == mdl.T_COM)
-    prog = refprog.move_com_program(tm.nref, com.ref, m.com(m.q0), [[0.0, 0.0, -0.2]], "001", tm.dt, 2.0, loop=True, absolute=False)
-    up = lambda t: torch.from_numpy(np.ascontiguousarray(t)).to(dev)  # noqa: E731
-    lim = dict(w=up(np.tile(st.default_weights, (B, 1))), tlb=up(np.tile(-m.tau_max, (B, 1))), tub=up(np.tile(m.tau_max, (B, 1))))
-    q0, v0 = up(s["q"]), up(s["v"])
-    h = capi.Handle(0, capi.F64)
+    h, m, st, tm, trace, q0, v0 = mq.traced_squat(B, K, 1, lambda h, m, tm: h.set_wrench_frames(0, tm.contact_frame), more=("x", "tau", "status"))
     try:
-        h.set_structure(0, st)
-        h.set_model(0, m, tm)
-        h.set_wrench_frames(0, tm.contact_frame)
-        stream = torch.cuda.current_stream().cuda_stream
-        ref = h.reference_samples(prog, up(s["ref"]), -37 * np.arange(B), 0, K, torch.zeros(K, B, tm.nref, dtype=torch.float64, device=dev), stream=stream)
-        f = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)  # noqa: E731
-        out = dict(x=f(B, st.n), tau=f(B, st.na), status=torch.full((B,), -99, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev))
-        trace = dict(q=f(K, B, m.nq), v=f(K, B, m.nv), x=f(K, B, st.n), tau=f(K, B, st.na), status=torch.full((K, B), -99, dtype=torch.int32, device=dev))
-        h.rollout_traced(0, B, K, dict(q=q0, v=v0, ref=ref), lim, out, f(B, m.nq), f(B, m.nv), tm.dt, trace=trace, stride=1, stream=stream)
-        torch.cuda.synchronize()
         assert (trace["status"] == 0).all().item()
         # entry r's x belongs to the state BEFORE tick r: entry r - 1's q, v
         qb = torch.cat([q0[None], trace["q"][:-1]]).contiguous()
         vb = torch.cat([v0[None], trace["v"][:-1]]).contiguous()
-        T = up(np.asarray(st.force_gen()).reshape(st.nc, 6, 12))
+        T = torch.from_numpy(np.asarray(st.force_gen()).reshape(st.nc, 6, 12)).to(dev)
         w = torch.einsum("cij,rbcj->rbci", T, trace["x"][..., st.nv:].reshape(K, B, st.nc, 12)).contiguous()
         whole = _run_lda(h, 0, K * B, m.nv, qb.reshape(K * B, -1), vb.reshape(K * B, -1), trace["x"].reshape(K * B, -1), st.n, w.reshape(K * B, st.nc, 6), torch, dev)
         for r in range(K):
@@ -416,10 +381,8 @@ def test_audit_of_a_traced_squat():
 
 def _run_lda(h, slot, B, nv, q, v, x, ldx, w, torch, dev):
     """tau [B, nv] with a tick's x [B, ldx] passed as `a`, lda = ldx: NaN-prefilled, guarded."""
-    whole = torch.full((B * nv + GUARD,), float("nan"), dtype=torch.float64, device=dev)
-    h.inverse_dynamics(slot, B, q.contiguous(), whole[:B * nv], v=v.contiguous(), a=x.contiguous(), lda=ldx, wrench=w.contiguous(),
+    whole, part = mq.guarded(B * nv, torch.float64, dev, torch)
+    h.inverse_dynamics(slot, B, q.contiguous(), part, v=v.contiguous(), a=x.contiguous(), lda=ldx, wrench=w.contiguous(),
                        stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
-    out = whole.cpu().numpy()
-    assert np.isnan(out[B * nv:]).all() and np.isfinite(out[:B * nv]).all()
-    return out[:B * nv].reshape(B, nv)
+    return mq.read_guarded(whole, B * nv, "tau").reshape(B, nv)

@@ -9,57 +9,32 @@ One case differs from what one would write down first.  A floating tree of 64 bo
 nv > 64 (the dv block's 64 x 64 register grid), so no slot can hold it: the lane limit is tested on a FIXED tree of 64 bodies and the
 floating base at its own limit, 59 bodies (nv = 64)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
-from inria_wbc_amd import capi, refprog, structure
+from inria_wbc_amd import capi, structure
 from inria_wbc_amd import model as mdl
 from inria_wbc_amd import observe as obs
+from tests import model_queries as mq
+from tests.model_queries import BATCHES, _torch
 
 pytestmark = pytest.mark.gpu
 
 TOL_ROWS = 1e-10
-BATCHES = (1, 3, 5, 67)
 NMAX = max(BATCHES)
 FIELDS = capi.OBSERVABLES
 WIDTH = {"com": 3, "vcom": 3, "placement": 12, "velocity": 6}
-GUARD = 16  # elements behind every output buffer that must stay untouched
-
-
-def _torch():
-    import torch
-    return torch, torch.device("cuda", 0)
-
-
-def _minimal(m):
-    """The smallest stack a slot accepts for `m`: one SE(3) task on frame 0 (the observables need the tree, not the tasks)."""
-    st = structure._mk("observe_" + m.name, m.nv, m.na, [], [("a", 3, 1.0)], None, [], False, False, [])
-    return st, mdl.build_taskmap(m, st, [dict(name="a", type="se3", tracked=m.frame_names[0], kp=10.0, mask="111000")])
 
 
 def _tree(seed, nb, fb, chain=False):
-    def f():
-        m = mdl.random_tree(seed, nb, fb, nframe=12)
-        if chain:  # (the way three_limbs in tests/test_gpu_terms.py rewrites parents) depth nb - 1: every doubling round moves something
-            m.parent = np.arange(-1, nb - 1, dtype=np.int32)
-        m.frame_body[0], m.frame_body[1] = 0, nb - 1  # a frame on body 0, a frame on the last body
-        m.validate()
-        return (m,) + _minimal(m)
-    return f
+    return mq.tree_case("observe_", seed, nb, fb, "chain" if chain else None)
 
 
-def _shipped(model, st, stack):
-    def f():
-        m = model()
-        s = st()
-        return m, s, mdl.build_taskmap(m, s, stack())
-    return f
-
-
-CASES = {"talos": _shipped(mdl.talos_like, structure.talos_structure, mdl.talos_stack),
-         "icub": _shipped(mdl.icub_like, structure.icub_structure, mdl.icub_stack),
-         "franka": _shipped(mdl.franka_like, structure.franka_structure, mdl.franka_stack),
+CASES = {"talos": mq.talos_case,
+         "icub": mq.shipped_case(mdl.icub_like, structure.icub_structure, mdl.icub_stack),
+         "franka": mq.shipped_case(mdl.franka_like, structure.franka_structure, mdl.franka_stack),
          "tree_one_body": _tree(51, 1, False), "tree_30_floating": _tree(52, 30, True), "tree_62_fixed": _tree(53, 62, False),
          "tree_64_fixed_lane_limit": _tree(54, 64, False), "tree_59_floating_nv_limit": _tree(55, 59, True), "chain_62": _tree(56, 62, False, chain=True)}
 
@@ -92,12 +67,7 @@ def _pick(ora, frames):
 
 def _bufs(B, nf, td, dev, torch, which=FIELDS):
     """NaN-filled output buffers with GUARD elements behind each: {name: (whole buffer, the part wbcqp_observe may write)}."""
-    out = {}
-    for k in which:
-        n = B * WIDTH[k] * (1 if k in ("com", "vcom") else nf)
-        whole = torch.full((n + GUARD,), float("nan"), dtype=td, device=dev)
-        out[k] = (whole, whole[:n])
-    return out
+    return {k: mq.guarded(B * WIDTH[k] * (1 if k in ("com", "vcom") else nf), td, dev, torch) for k in which}
 
 
 def _observe(h, slot, B, nf, q, v, dev, torch, which=FIELDS, td=None):
@@ -108,13 +78,7 @@ def _observe(h, slot, B, nf, q, v, dev, torch, which=FIELDS, td=None):
     need_v = "vcom" in which or ("velocity" in which and nf)
     h.observe(slot, B, q[:B].contiguous(), v[:B].contiguous() if need_v else None, stream=torch.cuda.current_stream().cuda_stream, **kw)
     torch.cuda.synchronize()
-    res = {}
-    for k, (whole, part) in bufs.items():
-        a = whole.cpu().numpy()
-        assert np.isnan(a[part.numel():]).all(), (k, "written past the end")
-        assert np.isfinite(a[:part.numel()]).all(), (k, "an element was not written")
-        res[k] = a[:part.numel()].reshape((B, 3) if k in ("com", "vcom") else (B, nf, WIDTH[k]))
-    return res
+    return {k: mq.read_guarded(whole, part.numel(), k).reshape((B, 3) if k in ("com", "vcom") else (B, nf, WIDTH[k])) for k, (whole, part) in bufs.items()}
 
 
 def _worst(got, want):
@@ -123,9 +87,7 @@ def _worst(got, want):
 
 @pytest.fixture(scope="module")
 def handle():
-    h = capi.Handle(0, capi.F64)
-    yield h
-    h.close()
+    yield from mq.open_handle()
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -203,22 +165,8 @@ def test_same_bits_on_two_launches_and_at_any_place_in_a_batch(handle):
     handle.set_observed_frames(3, frames)
     qn, vn = _states(m, tm, NMAX, 74_000)
     q, v = torch.from_numpy(qn).to(dev), torch.from_numpy(vn).to(dev)
-    a = _observe(handle, 3, NMAX, len(frames), q, v, dev, torch)
-    b = _observe(handle, 3, NMAX, len(frames), q, v, dev, torch)
-    c = _observe(handle, 3, 6, len(frames), q[10:16], v[10:16], dev, torch)  # rows 10 .. 15 as a batch of their own: other waves, other workgroups
-    for k in FIELDS:
-        assert np.array_equal(a[k], b[k]), k
-        assert np.array_equal(a[k][10:16], c[k]), k
-
-
-def _squat(B, K, dev, torch):
-    m, st, tm = CASES["talos"]()
-    s = mdl.sample_states(m, tm, B, 97_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
-    com = next(b for b in tm.blocks if b.kind == mdl.T_COM)
-    prog = refprog.move_com_program(tm.nref, com.ref, m.com(m.q0), [[0.0, 0.0, -0.2]], "001", tm.dt, 2.0, loop=True, absolute=False)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    lim = dict(w=up(np.tile(st.default_weights, (B, 1))), tlb=up(np.tile(-m.tau_max, (B, 1))), tub=up(np.tile(m.tau_max, (B, 1))))
-    return m, st, tm, prog, -37 * np.arange(B), dict(q=up(s["q"]), v=up(s["v"])), up(s["ref"]), lim
+    a = mq.same_bits_on_two_launches_and_at_any_place_in_a_batch(lambda lo, hi: _observe(handle, 3, hi - lo, len(frames), q[lo:hi], v[lo:hi], dev, torch), NMAX)
+    assert set(a) == set(FIELDS)
 
 
 def _trace_checks(h, slots, m, frames, trq, trv, B, n_rec, dev, torch):
@@ -241,22 +189,10 @@ def _trace_checks(h, slots, m, frames, trq, trv, B, n_rec, dev, torch):
 def test_observe_over_a_trace():
     torch, dev = _torch()
     B, K, stride = 8, 12, 3
-    n_rec = K // stride
-    m, st, tm, prog, offsets, state, base, lim = _squat(B, K, dev, torch)
-    h = capi.Handle(0, capi.F64)
+    names = ["leg_left_6_joint", "leg_right_6_joint", "gripper_left_joint", "gripper_right_joint", "base_link"]
+    h, m, _, _, trace, _, _ = mq.traced_squat(B, K, stride, lambda h, m, tm: h.set_observed_frames(0, obs.frame_ids(m, names)))
     try:
-        h.set_structure(0, st)
-        h.set_model(0, m, tm)
-        frames = obs.frame_ids(m, ["leg_left_6_joint", "leg_right_6_joint", "gripper_left_joint", "gripper_right_joint", "base_link"])
-        h.set_observed_frames(0, frames)
-        stream = torch.cuda.current_stream().cuda_stream
-        ref = h.reference_samples(prog, base, offsets, 0, K, torch.zeros(K, B, tm.nref, dtype=torch.float64, device=dev), stream=stream)
-        f = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)  # noqa: E731
-        out = dict(x=f(B, st.n), tau=f(B, st.na), status=torch.full((B,), -99, dtype=torch.int32, device=dev), iters=torch.zeros(B, dtype=torch.int32, device=dev))
-        trace = dict(q=f(n_rec, B, m.nq), v=f(n_rec, B, m.nv))
-        h.rollout_traced(0, B, K, dict(state, ref=ref), lim, out, f(B, m.nq), f(B, m.nv), tm.dt, trace=trace, stride=stride, stream=stream)
-        torch.cuda.synchronize()
-        w = _trace_checks(h, [0], m, frames, trace["q"], trace["v"], B, n_rec, dev, torch)
+        w = _trace_checks(h, [0], m, obs.frame_ids(m, names), trace["q"], trace["v"], B, K // stride, dev, torch)
         print("observe over a traced roll-out (4 x 8 states) against the oracle: %s" % {k: "%.1e" % e for k, e in w.items()})
     finally:
         h.close()
@@ -315,23 +251,11 @@ def test_f32_handle_rounds_the_f64_result(handle):
 
 
 def test_nothing_else_moves(handle):
-    m, st, tm = CASES["talos"]()
-    handle.set_structure(3, st)
-    handle.set_model(3, m, tm)
-    B = 6
-    s = mdl.sample_states(m, tm, B, 77_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
-    tlb, tub, w = np.tile(-m.tau_max, (B, 1)), np.tile(m.tau_max, (B, 1)), np.tile(st.default_weights, (B, 1))
-    rows0 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
-    tick0 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
-    handle.set_observed_frames(3, list(range(40)))
-    handle.observe_host(3, s["q"], s["v"])
-    rows1 = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
-    tick1 = handle.tick_host(3, s["q"], s["v"], s["ref"], tlb, tub, w, tm.dt)
-    for k in rows0:
-        assert np.array_equal(rows0[k], rows1[k]), k
-    for k in tick0:
-        assert np.array_equal(tick0[k], tick1[k]), k
-    assert (tick0["status"] == 0).all()
+    def query(s, tick):
+        handle.set_observed_frames(3, list(range(40)))
+        handle.observe_host(3, s["q"], s["v"])
+
+    mq.nothing_else_moves(handle, CASES["talos"](), 77_000, query)
 
 
 def test_refusals_come_before_any_launch():
@@ -346,11 +270,7 @@ def test_refusals_come_before_any_launch():
         ptr = {k: b[1].data_ptr() for k, b in bufs.items()}
         stream = torch.cuda.current_stream().cuda_stream
 
-        def refused(call):
-            with pytest.raises(capi.WbcqpError) as e:
-                call()
-            assert e.value.code == 1, e.value  # WBCQP_ERR_INVALID
-            assert (h.lib.wbcqp_last_error(h._h) or b"").decode().strip(), "no message in wbcqp_last_error"
+        refused = functools.partial(mq.refused, h)
 
         def raw_set(slot, n, arr):
             h._check(h.lib.wbcqp_set_observed_frames(h._h, slot, n, arr.ctypes.data_as(capi.c_i32_p) if arr is not None else None))
@@ -385,12 +305,48 @@ def test_refusals_come_before_any_launch():
         raw_observe(0, 0, q.data_ptr(), v.data_ptr(), **ptr)  # batch == 0: WBCQP_OK, nothing launched
         torch.cuda.synchronize()
         for k, (whole, _) in bufs.items():
-            assert torch.isnan(whole).all().item(), (k, "a refused call wrote something")
+            assert mq.unwritten(whole.cpu().numpy()).all(), (k, "a refused call wrote something")
         got = _observe(h, 0, B, nf, q, v, dev, torch)  # and the selection [3, 5] still stands
         want = obs.observe(m, qn, vn, [3, 5])
         assert max(_worst(got, want).values()) <= TOL_ROWS
     finally:
         h.close()
+
+
+def _talos_both(handle, seed, B=4, nf=2):
+    """Talos on slot 3 of the module's handle; B states and prefilled outputs for nf frames, each as a (device, host) pair."""
+    m, st, tm = CASES["talos"]()
+    handle.set_structure(3, st)
+    handle.set_model(3, m, tm)
+    qn, vn = _states(m, tm, B, seed)
+    out = {k: mq.prefilled_both(B * WIDTH[k] * (1 if k in ("com", "vcom") else nf)) for k in FIELDS}
+    return m, mq.both(qn), mq.both(vn), out, lambda *ks: mq.Out(capi.CObservables, **{k: out[k] for k in ks})
+
+
+def test_a_refused_selection_keeps_the_one_before(handle):
+    m, (_, qn), (_, vn), _, _ = _talos_both(handle, 78_100)
+
+    def still_stands(frames):
+        got = handle.observe_host(3, qn, vn)
+        assert got["placement"].shape == (4, len(frames), 12) and max(_worst(got, obs.observe(m, qn, vn, frames)).values()) <= TOL_ROWS
+
+    mq.a_refused_selection_keeps_the_one_before(handle, "observed", m.nframe, 64, still_stands)
+
+
+def test_host_refusals_are_the_device_refusals(handle):
+    _, q, v, out, O = _talos_both(handle, 78_200)  # (no frames are selected)
+    mq.host_refusals_match(handle, "observe", [(3, 4, q, v, O("placement")),    # placement asked for with no frames selected
+                                               (3, 4, q, None, O("com", "vcom")),  # vcom asked for with v NULL
+                                               (3, 4, None, v, O("com")),          # q NULL
+                                               (3, -1, q, v, O("com")),            # a negative batch
+                                               (9, 4, q, v, O("com"))],            # a slot without a model
+                           out.values())
+
+
+def test_batch_zero_through_the_host_entry_point(handle):
+    _, q, v, out, O = _talos_both(handle, 78_300)
+    handle.set_observed_frames(3, [3, 5])
+    mq.host_batch_zero(handle, "observe", [(3, 0, q, v, O(*FIELDS)), (3, 0, None, v, O(*FIELDS))], out.values())  # (q is not looked at)
 
 
 def test_set_structure_and_set_model_drop_the_selection():
@@ -403,17 +359,11 @@ def test_set_structure_and_set_model_drop_the_selection():
         h.set_model(0, m, tm)
         h.set_observed_frames(0, [1, 2])
         assert h.observe_host(0, qn, vn)["placement"].shape == (3, 2, 12)
-        for again in ("structure", "model"):
-            if again == "structure":
-                h.set_structure(0, st)
-            h.set_model(0, m, tm)
-            buf = torch.full((3 * 2 * 12,), float("nan"), dtype=torch.float64, device=dev)
-            with pytest.raises(capi.WbcqpError) as e:
-                h.observe(0, 3, torch.from_numpy(qn).to(dev), None, placement=buf)
-            assert e.value.code == 1 and "no frames" in str(e.value)
-            torch.cuda.synchronize()
-            assert torch.isnan(buf).all().item()
+        def and_then():
             assert set(h.observe_host(0, qn, vn)) == {"com", "vcom"}  # the CoM needs no selection
             h.set_observed_frames(0, [1, 2])
+
+        mq.set_structure_and_set_model_drop(h, (m, st, tm), lambda: torch.full((3 * 2 * 12,), float("nan"), dtype=torch.float64, device=dev),
+                                            lambda buf: h.observe(0, 3, torch.from_numpy(qn).to(dev), None, placement=buf), "no frames", and_then)
     finally:
         h.close()

@@ -5,6 +5,7 @@ import subprocess
 
 import pytest
 
+from tests import model_queries as mq
 from tests.test_inverse_dynamics_host import AUDIT_TOL
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,8 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def host_build(built_lib):
-    from inria_wbc_amd import build
-    return build.build_host()
+    return mq.host_build()
 
 
 @pytest.mark.gpu
@@ -40,11 +40,5 @@ def test_rnea_double_support_after_move_com(host_build):
 
 @pytest.mark.gpu
 def test_file_source_refuses(host_build, tmp_path):
-    from tools import dump_batch
-    from inria_wbc_amd import structure, synth
-    st = structure.talos_structure()
-    path = str(tmp_path / "b.bin")
-    dump_batch.dump(path, st, synth.generate(st, 2, synth.SEED_BASE["talos"]))
-    r = subprocess.run([host_build["inverse_dynamics_facade_test"], "--file-source", os.path.join(ROOT, "configs/talos/pos_tracker.yaml"), path],
-                       capture_output=True, text=True, timeout=120)
+    r = mq.run_file_source(host_build["inverse_dynamics_facade_test"], tmp_path)
     assert r.returncode == 0 and "refused: 2 of 2" in r.stdout, r.stdout + r.stderr

@@ -6,14 +6,15 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import model_queries as mq
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FRAMES = ["leg_left_6_joint", "gripper_right_joint", "base_link"]
 
 
 @pytest.fixture(scope="module")
 def host_build(built_lib):
-    from inria_wbc_amd import build
-    return build.build_host()
+    return mq.host_build()
 
 
 @pytest.mark.gpu
@@ -54,11 +55,5 @@ def test_com_now_and_model_frames_after_move_com(host_build, tmp_path):
 
 @pytest.mark.gpu
 def test_file_source_refuses_the_accessors(host_build, tmp_path):
-    from tools import dump_batch
-    from inria_wbc_amd import structure, synth
-    st = structure.talos_structure()
-    path = str(tmp_path / "b.bin")
-    dump_batch.dump(path, st, synth.generate(st, 2, synth.SEED_BASE["talos"]))
-    r = subprocess.run([host_build["observe_facade_test"], "--file-source", os.path.join(ROOT, "configs/talos/pos_tracker.yaml"), path],
-                       capture_output=True, text=True, timeout=120)
+    r = mq.run_file_source(host_build["observe_facade_test"], tmp_path)
     assert r.returncode == 0 and "refused: 3 of 3" in r.stdout, r.stdout + r.stderr
