@@ -193,6 +193,51 @@ def eiquadprog(H, g, CE, ce0, CI, ci0, max_iter: int = 1000):
     return dict(x=x, u=u[:iq.value].copy(), A=A[:iq.value].copy(), iq=iq.value, iters=it.value, fval=fv.value, status=status)
 
 
+class _EventLog(C.Structure):
+    _fields_ = [("cap", C.c_int), ("count", C.c_int), ("rec", c_int_p)]
+
+
+# codes of wbco_event_log records (oracle/wbc_oracle.h: WBCO_EV_*)
+EV_PICK, EV_FULL_ADD, EV_DEPENDENT, EV_PARTIAL_DROP, EV_DUAL_DROP, EV_EXIT_PSI, EV_EXIT_NONE, EV_UNBOUNDED, EV_MAX_ITER = range(9)
+EV_NAMES = ("PICK", "FULL_ADD", "DEPENDENT", "PARTIAL_DROP", "DUAL_DROP", "EXIT_PSI", "EXIT_NONE", "UNBOUNDED", "MAX_ITER")
+
+
+def eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter: int = 1000, cap: int = 8192):
+    """eiquadprog() through wbco_eiquadprog_fast_log: the same dict plus `events`, an int32 [count, 4] array of
+    (code, row, position, iq) records (EV_*; row / position -1 where an event has none; iq before the event takes effect)."""
+    H = np.ascontiguousarray(H, np.float64); g = np.ascontiguousarray(g, np.float64)
+    n = g.size
+    CE = np.ascontiguousarray(CE, np.float64).reshape(-1, n); ce0 = np.ascontiguousarray(ce0, np.float64).reshape(-1)
+    CI = np.ascontiguousarray(CI, np.float64).reshape(-1, n); ci0 = np.ascontiguousarray(ci0, np.float64).reshape(-1)
+    neq, nin2 = CE.shape[0], CI.shape[0]
+    x = np.zeros(n); u = np.zeros(neq + nin2 + 2); A = np.zeros(neq + nin2 + 2, np.int32)
+    iq = C.c_int(0); it = C.c_int(0); fv = C.c_double(0.0)
+    CEp = CE if neq else np.zeros((1, n)); ce0p = ce0 if neq else np.zeros(1)
+    CIp = CI if nin2 else np.zeros((1, n)); ci0p = ci0 if nin2 else np.zeros(1)
+    rec = np.zeros((cap, 4), np.int32)
+    log = _EventLog(cap, 0, _ip(rec))
+    status = lib().wbco_eiquadprog_fast_log(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
+                                            _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
+                                            int(max_iter), None, C.byref(log))
+    assert log.count <= cap, ("event log overflow", log.count, cap)
+    return dict(x=x, u=u[:iq.value].copy(), A=A[:iq.value].copy(), iq=iq.value, iters=it.value, fval=fv.value, status=status,
+                events=rec[:log.count].copy())
+
+
+def tick_log(st, inputs: Dict[str, np.ndarray], index: int = 0, ref: Optional[dict] = None):
+    """The event log of QP `index` of a structured input set: assemble() then eiquadprog_log() with the structure's max_iter.
+    x and the iteration count are asserted BITWISE those of tick_batch (`ref`: its outputs for the whole set, if the caller has them),
+    so a log always describes the run the parity tests compare against.  Returns eiquadprog_log's dict."""
+    H, g, CE, ce0, CI, ci0 = assemble(st, inputs, index)
+    out = eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter=st.max_iter)
+    if ref is None:
+        one = {k: np.asarray(v)[index:index + 1] for k, v in inputs.items() if not k.startswith("_")}
+        ref, index = tick_batch(st, one), 0
+    assert out["iters"] == int(ref["iters"][index]), ("logged run took another path", out["iters"], int(ref["iters"][index]))
+    assert out["x"].tobytes() == np.ascontiguousarray(ref["x"][index]).tobytes(), "logged run's x is not tick_batch's, bit for bit"
+    return out
+
+
 def eiquadprog_timed(H, g, CE, ce0, CI, ci0, reps: int = 200, max_iter: int = 1000, native: bool = False):
     """(seconds per solve, status, iterations): `reps` solves of one dense QP inside ONE C loop after a warm-up solve
     (wbco_eiquadprog_timed) -- no Python between two solves."""

@@ -384,12 +384,37 @@ long wbco_ws_size(int n, int neq, int nin2)
     return 3L * n * n + 5L * n + 2L * m + nin2 + 2L * m + 2L * nin2 + 64;
 }
 
+/* one record of the event log (never called with a null log: the callers test it) */
+static void gi_log_event(wbco_event_log* log, int code, int row, const int* A, int neq, int iq)
+{
+    int pos = -1;
+    if (row >= 0)
+        for (int k = neq; k < iq; ++k)
+            if (A[k] == row) pos = k - neq;
+    if (code == WBCO_EV_FULL_ADD) pos = iq - neq;
+    if (log->count < log->cap) {
+        int* r = log->rec + 4 * (size_t)log->count;
+        r[0] = code; r[1] = row; r[2] = pos; r[3] = iq;
+    }
+    log->count++;
+}
+
 int wbco_eiquadprog_fast(int n, int neq, int nin2,
                          const double* H, const double* g,
                          const double* CE, const double* ce0,
                          const double* CI, const double* ci0,
                          double* x, double* u_out, int* A_out, int* iq_out, int* iter_out, double* fval,
                          int max_iter, double* ws_in)
+{
+    return wbco_eiquadprog_fast_log(n, neq, nin2, H, g, CE, ce0, CI, ci0, x, u_out, A_out, iq_out, iter_out, fval, max_iter, ws_in, NULL);
+}
+
+int wbco_eiquadprog_fast_log(int n, int neq, int nin2,
+                             const double* H, const double* g,
+                             const double* CE, const double* ce0,
+                             const double* CI, const double* ci0,
+                             double* x, double* u_out, int* A_out, int* iq_out, int* iter_out, double* fval,
+                             int max_iter, double* ws_in, wbco_event_log* log)
 {
     double* ws = ws_in ? ws_in : (double*)malloc(sizeof(double) * (size_t)wbco_ws_size(n, neq, nin2));
     const long m = neq + nin2 + 2;
@@ -499,6 +524,7 @@ l1:
     iter++;
     if (iter >= max_iter) {
         status = WBCO_EIQ_MAX_ITER_REACHED;
+        if (log) gi_log_event(log, WBCO_EV_MAX_ITER, -1, A, neq, iq);
         goto done;
     }
     /* step 1: choose a violated constraint */
@@ -519,6 +545,7 @@ l1:
     }
     if (fabs(psi) <= nin2 * DBL_EPSILON * c1 * c2 * 100.0) {
         status = WBCO_EIQ_OPTIMAL; /* numerically no infeasibility left */
+        if (log) gi_log_event(log, WBCO_EV_EXIT_PSI, -1, A, neq, iq);
         goto done;
     }
     for (int i = 0; i < iq; ++i) {
@@ -541,11 +568,13 @@ l2:
     }
     if (ss >= 0.0) {
         status = WBCO_EIQ_OPTIMAL;
+        if (log) gi_log_event(log, WBCO_EV_EXIT_NONE, -1, A, neq, iq);
         goto done;
     }
     for (int j = 0; j < n; ++j) np[j] = CI[IDX(ip, j, n)];
     u[iq] = 0.0;
     A[iq] = ip;
+    if (log) gi_log_event(log, WBCO_EV_PICK, ip, A, neq, iq);
 
 l2a:
     /* step 2a: step direction in primal (z) and dual (r) space */
@@ -578,6 +607,7 @@ l2a:
         /* step 2c */
         if (t >= inf) {
             status = WBCO_EIQ_UNBOUNDED; /* dual unbounded = primal infeasible */
+            if (log) gi_log_event(log, WBCO_EV_UNBOUNDED, ip, A, neq, iq);
             goto done;
         }
         if (t2 >= inf) {
@@ -585,6 +615,7 @@ l2a:
             for (int k = 0; k < iq; ++k) u[k] -= t * r[k];
             u[iq] += t;
             iai[l] = l;
+            if (log) gi_log_event(log, WBCO_EV_DUAL_DROP, l, A, neq, iq);
             gi_delete_constraint(n, R, J, A, u, neq, &iq, l);
             goto l2a;
         }
@@ -597,6 +628,7 @@ l2a:
     if (t == t2) {
         /* full step: add constraint ip to the active set */
         if (!gi_add_constraint(n, R, J, d, &iq, &R_norm)) {
+            if (log) gi_log_event(log, WBCO_EV_DEPENDENT, ip, A, neq, iq - 1);
             iaexcl[ip] = 0;
             gi_delete_constraint(n, R, J, A, u, neq, &iq, ip);
             for (int i = 0; i < nin2; ++i) iai[i] = i;
@@ -608,12 +640,15 @@ l2a:
             for (int i = 0; i < n; ++i) x[i] = x_old[i];
             goto l2;
         }
-        else
+        else {
             iai[ip] = -1;
+            if (log) gi_log_event(log, WBCO_EV_FULL_ADD, ip, A, neq, iq - 1);
+        }
         goto l1;
     }
     /* partial step: drop constraint l */
     iai[l] = l;
+    if (log) gi_log_event(log, WBCO_EV_PARTIAL_DROP, l, A, neq, iq);
     gi_delete_constraint(n, R, J, A, u, neq, &iq, l);
     {
         double v = ci0[ip];

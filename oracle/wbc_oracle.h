@@ -127,6 +127,34 @@ void wbco_assemble(const wbco_structure* st, const wbco_inputs* in,
  * H is overwritten?  No: inputs are const; workspace is allocated internally unless ws != NULL
  * (ws from wbco_ws_size doubles).  Returns WBCO_EIQ_*. */
 long wbco_ws_size(int n, int neq, int nin2);
+
+/* The branches of the active-set loop, as events: (code, row, position, iq) per record.  `row` is the one-sided CI row the event is about
+ * (-1: none), `position` its place in the inequality block of the active set (0 = first; -1: none), `iq` the size of the active set
+ * BEFORE the event takes effect.  `count` counts every event; only the first `cap` are recorded. */
+enum {
+    WBCO_EV_PICK = 0,         /* step 2 chose `row` */
+    WBCO_EV_FULL_ADD = 1,     /* full step: `row` enters the active set at `position` */
+    WBCO_EV_DEPENDENT = 2,    /* add_constraint refused `row`: excluded, A / u / x restored, back to step 2 */
+    WBCO_EV_PARTIAL_DROP = 3, /* partial step in primal and dual space: `row` leaves from `position` */
+    WBCO_EV_DUAL_DROP = 4,    /* step in dual space only (t2 = inf): `row` leaves from `position` */
+    WBCO_EV_EXIT_PSI = 5,     /* step 1: |psi| under the tolerance */
+    WBCO_EV_EXIT_NONE = 6,    /* step 2: nothing eligible is violated */
+    WBCO_EV_UNBOUNDED = 7,    /* t1 = t2 = inf while `row` is the candidate */
+    WBCO_EV_MAX_ITER = 8
+};
+typedef struct {
+    int cap;   /* records that fit in rec[4 * cap] */
+    int count; /* events seen (may exceed cap) */
+    int* rec;
+} wbco_event_log;
+
+/* wbco_eiquadprog_fast with the event log (log may be NULL: then it IS wbco_eiquadprog_fast). */
+int wbco_eiquadprog_fast_log(int n, int neq, int nin2,
+                             const double* H, const double* g,
+                             const double* CE, const double* ce0,
+                             const double* CI, const double* ci0,
+                             double* x, double* u, int* A, int* iq_out, int* iter_out, double* fval,
+                             int max_iter, double* ws, wbco_event_log* log);
 int wbco_eiquadprog_fast(int n, int neq, int nin2,
                          const double* H, const double* g,
                          const double* CE, const double* ce0,

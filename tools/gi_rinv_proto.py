@@ -81,6 +81,9 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
             sip = s[ip]
             if trace is not None:
                 trace.setdefault("events", []).append(("pick", ip, iq - neq))
+                c2 = cand.copy(); c2[ip] = 0.0
+                j2 = int(np.argmin(c2))  # the runner-up and how far behind it is: a near tie is decided by the last bits of s
+                trace.setdefault("picks", []).append((ip, float(s[ip]), j2, float(c2[j2])))
             u[iq] = 0.0
             A = A[:iq] + [ip]
             if round5 and pend is not None:
@@ -111,10 +114,14 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
                 t2 = -sip / znp if abs(zz) > EPS else np.inf
                 t = min(t1, t2)
                 if t == np.inf:
+                    if trace is not None:
+                        trace["partial_steps"] = partial_steps
                     return dict(x=x, status=INFEASIBLE, iters=it)
                 if t2 == np.inf:  # dual step
                     u[neq:iq] -= t * r
                     u[iq] += t
+                    if trace is not None:
+                        trace["dual_steps"] = trace.get("dual_steps", 0) + 1
                 else:
                     x = x + t * z
                     u[neq:iq] -= t * r
@@ -193,10 +200,12 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
                     pend = (w, v, iq)
                 else:
                     J[:, iq:] = rnd(J[:, iq:] - np.outer(w, v))
+            if trace is not None:  # every add_constraint: the new diagonal of R beside R_norm (a row in the span of the active ones leaves rounding noise here)
+                trace.setdefault("adds", []).append((ip, iq, float(alpha), float(R_norm)))
             if abs(alpha) <= EPS * R_norm:  # dependent: back to the saved iterate, pick another
                 excl[ip] = False
-                for i in range(min(iq, len(A_old))):
-                    pass
+                if trace is not None:
+                    trace["rejected"] = trace.get("rejected", 0) + 1
                 A = list(A_old[:iq])
                 act[:] = False
                 for a in A:
@@ -212,6 +221,8 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
             R_norm = max(R_norm, abs(alpha))
             act[ip] = True
             iq += 1
+            if trace is not None and iq == n:
+                trace["vertices"] = trace.get("vertices", 0) + 1
             break
         if done:
             break
