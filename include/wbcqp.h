@@ -56,7 +56,9 @@ extern "C" {
  *        chosen model frames from (q, v) on the device); wbcqp_set_model now keeps the model's whole frame table on the host;
  *        wbcqp_sphere_model, wbcqp_collisions, wbcqp_set_collision_spheres, wbcqp_check_collisions and wbcqp_check_collisions_host (self-collision
  *        of a robot's sphere model from q on the device); wbcqp_set_wrench_frames, wbcqp_inverse_dynamics and wbcqp_inverse_dynamics_host (the joint
- *        torques of a motion under external wrenches at model frames, on the device)
+ *        torques of a motion under external wrenches at model frames, on the device); wbcqp_torque_monitor, wbcqp_torque_checks,
+ *        wbcqp_torque_monitor_state_bytes, wbcqp_detect_torque_collisions and wbcqp_detect_torque_collisions_host (external collisions of a fleet
+ *        from the discrepancy of model and measured joint torques over a stream of ticks, on the device)
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -703,6 +705,63 @@ int wbcqp_inverse_dynamics(wbcqp_handle* handle, int slot, int batch, const void
 /* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done.  `a` is read up to its last row's nv-th entry. */
 int wbcqp_inverse_dynamics_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
                                 void* tau);
+
+/* ---- Did a robot hit something: model torques against measured torques over a stream of ticks ----
+ * The reference's inria_wbc::safety::TorqueCollisionDetection (src/safety/torque_collision_detection.cpp) with the filters of
+ * include/inria_wbc/estimators/filtering.hpp, as its controller wires them (src/controllers/talos_pos_tracker.cpp:62-158), for a whole fleet and
+ * n_ticks ticks in one call.  One wavefront per instance (torque_monitor_kernel, csrc/wbcqp_monitor.hpp), one lane per monitored joint; the wave walks
+ * its instance's ticks in order.  No slot and no model: this is signal processing on arrays the other calls produce.  Per instance and tick:
+ *   1. filter the sensors' samples over a window (Filter::filter): while fewer than `window` samples have been seen the window is the samples so far,
+ *      afterwards the last `window` samples.  MEAN: the window summed oldest first, one division by the count.  MEDIAN: the middle element of the
+ *      sorted window, the mean of the two middle ones for an even count (a NaN sorts above every number).  NONE: the sample itself.
+ *   2. filtered += offset, when given
+ *   3. discrepancy = tau_model[joint[j]] - filtered[j]; RAW validity is |discrepancy| < threshold, strict
+ *   4. with K = max_invalid + 1, joint j is INVALID iff in each of the last K ticks it was raw-invalid with the same non-zero sign of the discrepancy
+ *   5. detected = any joint invalid (the reference's check returns false)
+ * A NaN discrepancy is raw-invalid but has no sign, so by itself it never makes a joint invalid (the reference casts the sign of a NaN to int, which is
+ * undefined; this is the reading its ring of signs gives when that cast yields 0).  The same holds for a discrepancy of exactly zero under a threshold <= 0.
+ * Arrays (tau_model, tau_sensor, discrepancy, filtered of the handle's dtype):
+ *   tau_model   row (t, i) at tau_model + (t * batch + i) * ldt: a trace's tau with ldt = na as it lies; the output of inverse dynamics passed as pointer
+ *               + 6 elements with ldt = nv.  Read at the columns `joint` alone.
+ *   tau_sensor  [n_ticks][batch][n_joints]
+ *   state       [batch][state_bytes], in and out, always double whatever the dtype: the window and the K-step memory of every joint.  All-zero bytes
+ *               are a freshly reset detector (the reference's reset is a memset); NULL: a fresh detector for this call, discarded afterwards.
+ *               A state belongs to the monitor's n_joints, filter, window and max_invalid; thresholds, offsets and columns may change between calls.
+ * A stream cut into calls at any tick, the state carried along, gives the bits of one call.  Only additions, one division and one subtraction: no
+ * atomics, nothing to fuse, an instance's results depend on its own rows alone (F32 handles read float, compute in double, write float). */
+#define WBCQP_MAX_MONITORED 64 /* one lane per monitored joint */
+#define WBCQP_MAX_FILTER_WINDOW 64
+#define WBCQP_MAX_INVALID 31
+enum { WBCQP_FILTER_NONE = 0, WBCQP_FILTER_MEAN = 1, WBCQP_FILTER_MEDIAN = 2 };
+typedef struct {
+    int32_t n_joints;        /* 1 .. WBCQP_MAX_MONITORED */
+    const int32_t* joint;    /* [n_joints] column of a tau_model row; repeats allowed */
+    const double* threshold; /* [n_joints]; +-inf and negative values allowed (the reference's file uses 1e10 as "off"), NaN refused */
+    const double* offset;    /* [n_joints] or NULL (set_offset / remove_offset); finite */
+    int32_t filter, window;  /* WBCQP_FILTER_*; 1 .. WBCQP_MAX_FILTER_WINDOW (ignored for NONE) */
+    int32_t max_invalid;     /* 0 .. WBCQP_MAX_INVALID: set_max_consecutive_invalid */
+} wbcqp_torque_monitor;      /* HOST; copied into the kernel's arguments each call (about 1.3 KB): no device table, nothing to drop */
+typedef struct {
+    int32_t* detected;   /* [n_ticks][batch] 1 where the reference's check returned false */
+    uint64_t* invalid;   /* [n_ticks][batch] bit j: monitored joint j invalid (get_invalid_ids) */
+    void* discrepancy;   /* [n_ticks][batch][n_joints] handle's dtype (get_discrepancy) */
+    void* filtered;      /* [n_ticks][batch][n_joints] handle's dtype (get_filtered_sensors, offset included) */
+    int32_t* first_tick; /* [batch] first tick of THIS call with detected, -1 if none */
+    int32_t* n_detected; /* [batch] ticks of this call with detected */
+} wbcqp_torque_checks;   /* each may be NULL: not written */
+/* Bytes of one instance's state for this monitor: 8 + 8 n_joints + 8 window n_joints (no window for NONE).  Pure host code; 0 for a monitor the calls
+ * below refuse (NULL, n_joints / filter / window / max_invalid out of range, a NULL or negative joint, a NaN threshold, a non-finite offset). */
+int64_t wbcqp_torque_monitor_state_bytes(const wbcqp_torque_monitor* monitor);
+/* DEVICE pointers (state included), asynchronous on `stream`, ordered like wbcqp_observe; the monitor itself is read on the host before the call returns.
+ * Refused with WBCQP_ERR_INVALID before anything is launched: a monitor as above, a joint outside [0, ldt), batch < 0, n_ticks < 0, tau_model, tau_sensor
+ * or out NULL.  WBCQP_OK with nothing launched: batch == 0, n_ticks == 0, or every output NULL and state NULL.  Every output NULL with a state given
+ * still runs and advances the state. */
+int wbcqp_detect_torque_collisions(wbcqp_handle* handle, const wbcqp_torque_monitor* monitor, int batch, int n_ticks, const void* tau_model, int ldt,
+                                   const void* tau_sensor, void* state, const wbcqp_torque_checks* out, void* stream);
+/* Same with HOST pointers, state included (staged both ways): through device buffers owned by the handle, blocks until done.  tau_model is read up to
+ * its last row's highest monitored column. */
+int wbcqp_detect_torque_collisions_host(wbcqp_handle* handle, const wbcqp_torque_monitor* monitor, int batch, int n_ticks, const void* tau_model, int ldt,
+                                        const void* tau_sensor, void* state, const wbcqp_torque_checks* out);
 
 /* ---- References generated on the device from a reference program ----
  * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the

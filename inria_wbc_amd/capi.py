@@ -33,8 +33,10 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program",
            "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host",
            "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host",
-           "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host")
+           "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host",
+           "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host")
 OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe writes (wbcqp_observables); per instance 3, 3, n_frames x 12, n_frames x 6
+TORQUE_CHECKS = ("detected", "invalid", "discrepancy", "filtered", "first_tick", "n_detected")  # what wbcqp_detect_torque_collisions writes (wbcqp_torque_checks)
 COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
@@ -171,6 +173,33 @@ class CCollisions(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in COLLISIONS]
 
 
+class CTorqueMonitor(C.Structure):
+    _fields_ = [("n_joints", C.c_int32), ("joint", c_i32_p), ("threshold", c_f64_p), ("offset", c_f64_p), ("filter", C.c_int32), ("window", C.c_int32),
+                ("max_invalid", C.c_int32)]
+
+
+class CTorqueChecks(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in TORQUE_CHECKS]
+
+
+class TorqueMonitorBuffers:
+    """Host-side wbcqp_torque_monitor from a torque_monitor.Monitor (anything with its attributes); keeps the arrays alive."""
+
+    def __init__(self, monitor):
+        self.joint = np.ascontiguousarray(monitor.joint, dtype=np.int32).reshape(-1)
+        self.threshold = np.ascontiguousarray(monitor.threshold, dtype=np.float64).reshape(-1)
+        self.offset = None if monitor.offset is None else np.ascontiguousarray(monitor.offset, dtype=np.float64).reshape(-1)
+        assert self.threshold.size == self.joint.size and (self.offset is None or self.offset.size == self.joint.size)
+        self.c = CTorqueMonitor(int(self.joint.size), self.joint.ctypes.data_as(c_i32_p), self.threshold.ctypes.data_as(c_f64_p),
+                                self.offset.ctypes.data_as(c_f64_p) if self.offset is not None else None, int(monitor.filter), int(monitor.window),
+                                int(monitor.max_invalid))
+
+
+def torque_monitor_state_bytes(monitor) -> int:
+    """wbcqp_torque_monitor_state_bytes: bytes of one instance's detector state, 0 for a monitor the library refuses.  Host code: no GPU needed."""
+    return int(load_library().wbcqp_torque_monitor_state_bytes(C.byref(TorqueMonitorBuffers(monitor).c)))
+
+
 def load_library(path: Optional[str] = None):
     """Loads libwbcqp.so -- after torch, when torch is installed: the library links libamdhip64.so.7, and a process in which it comes FIRST gets
     /opt/rocm's HIP runtime while a later `import torch` brings torch's bundled one.  Two runtimes on one GPU work, but the first one then answers
@@ -234,6 +263,12 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_set_wrench_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
     lib.wbcqp_inverse_dynamics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.wbcqp_inverse_dynamics_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.wbcqp_torque_monitor_state_bytes.argtypes = [C.POINTER(CTorqueMonitor)]
+    lib.wbcqp_torque_monitor_state_bytes.restype = C.c_int64
+    lib.wbcqp_detect_torque_collisions.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(CTorqueChecks), C.c_void_p]
+    lib.wbcqp_detect_torque_collisions_host.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                        C.c_void_p, C.POINTER(CTorqueChecks)]
     _lib = lib
     return lib
 
@@ -552,6 +587,39 @@ class Handle:
         self._check(self.lib.wbcqp_inverse_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(a), int(a.shape[-1]) if a is not None else 0,
                                                          dat(wrench), tau.ctypes.data))
         return tau
+
+    def detect_torque_collisions(self, monitor, batch: int, n_ticks: int, tau_model, ldt: int, tau_sensor, state=None, detected=None, invalid=None,
+                                 discrepancy=None, filtered=None, first_tick=None, n_detected=None, stream: int = 0):
+        """External collisions from joint torques on device tensors (wbcqp_detect_torque_collisions).  monitor: a torque_monitor.Monitor;
+        tau_model: row (t, i) starts (t * batch + i) * ldt elements after its data pointer (or an int: a device address, e.g. the output of
+        inverse_dynamics moved by six elements); tau_sensor [n_ticks, batch, n_joints]; state: uint8 / float64 tensor of batch * state_bytes bytes,
+        in and out, or None; outputs, each optional: detected [n_ticks, batch] int32, invalid [n_ticks, batch] int64 (bit j: joint j),
+        discrepancy / filtered [n_ticks, batch, n_joints] (the handle's dtype), first_tick / n_detected [batch] int32."""
+        mb = TorqueMonitorBuffers(monitor)
+        ptr = lambda t: (t if isinstance(t, int) else t.data_ptr()) if t is not None else None
+        out = CTorqueChecks(ptr(detected), ptr(invalid), ptr(discrepancy), ptr(filtered), ptr(first_tick), ptr(n_detected))
+        self._check(self.lib.wbcqp_detect_torque_collisions(self._h, C.byref(mb.c), int(batch), int(n_ticks), ptr(tau_model), int(ldt), ptr(tau_sensor),
+                                                            ptr(state), C.byref(out), C.c_void_p(stream)))
+
+    def detect_torque_collisions_host(self, monitor, tau_model: np.ndarray, tau_sensor: np.ndarray, state: Optional[np.ndarray] = None,
+                                      outputs: Sequence[str] = TORQUE_CHECKS) -> Dict[str, np.ndarray]:
+        """wbcqp_detect_torque_collisions_host: tau_model [T, B, ldt], tau_sensor [T, B, n_joints]; state: a contiguous uint8 array
+        [B, state_bytes], updated in place, or None.  Returns the outputs named in `outputs` as numpy arrays (invalid as uint64)."""
+        tau_model = np.ascontiguousarray(tau_model, dtype=self.np_dtype)
+        tau_sensor = np.ascontiguousarray(tau_sensor, dtype=self.np_dtype)
+        T, B, n = tau_sensor.shape
+        assert tau_model.shape[:2] == (T, B), (tau_model.shape, tau_sensor.shape)
+        if state is not None:
+            assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"], "state: a contiguous uint8 array [B, state_bytes]"
+        shapes = {"detected": ((T, B), np.int32), "invalid": ((T, B), np.uint64), "discrepancy": ((T, B, n), self.np_dtype),
+                  "filtered": ((T, B, n), self.np_dtype), "first_tick": ((B,), np.int32), "n_detected": ((B,), np.int32)}
+        res = {k: np.zeros(*shapes[k]) for k in outputs}
+        mb = TorqueMonitorBuffers(monitor)
+        out = CTorqueChecks(*[res[k].ctypes.data if k in res else None for k in TORQUE_CHECKS])
+        self._check(self.lib.wbcqp_detect_torque_collisions_host(self._h, C.byref(mb.c), B, T, tau_model.ctypes.data, int(tau_model.shape[2]),
+                                                                 tau_sensor.ctypes.data, state.ctypes.data if state is not None else None,
+                                                                 C.byref(out)))
+        return res
 
     def set_collision_spheres(self, slot: int, table):
         """The slot's sphere model (wbcqp_set_collision_spheres): a collision.SphereTable (collision.sphere_table builds one from the reference's

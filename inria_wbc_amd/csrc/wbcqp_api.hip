@@ -7,13 +7,15 @@
 //
 // This file holds the exported entry points; the host code behind them is in the wbcqp_host_*.hpp headers, included here and nowhere else (the library
 // stays ONE translation unit): the handle, the description of a call's arrays and the staging (handle), structure -> sizes and LDS layouts (derive),
-// arguments -> kernel launches (launch), reference programs (program), the loops over ticks (rollout), the model queries on a fleet's states (queries).
+// arguments -> kernel launches (launch), reference programs (program), the loops over ticks (rollout), the model queries on a fleet's states (queries),
+// the torque monitor on a fleet's streams of joint torques (monitor).
 #include "wbcqp_host_handle.hpp"
 #include "wbcqp_host_derive.hpp"
 #include "wbcqp_host_launch.hpp"
 #include "wbcqp_host_program.hpp"
 #include "wbcqp_host_rollout.hpp"
 #include "wbcqp_host_queries.hpp"
+#include "wbcqp_host_monitor.hpp"
 
 namespace {
 
@@ -660,6 +662,45 @@ int wbcqp_inverse_dynamics_host(wbcqp_handle* h, int slot, int batch, const void
     Arr dn[1] = {{-1, tau, B * nv * es, 0}};
     return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
         return launch_inverse_dynamics(h, *s, batch, u[0], u[1], u[2], lda, u[3], d[0], nullptr);
+    });
+}
+
+int64_t wbcqp_torque_monitor_state_bytes(const wbcqp_torque_monitor* monitor)
+{
+    return monitor_flaw(monitor) ? 0 : (int64_t)monitor_state_bytes(monitor->n_joints, monitor->filter, monitor->window);
+}
+
+int wbcqp_detect_torque_collisions(wbcqp_handle* h, const wbcqp_torque_monitor* monitor, int batch, int n_ticks, const void* tau_model, int ldt,
+                                   const void* tau_sensor, void* state, const wbcqp_torque_checks* out, void* stream)
+{
+    MonitorDev D;
+    bool run = false;
+    WB_TRY(check_torque_monitor(h, monitor, batch, n_ticks, tau_model, ldt, tau_sensor, state, out, &D, &run));
+    if (!run) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_torque_monitor(h, D, batch, n_ticks, tau_model, ldt, tau_sensor, state, state, *out, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_detect_torque_collisions_host(wbcqp_handle* h, const wbcqp_torque_monitor* monitor, int batch, int n_ticks, const void* tau_model, int ldt,
+                                        const void* tau_sensor, void* state, const wbcqp_torque_checks* out)
+{
+    MonitorDev D;
+    bool run = false;
+    WB_TRY(check_torque_monitor(h, monitor, batch, n_ticks, tau_model, ldt, tau_sensor, state, out, &D, &run));
+    if (!run) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), rows = (size_t)n_ticks * batch, nj = (size_t)D.n_joints;
+    const size_t sb = (size_t)batch * monitor_state_bytes(D.n_joints, D.filter, D.window);
+    const int reach = *std::max_element(D.joint, D.joint + D.n_joints) + 1; // (rows ldt apart, the last one read up to its highest monitored column)
+    Arr up[3] = {{-1, const_cast<void*>(tau_model), ((rows - 1) * (size_t)ldt + reach) * es, 0}, {-1, const_cast<void*>(tau_sensor), rows * nj * es, 0},
+                 {-1, state, sb, 0}};
+    Arr dn[7] = {{-1, out->detected, rows * 4, 0}, {-1, out->invalid, rows * 8, 0}, {-1, out->discrepancy, rows * nj * es, 0},
+                 {-1, out->filtered, rows * nj * es, 0}, {-1, out->first_tick, (size_t)batch * 4, 0}, {-1, out->n_detected, (size_t)batch * 4, 0},
+                 {-1, state, sb, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        const wbcqp_torque_checks dev = {static_cast<int32_t*>(d[0]), static_cast<uint64_t*>(d[1]), d[2], d[3], static_cast<int32_t*>(d[4]),
+                                         static_cast<int32_t*>(d[5])};
+        return launch_torque_monitor(h, D, batch, n_ticks, u[0], ldt, u[1], u[2], d[6], dev, nullptr);
     });
 }
 
