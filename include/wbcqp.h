@@ -58,7 +58,11 @@ extern "C" {
  *        of a robot's sphere model from q on the device); wbcqp_set_wrench_frames, wbcqp_inverse_dynamics and wbcqp_inverse_dynamics_host (the joint
  *        torques of a motion under external wrenches at model frames, on the device); wbcqp_torque_monitor, wbcqp_torque_checks,
  *        wbcqp_torque_monitor_state_bytes, wbcqp_detect_torque_collisions and wbcqp_detect_torque_collisions_host (external collisions of a fleet
- *        from the discrepancy of model and measured joint torques over a stream of ticks, on the device)
+ *        from the discrepancy of model and measured joint torques over a stream of ticks, on the device); wbcqp_observe_acom and wbcqp_observe_acom_host (wbcqp_observe with
+ *        the CoM's bias acceleration as one more output); wbcqp_stabilizer, wbcqp_stab_inputs, wbcqp_stab_outputs,
+ *        wbcqp_stabilizer_state_bytes, wbcqp_stabilize and wbcqp_stabilize_host (the humanoid controllers' stabiliser: CoP estimator, filters and
+ *        admittance laws that rewrite a tick's references, on the device).  151 therefore names more than one set of declarations: every one of them
+ *        contains the one before it unchanged (nothing was removed or resized), so a caller checks for a symbol, not for the number
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
  *   140  wbcqp_rollout, wbcqp_outputs.active_mask (WBCQP_FLAG_WARM_START), wbcqp_state.momentum, wbcqp_layout.wave_per_qp
@@ -627,6 +631,13 @@ int wbcqp_set_observed_frames(wbcqp_handle* handle, int slot, int n_frames, cons
 int wbcqp_observe(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream);
 /* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done. */
 int wbcqp_observe_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out);
+/* wbcqp_observe with one more output, acom [batch][3]: the acceleration of the CoM with zero joint accelerations and no gravity, in the world's axes --
+ * sum_i m_i a_ci / sum_i m_i, what tsid keeps as data.acom[0] and the CoM task subtracts as its drift; the stabiliser's model ZMP needs it (below).  The
+ * same launch of the same kernel: the acceleration sweep sits behind a wave-uniform branch, and the outputs of `out` have the bits wbcqp_observe gives
+ * them.  (A call of its own and not a fifth member: wbcqp_observables keeps its size for callers built against it.)  `out` may be NULL (acom alone); acom
+ * needs v (refused with v == NULL); acom == NULL is wbcqp_observe.  The _host twin takes HOST pointers. */
+int wbcqp_observe_acom(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* acom, void* stream);
+int wbcqp_observe_acom_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* acom);
 
 /* ---- Does a robot's sphere model touch itself ----
  * The reference's CollisionCheck::is_colliding (src/safety/collision_check.cpp:27-87), which its controller runs on the solver's own model after every
@@ -762,6 +773,90 @@ int wbcqp_detect_torque_collisions(wbcqp_handle* handle, const wbcqp_torque_moni
  * its last row's highest monitored column. */
 int wbcqp_detect_torque_collisions_host(wbcqp_handle* handle, const wbcqp_torque_monitor* monitor, int batch, int n_ticks, const void* tau_model, int ldt,
                                         const void* tau_sensor, void* state, const wbcqp_torque_checks* out);
+
+/* ---- Keep a fleet on its feet: CoP estimator and admittance laws on a tick's references ----
+ * The stabiliser of the reference's humanoid controllers (src/controllers/humanoid_pos_tracker.cpp:134-302, src/stabilizers/stabilizer.cpp,
+ * src/estimators/cop.cpp, include/inria_wbc/estimators/filtering.hpp), one tick of it for every robot of a fleet.  Only a tick's references change, never
+ * the QP's structure: one wavefront per instance (stabilize_kernel, csrc/wbcqp_stabilize.hpp) reads the reference row, the feet's force/torque samples,
+ * the model's CoM, its acceleration and the feet's positions, and writes the row that wbcqp_problem_data / wbcqp_tick / wbcqp_tick_mixed consume
+ * unchanged.  The caller keeps `ref` and passes ref_out to the tick: that is the reference's "put the references back".  Per instance and tick, in double
+ * (w = window, FMIN = 30):
+ *   filters   every filter is a moving average: the samples so far while fewer than w have been pushed, afterwards the last w; summed oldest first, one
+ *             division by the count.  READY: at least w samples since the start or the last reset.
+ *   CoP       left foot, when lf_force.z > FMIN: raw = foot.xy + ((-torque.y - foot.z force.x) / force.z, (torque.x - foot.z force.y) / force.z), pushed
+ *             into the left CoP filter; otherwise that filter is RESET.  The right foot alike.  With both raw CoPs: Kajita's weighted combination
+ *             (cop.cpp:71-83, in its order of operations) pushed into the combined filter; with a foot missing the combined filter is neither pushed nor
+ *             reset, so its stale samples are averaged after touch-down.  A filtered CoP is VALID this tick iff its raw value existed this tick, its
+ *             filter is ready and neither coordinate is NaN.  valid_cop: the first valid one of (combined, left, right).
+ *   forces    when |lf_force| > FMIN (sqrt(x^2 + y^2 + z^2)), lf_force.z is pushed into the left force filter; otherwise the filtered force of this tick
+ *             is zero and the filter is left alone.  The right foot alike.
+ *   CoM       with a valid_cop: zmp = com.xy - com.z / 9.81 * acom.xy, cor = zmp - valid_cop; on the xy entries of the CoM reference
+ *             pos -= p[0:2] cor, vel -= p[2:4] cor / dt, acc -= p[4:6] cor / (dt dt)                                       (p = com_gains)
+ *   ankles    per foot with a valid CoP and an active contact: pitch = p[0] (cop.x - foot.x), roll = p[1] (cop.y - foot.y); (e0, e1, e2) = Eigen's
+ *             eulerAngles(0, 1, 2) of the foot task's reference rotation; R' = Rx(e0 + roll) Ry(e1 + pitch) Rz(e2); vel[4] += p[2] pitch / dt,
+ *             vel[3] += p[3] roll / dt, acc[4] += p[4] pitch / (dt dt), acc[3] += p[5] roll / (dt dt)                      (p = ankle_gains)
+ *             The foot task's reference becomes (its translation, R', these vel / acc); the contact's (ITS translation, R', the FOOT TASK's vel / acc).
+ *             Eigen's first angle lies in [0, pi]: for a rotation whose atan2(R(1,2), R(2,2)) > 0 the added pitch acts with the opposite sign.
+ *   torso     with x_prev, both force columns and both force filters ready: n_l, n_r = sum over the contact's four point forces of normal . f_i in
+ *             x_prev; zctrl = |n_l - n_r| - |lf_filtered.z - rf_filtered.z|; roll = g[0] zctrl; the torso reference's e0 += roll,
+ *             vel[3] += g[1] roll / dt, acc[3] += g[2] roll / (dt dt)                                                      (g = ffda_gains)
+ *   guards    where the reference throws -- a CoP handed to a law with |x| >= 10 AND |y| >= 10 (WBCQP_STAB_ERR_COP); otherwise, inside the torso law,
+ *             |lf_filtered.z + rf_filtered.z| > 10 mass 9.81 (WBCQP_STAB_ERR_FORCE) -- the instance's ref_out is its ref, no law's bit is set, and its
+ *             state has advanced as usual (the reference throws after its filters are updated).  No other instance is affected.
+ * com, acom and the feet's positions are arrays of the caller's: wbcqp_observe_acom's com, acom and placement as they lie (lf_pos = 12 f + 9 for observed
+ * frame f).  The reference reads them from the state the PREVIOUS tick's rows were formed at.
+ * Every product, sum and quotient rounds once, in the reference's association; rotations go through atan2 / sin / cos and are the only entries that depend
+ * on the device's libm.  No atomics, an instance's results depend on its own rows alone (F32 handles read float, compute in double, write float).
+ * Not here: the ZMP force distributor (use_zmp: it sets force references and regularisation weights, which live in the slot), the momentum / IMU
+ * admittances (the reference's controller never calls them), the torso-roll clamp of TalosPosTracker, a roll-out form (a stabilised tick needs that
+ * tick's sensors).  A mixed fleet: one call per contact set on that set's rows. */
+#define WBCQP_MAX_STAB_WINDOW 64
+enum {
+    WBCQP_STAB_COP = 1, WBCQP_STAB_LCOP = 2, WBCQP_STAB_RCOP = 4,                               /* the combined / left / right filtered CoP is valid */
+    WBCQP_STAB_COM = 8, WBCQP_STAB_LANKLE = 16, WBCQP_STAB_RANKLE = 32, WBCQP_STAB_FFDA = 64, /* the law was applied */
+    WBCQP_STAB_ERR_COP = 128, WBCQP_STAB_ERR_FORCE = 256
+};
+typedef struct {
+    int32_t window;                              /* filter_size, 1 .. WBCQP_MAX_STAB_WINDOW */
+    double dt, mass;                             /* CONTROLLER.dt; total model mass (Mg = mass * 9.81) */
+    double com_gains[6], ankle_gains[6], ffda_gains[3];
+    int32_t nref;
+    int32_t com_ref, lf_ref, rf_ref, torso_ref;  /* offsets in a reference row (wbcqp_task.ref); all required */
+    int32_t lf_contact_ref, rf_contact_ref;      /* wbcqp_taskmap.contact_ref of the foot's contact; -1: contact not active */
+    int32_t lf_force_col, rf_force_col;          /* first of the contact's 12 force variables in a row of x; -1: not active */
+    double normal[3];                            /* contact normal (tasks.yaml `normal`) */
+    int32_t lf_pos, rf_pos;                      /* element offset of the foot's translation inside a row of `placement` */
+} wbcqp_stabilizer;                              /* HOST, read before the call returns */
+typedef struct {
+    const void* ref;       /* [batch][nref] */
+    const void* wrench;    /* [batch][12]: lf_force, lf_torque, rf_force, rf_torque (the sensor_data keys) */
+    const void* com;       /* [batch][3] */
+    const void* acom;      /* [batch][3] */
+    const void* placement; /* row i at placement + i * ldp: wbcqp_observables.placement as it lies */
+    int32_t ldp;
+    const void* x_prev;    /* row i at x_prev + i * ldx: the previous tick's x, or NULL (first tick: no torso law) */
+    int32_t ldx;
+} wbcqp_stab_inputs;
+typedef struct {
+    void* ref_out;  /* [batch][nref]; may equal ref exactly (in place) */
+    int32_t* flags; /* [batch] WBCQP_STAB_* */
+    void* cop;      /* [batch][3][2] filtered CoP: combined, left, right; NaN where not valid */
+} wbcqp_stab_outputs; /* each may be NULL (and so may the struct) */
+/* Bytes of one instance's state: 40 + 64 window.  Layout (always double, whatever the dtype): [5]{int32 count, int32 head} of the filters combined, left,
+ * right CoP, left, right force z; then [window][8] samples, channels combined x, y, left x, y, right x, y, left fz, right fz.  All-zero bytes are a
+ * fresh stabiliser.  A state belongs to its window.  The block is read and written as 8-byte words: `state` must be 8-byte aligned (the size is a
+ * multiple of 8, so every instance's block then is).  Pure host code; 0 for a stabiliser the calls below refuse. */
+int64_t wbcqp_stabilizer_state_bytes(const wbcqp_stabilizer* stabilizer);
+/* DEVICE pointers (state included; state NULL: a fresh stabiliser for this call, discarded afterwards), asynchronous on `stream`, ordered like
+ * wbcqp_observe.  Refused with WBCQP_ERR_INVALID before anything is launched: a NULL stabiliser, inputs, ref, wrench, com, acom or placement; window out
+ * of range; dt or mass not finite or not > 0; a gain or the normal not finite; a required offset negative (an optional one below -1), an offset whose
+ * block (CoM 9, others 24) runs past nref, two blocks that overlap; ldp < max(lf_pos, rf_pos) + 3; with x_prev, ldx < an active force column + 12; batch < 0.
+ * WBCQP_OK with nothing launched: batch == 0; every output NULL and state NULL. */
+int wbcqp_stabilize(wbcqp_handle* handle, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state,
+                    const wbcqp_stab_outputs* out, void* stream);
+/* Same with HOST pointers, state included (staged both ways): through device buffers owned by the handle, blocks until done. */
+int wbcqp_stabilize_host(wbcqp_handle* handle, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state,
+                         const wbcqp_stab_outputs* out);
 
 /* ---- References generated on the device from a reference program ----
  * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the

@@ -84,7 +84,8 @@ def build_host(verbose: bool = False) -> dict:
     out = {"lib": lib, "test_facade": os.path.join(LIBDIR, "test_facade"), "qp_timer_test": os.path.join(LIBDIR, "qp_timer_test"),
            "observe_facade_test": os.path.join(LIBDIR, "observe_facade_test"), "collision_facade_test": os.path.join(LIBDIR, "collision_facade_test"),
            "inverse_dynamics_facade_test": os.path.join(LIBDIR, "inverse_dynamics_facade_test"),
-           "torque_collision_facade_test": os.path.join(LIBDIR, "torque_collision_facade_test")}
+           "torque_collision_facade_test": os.path.join(LIBDIR, "torque_collision_facade_test"),
+           "stabilizer_facade_test": os.path.join(LIBDIR, "stabilizer_facade_test")}
     # (nothing to do when the outputs are newer than every source of the facade, the C ABI header and the library)
     deps = [LIB, os.path.join(_HERE, "..", "include", "wbcqp.h"), os.path.abspath(__file__)]
     for root, _, files in os.walk(HOST):
@@ -103,6 +104,7 @@ def build_host(verbose: bool = False) -> dict:
                   out["inverse_dynamics_facade_test"]] + link,
         common + [os.path.join(HOST, "tests", "torque_collision_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o",
                   out["torque_collision_facade_test"]] + link,
+        common + [os.path.join(HOST, "tests", "stabilizer_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["stabilizer_facade_test"]] + link,
     ]
     for cmd in cmds:
         if verbose:

@@ -31,11 +31,15 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_sync", "wbcqp_launch_order", "wbcqp_solve_dense", "wbcqp_solve_dense_host", "wbcqp_rollout",
            "wbcqp_tick_mixed", "wbcqp_rollout_mixed", "wbcqp_task_costs", "wbcqp_rollout_traced", "wbcqp_rollout_mixed_traced",
            "wbcqp_check_program", "wbcqp_reference_samples", "wbcqp_rollout_program", "wbcqp_rollout_mixed_program",
-           "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host",
+           "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host", "wbcqp_observe_acom", "wbcqp_observe_acom_host",
            "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host",
            "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host",
-           "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host")
+           "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host",
+           "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host")
 OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe writes (wbcqp_observables); per instance 3, 3, n_frames x 12, n_frames x 6
+# (a fifth output, acom [3], comes from wbcqp_observe_acom: asked for by name -- observe(acom=...), observe_host(acom=True))
+STAB_INPUTS = ("ref", "wrench", "com", "acom", "placement", "x_prev")  # the arrays of wbcqp_stab_inputs
+STAB_OUTPUTS = ("ref_out", "flags", "cop")  # what wbcqp_stabilize writes (wbcqp_stab_outputs)
 TORQUE_CHECKS = ("detected", "invalid", "discrepancy", "filtered", "first_tick", "n_detected")  # what wbcqp_detect_torque_collisions writes (wbcqp_torque_checks)
 COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
@@ -195,6 +199,36 @@ class TorqueMonitorBuffers:
                                 int(monitor.max_invalid))
 
 
+class CStabilizer(C.Structure):
+    _fields_ = [("window", C.c_int32), ("dt", C.c_double), ("mass", C.c_double), ("com_gains", C.c_double * 6), ("ankle_gains", C.c_double * 6),
+                ("ffda_gains", C.c_double * 3), ("nref", C.c_int32), ("com_ref", C.c_int32), ("lf_ref", C.c_int32), ("rf_ref", C.c_int32),
+                ("torso_ref", C.c_int32), ("lf_contact_ref", C.c_int32), ("rf_contact_ref", C.c_int32), ("lf_force_col", C.c_int32),
+                ("rf_force_col", C.c_int32), ("normal", C.c_double * 3), ("lf_pos", C.c_int32), ("rf_pos", C.c_int32)]
+
+
+class CStabInputs(C.Structure):
+    _fields_ = [("ref", C.c_void_p), ("wrench", C.c_void_p), ("com", C.c_void_p), ("acom", C.c_void_p), ("placement", C.c_void_p), ("ldp", C.c_int32),
+                ("x_prev", C.c_void_p), ("ldx", C.c_int32)]
+
+
+class CStabOutputs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in STAB_OUTPUTS]
+
+
+def c_stabilizer(stab) -> CStabilizer:
+    """wbcqp_stabilizer from a stabilizer.Stabilizer (anything with its attributes)."""
+    vec = lambda a, n: (C.c_double * n)(*[float(x) for x in np.asarray(a, dtype=np.float64).reshape(n)])  # noqa: E731
+    return CStabilizer(int(stab.window), float(stab.dt), float(stab.mass), vec(stab.com_gains, 6), vec(stab.ankle_gains, 6), vec(stab.ffda_gains, 3),
+                       int(stab.nref), int(stab.com_ref), int(stab.lf_ref), int(stab.rf_ref), int(stab.torso_ref), int(stab.lf_contact_ref),
+                       int(stab.rf_contact_ref), int(stab.lf_force_col), int(stab.rf_force_col), vec(stab.normal, 3), int(stab.lf_pos), int(stab.rf_pos))
+
+
+def stabilizer_state_bytes(stab) -> int:
+    """wbcqp_stabilizer_state_bytes: bytes of one instance's filters, 0 for a stabiliser the library refuses (None: a NULL one).  Host code: no GPU
+    needed."""
+    return int(load_library().wbcqp_stabilizer_state_bytes(C.byref(c_stabilizer(stab)) if stab is not None else None))
+
+
 def torque_monitor_state_bytes(monitor) -> int:
     """wbcqp_torque_monitor_state_bytes: bytes of one instance's detector state, 0 for a monitor the library refuses.  Host code: no GPU needed."""
     return int(load_library().wbcqp_torque_monitor_state_bytes(C.byref(TorqueMonitorBuffers(monitor).c)))
@@ -257,6 +291,8 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_set_observed_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
     lib.wbcqp_observe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p]
     lib.wbcqp_observe_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables)]
+    lib.wbcqp_observe_acom.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p, C.c_void_p]
+    lib.wbcqp_observe_acom_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p]
     lib.wbcqp_set_collision_spheres.argtypes = [C.c_void_p, C.c_int, C.POINTER(CSphereModel)]
     lib.wbcqp_check_collisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions), C.c_void_p]
     lib.wbcqp_check_collisions_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions)]
@@ -269,6 +305,10 @@ def load_library(path: Optional[str] = None):
                                                    C.POINTER(CTorqueChecks), C.c_void_p]
     lib.wbcqp_detect_torque_collisions_host.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                                         C.c_void_p, C.POINTER(CTorqueChecks)]
+    lib.wbcqp_stabilizer_state_bytes.argtypes = [C.POINTER(CStabilizer)]
+    lib.wbcqp_stabilizer_state_bytes.restype = C.c_int64
+    lib.wbcqp_stabilize.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.c_int, C.POINTER(CStabInputs), C.c_void_p, C.POINTER(CStabOutputs), C.c_void_p]
+    lib.wbcqp_stabilize_host.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.c_int, C.POINTER(CStabInputs), C.c_void_p, C.POINTER(CStabOutputs)]
     _lib = lib
     return lib
 
@@ -534,15 +574,18 @@ class Handle:
         them), repeats allowed, at most 64 (wbcqp_set_observed_frames)."""
         self._select_frames(slot, frames, self.lib.wbcqp_set_observed_frames, "observed")
 
-    def observe(self, slot: int, batch: int, q, v=None, com=None, vcom=None, placement=None, velocity=None, stream: int = 0):
-        """CoM and frame poses of `batch` states on device tensors (wbcqp_observe): q [batch, nq], v [batch, nv] (None when neither vcom nor
-        velocity is asked for); outputs, each optional: com / vcom [batch, 3], placement [batch, n_frames, 12], velocity [batch, n_frames, 6]."""
+    def observe(self, slot: int, batch: int, q, v=None, com=None, vcom=None, placement=None, velocity=None, stream: int = 0, acom=None):
+        """CoM and frame poses of `batch` states on device tensors (wbcqp_observe): q [batch, nq], v [batch, nv] (None when neither vcom, acom nor
+        velocity is asked for); outputs, each optional: com / vcom / acom [batch, 3], placement [batch, n_frames, 12], velocity [batch, n_frames, 6]."""
         out = CObservables(self._ptr(com), self._ptr(vcom), self._ptr(placement), self._ptr(velocity))
+        if acom is not None:  # (wbcqp_observe_acom: the same launch with one more output)
+            self._check(self.lib.wbcqp_observe_acom(self._h, slot, int(batch), self._ptr(q), self._ptr(v), C.byref(out), self._ptr(acom), C.c_void_p(stream)))
+            return
         self._check(self.lib.wbcqp_observe(self._h, slot, int(batch), self._ptr(q), self._ptr(v), C.byref(out), C.c_void_p(stream)))
 
-    def observe_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None) -> Dict[str, np.ndarray]:
+    def observe_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, acom: bool = False) -> Dict[str, np.ndarray]:
         """wbcqp_observe_host: dict(com [B, 3], placement [B, n_frames, 12]) and, when v is given, vcom [B, 3] and velocity [B, n_frames, 6]
-        (placement / velocity only when frames are selected).  The library cannot be asked how many frames a slot observes, so the outputs are
+        (placement / velocity only when frames are selected); acom=True (needs v) adds acom [B, 3].  The library cannot be asked how many frames a slot observes, so the outputs are
         sized from what THIS Handle's set_observed_frames last selected on the slot: a selection made any other way (the raw library, another
         wrapper of the same handle) is not seen here -- such callers size their own buffers and use observe()."""
         q = np.ascontiguousarray(q, dtype=self.np_dtype)
@@ -557,6 +600,11 @@ class Handle:
             if nf:
                 res["velocity"] = np.zeros((B, nf, 6), self.np_dtype)
         out = CObservables(*[res[k].ctypes.data if k in res else None for k in OBSERVABLES])
+        if acom:
+            res["acom"] = np.zeros((B, 3), self.np_dtype)
+            self._check(self.lib.wbcqp_observe_acom_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out),
+                                                         res["acom"].ctypes.data))
+            return res
         self._check(self.lib.wbcqp_observe_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out)))
         return res
 
@@ -619,6 +667,38 @@ class Handle:
         self._check(self.lib.wbcqp_detect_torque_collisions_host(self._h, C.byref(mb.c), B, T, tau_model.ctypes.data, int(tau_model.shape[2]),
                                                                  tau_sensor.ctypes.data, state.ctypes.data if state is not None else None,
                                                                  C.byref(out)))
+        return res
+
+    def stabilize(self, stab, batch: int, ref, wrench, com, acom, placement, ldp: int = 0, x_prev=None, ldx: int = 0, state=None, ref_out=None,
+                  flags=None, cop=None, stream: int = 0):
+        """One tick of the stabiliser on device tensors (wbcqp_stabilize).  stab: a stabilizer.Stabilizer; ref [batch, nref], wrench [batch, 12],
+        com / acom [batch, 3]; placement: row i starts i * ldp elements after its data pointer (ldp = 0: its row length), as observe() writes it;
+        x_prev: the previous tick's x, rows ldx apart (0: its row length), or None; state: uint8 / float64 tensor of batch * state_bytes bytes, in
+        and out, or None; outputs, each optional: ref_out [batch, nref] (may be ref), flags [batch] int32, cop [batch, 3, 2]."""
+        ptr = lambda t: (t if isinstance(t, int) else t.data_ptr()) if t is not None else None  # noqa: E731
+        width = lambda t, ld: int(ld) if ld or t is None or isinstance(t, int) else int(t.numel() // max(int(t.shape[0]), 1))  # noqa: E731
+        cs = c_stabilizer(stab)
+        cin = CStabInputs(ptr(ref), ptr(wrench), ptr(com), ptr(acom), ptr(placement), width(placement, ldp), ptr(x_prev), width(x_prev, ldx))
+        out = CStabOutputs(ptr(ref_out), ptr(flags), ptr(cop))
+        self._check(self.lib.wbcqp_stabilize(self._h, C.byref(cs), int(batch), C.byref(cin), ptr(state), C.byref(out), C.c_void_p(stream)))
+
+    def stabilize_host(self, stab, inputs: Dict[str, np.ndarray], state: Optional[np.ndarray] = None,
+                       outputs: Sequence[str] = STAB_OUTPUTS) -> Dict[str, np.ndarray]:
+        """wbcqp_stabilize_host: inputs as stabilizer.step takes them (ref [B, nref], wrench [B, 12], com, acom [B, 3], placement [B, ldp], x_prev
+        [B, ldx] or absent); state: a contiguous uint8 array [B, state_bytes], updated in place, or None.  Returns the outputs named in `outputs`."""
+        a = {k: (np.ascontiguousarray(inputs[k], dtype=self.np_dtype) if inputs.get(k) is not None else None) for k in STAB_INPUTS}
+        B = a["ref"].shape[0]
+        a = {k: (t.reshape(B, -1) if t is not None else None) for k, t in a.items()}
+        if state is not None:
+            assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"], "state: a contiguous uint8 array [B, state_bytes]"
+        shapes = {"ref_out": ((B, int(stab.nref)), self.np_dtype), "flags": ((B,), np.int32), "cop": ((B, 3, 2), self.np_dtype)}
+        res = {k: np.zeros(*shapes[k]) for k in outputs}
+        dat = lambda t: t.ctypes.data if t is not None else None  # noqa: E731
+        cs = c_stabilizer(stab)
+        cin = CStabInputs(dat(a["ref"]), dat(a["wrench"]), dat(a["com"]), dat(a["acom"]), dat(a["placement"]), int(a["placement"].shape[1]),
+                          dat(a["x_prev"]), int(a["x_prev"].shape[1]) if a["x_prev"] is not None else 0)
+        out = CStabOutputs(*[res[k].ctypes.data if k in res else None for k in STAB_OUTPUTS])
+        self._check(self.lib.wbcqp_stabilize_host(self._h, C.byref(cs), B, C.byref(cin), dat(state), C.byref(out)))
         return res
 
     def set_collision_spheres(self, slot: int, table):

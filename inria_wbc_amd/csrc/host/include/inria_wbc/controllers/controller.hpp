@@ -7,6 +7,7 @@
 #ifndef IWBC_HIP_CONTROLLER_HPP
 #define IWBC_HIP_CONTROLLER_HPP
 
+#include <array>
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -73,6 +74,14 @@ namespace inria_wbc {
         // computed elsewhere and leaves the reference-driven right-hand sides to the controller; ModelSource
         // (model_source.hpp) computes everything on the device from the robot state (wbcqp_problem_data) and therefore
         // owns the task references too.
+        // the active stabiliser file (filter_size, com, ankle, ffda) with the controller's dt and the contacts' normal
+        struct StabilizerParams {
+            int window = 1;
+            double dt = 0.001;
+            std::array<double, 6> com{}, ankle{};
+            std::array<double, 3> ffda{}, normal{{0.0, 0.0, 1.0}};
+        };
+
         class ProblemSource {
         public:
             virtual ~ProblemSource() {}
@@ -109,6 +118,15 @@ namespace inria_wbc {
             virtual void add_foot_mass(const MatrixXd&, const std::string&, const std::string&, MatrixXd&, MatrixXd&) const
             {
                 IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
+            }
+            // One tick of the stabiliser (wbcqp_stabilize_host) on the source's stored references: com, acom and the two ankle frames are observed at
+            // (q, v); wrench is B x 12 (lf_force, lf_torque, rf_force, rf_torque); feet_forces_prev: B x 24, the previous solution's point forces of
+            // contact_lfoot then contact_rfoot, or null.  state: [B][wbcqp_stabilizer_state_bytes] bytes, sized and zeroed here when it does not fit.
+            // ref_out [B][nref] is what the tick reads instead of the stored references, which are not touched.  Only a source with a model can
+            virtual void stabilize(const StabilizerParams&, const MatrixXd&, const MatrixXd&, const MatrixXd&, const double*, std::vector<unsigned char>&,
+                                   std::vector<double>&, VectorXi&, MatrixXd&)
+            {
+                IWBC_ERROR("this problem source has no model: the stabilizer needs a model-driven source (CONTROLLER.model)");
             }
             // whether the source holds a kinematic model (what observe() and check_collisions() need)
             virtual bool has_model() const { return false; }
@@ -430,7 +448,7 @@ namespace inria_wbc {
                     // rows, QP and integration in one trip to the device: only the state and the references go up, the solution
                     // and the integrated state come back.  The rows stay on the device; cost() fetches them when somebody asks.
                     wbcqp_tick_io io{};
-                    io.state = {q.data.data(), dq.data.data(), source_->reference_data(), mom6.data()};
+                    io.state = {q.data.data(), dq.data.data(), tick_references_ ? tick_references_ : source_->reference_data(), mom6.data()};
                     io.rows = in;
                     io.rows.M = io.rows.h = io.rows.A = io.rows.b1 = io.rows.Ac = io.rows.bc = io.rows.blb = io.rows.bub = io.rows.Acop = nullptr;
                     last_q_ = q;
@@ -614,6 +632,7 @@ namespace inria_wbc {
             ComputedAt obs_at_; // the state and the source the four above were made for
 
             std::shared_ptr<ProblemSource> source_;
+            const double* tick_references_ = nullptr; // [batch][nref] read by the next tick instead of the source's stored references (the stabiliser's ref_out)
             TickInputs in_;
             MatrixXd last_q_, last_v_;
             bool rows_valid_ = false;

@@ -1,16 +1,30 @@
 // "humanoid-pos-tracker" and "talos-pos-tracker" (/root/reference/src/controllers/humanoid_pos_tracker.cpp:35,
-// /root/reference/src/controllers/talos_pos_tracker.cpp:35): the registration names and constructor signature of the
-// reference's two humanoid controllers, so that a configuration file that names them loads here.  HumanoidPosTracker's
-// update() is the plain PosTracker tick: what the reference adds around it -- the stabiliser (CoM / ankle / ZMP admittance on
-// force-torque and IMU data, humanoid_pos_tracker.cpp:133-260), the CoP estimator and its filters -- is host-side signal
-// processing outside the hot path (OUT OF SCOPE) and is NOT built; a configuration that switches the
-// stabiliser on is refused with a message that says so.  TalosPosTracker adds the torque-collision safety
-// (talos_pos_tracker.cpp:62-158) for every instance of the batch: before a tick's solve the measured joint torques are
-// compared with tau() as the previous tick left it, through wbcqp_detect_torque_collisions_host (a moving average over
-// filter_size samples, max_invalid + 1 consecutive same-signed violations).  The torso-roll clamp of its constructor is not built.
+// /root/reference/src/controllers/talos_pos_tracker.cpp:35): the reference's two humanoid controllers, under their registration names and with
+// their constructor signature, for B instances.
+//
+// HumanoidPosTracker adds the STABILISER around the tick (humanoid_pos_tracker.cpp:41-131 parse, :134-302 update): with
+// CONTROLLER.stabilizer.activated it reads params_fixed_base / params_ss / params_ds (files relative to base_path: filter_size, com, ankle,
+// ffda, use_zmp), and update(sensor_data) requires lf_force, rf_force, lf_torque, rf_torque and imu_vel (B x 3 each, or three numbers for all
+// instances), runs wbcqp_stabilize_host on the controller's stored references with com, acom and the two ankle frames observed at the state the
+// PREVIOUS tick's rows were formed at (the reference's tsid data lags by one tick; on the first tick: the constructor's state) and with the
+// previous solution's contact forces, and ticks on the stabilised references.  The stored references are never touched, which is the
+// reference's restore step.  An instance whose CoP or ground force fails the reference's sanity checks raises the reference's message with
+// the instance appended, before the solve and after every filter has advanced.  cop() is the valid CoP per instance (NaN where none),
+// stabilizer_flags() the WBCQP_STAB_* bits.  set_behavior_type selects the file; a change of filter_size starts fresh filters (the
+// reference resizes its buffers in place).
+// NOT built (include/wbcqp.h): the ZMP force distributor -- `use_zmp: true` in the ACTIVE file is refused, set use_zmp:
+// false; the momentum / IMU admittances (use_momentum is read by nobody in the reference's update either; imu_vel is required and unused, as
+// there); default gains -- activated: true without the three params_* keys is refused.
+//
+// TalosPosTracker adds the torque-collision safety (talos_pos_tracker.cpp:62-158) for every instance of the batch: before a tick's solve the
+// measured joint torques are compared with tau() as the previous tick left it, through wbcqp_detect_torque_collisions_host (a moving average
+// over filter_size samples, max_invalid + 1 consecutive same-signed violations).  The torso-roll clamp of its constructor is not built.
 #ifndef IWBC_HIP_HUMANOID_POS_TRACKER_HPP
 #define IWBC_HIP_HUMANOID_POS_TRACKER_HPP
 
+#include <cmath>
+#include <limits>
+#include <map>
 #include <inria_wbc/controllers/pos_tracker.hpp>
 
 namespace inria_wbc {
@@ -20,20 +34,157 @@ namespace inria_wbc {
             explicit HumanoidPosTracker(const yaml::Node& config) : PosTracker(config)
             {
                 behavior_type_ = behavior_types::FIXED_BASE; // humanoid_pos_tracker.cpp:39
-                yaml::Node c = IWBC_CHECK(config["CONTROLLER"]);
-                if (c["stabilizer"] && c["stabilizer"]["activated"] && c["stabilizer"]["activated"].as<bool>())
-                    IWBC_ERROR("humanoid-pos-tracker: stabilizer.activated is true, but the stabilizer (CoM / ankle / ZMP admittance, CoP "
-                               "estimator, sensor filters) is outside the batched hot path and is not part of this build; set "
-                               "stabilizer.activated: false");
-                if (verbose_) std::cout << "Humanoid pos tracker initialized (plain tick: no stabilizer in this build)" << std::endl;
+                parse_stabilizer(IWBC_CHECK(config["CONTROLLER"]));
+                if (verbose_) std::cout << "Humanoid pos tracker initialized (stabilizer: " << _use_stabilizer << ")" << std::endl;
             }
             // the reference accepts FIXED_BASE / SINGLE_SUPPORT / DOUBLE_SUPPORT only (humanoid_pos_tracker.cpp:116-131)
             void set_behavior_type(const std::string& bt) override
             {
                 if (bt != behavior_types::FIXED_BASE && bt != behavior_types::SINGLE_SUPPORT && bt != behavior_types::DOUBLE_SUPPORT)
                     IWBC_ERROR("_stabilizer_configs does not have ", bt);
+                if (_use_stabilizer) _check_active(bt);
                 Controller::set_behavior_type(bt);
             }
+
+            void update(const SensorData& sensor_data = {}) override
+            {
+                if (!_use_stabilizer) {
+                    PosTracker::update(sensor_data);
+                    return;
+                }
+                const StabilizerConfig& cfg = _check_active(behavior_type_);
+                const int B = batch_size();
+                MatrixXd wrench(B, 12);
+                _sensor(sensor_data, "lf_force", "the stabilizer needs the LF force", wrench, 0);
+                _sensor(sensor_data, "rf_force", "the stabilizer needs the RF force", wrench, 6);
+                _sensor(sensor_data, "lf_torque", "the stabilizer needs the LF torque", wrench, 3);
+                _sensor(sensor_data, "rf_torque", "the stabilizer needs the RF torque", wrench, 9);
+                IWBC_ASSERT(sensor_data.find("imu_vel") != sensor_data.end(), "the stabilizer imu needs angular velocity");
+                StabilizerParams p;
+                p.window = cfg.filter_size;
+                p.dt = dt_;
+                p.com = cfg.com;
+                p.ankle = cfg.ankle;
+                p.ffda = cfg.ffda;
+                if (!_stack().contacts().empty()) p.normal = _stack().contacts()[0].normal;
+                // the model state the reference's stabiliser sees: the one the previous tick's rows were formed at
+                const bool lagged = q_tsid_prev_.rows == B && B > 0;
+                const MatrixXd& q = lagged ? q_tsid_prev_ : q_tsid_;
+                const MatrixXd& v = lagged ? v_tsid_prev_ : v_tsid_;
+                // the previous solution's forces of both feet, when both were in contact then
+                MatrixXd feet;
+                auto lf = activated_contacts_forces_.find("contact_lfoot"), rf = activated_contacts_forces_.find("contact_rfoot");
+                if (lf != activated_contacts_forces_.end() && rf != activated_contacts_forces_.end() && lf->second.rows == B && rf->second.rows == B) {
+                    feet = MatrixXd(B, 24);
+                    for (int i = 0; i < B; ++i) {
+                        std::copy(lf->second.row(i), lf->second.row(i) + 12, feet.row(i));
+                        std::copy(rf->second.row(i), rf->second.row(i) + 12, feet.row(i) + 12);
+                    }
+                }
+                if (cfg.filter_size != _stab_window) _stab_state.clear(); // fresh filters
+                _stab_window = cfg.filter_size;
+                MatrixXd cops;
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                source_->stabilize(p, q, v, wrench, feet.rows ? feet.data.data() : nullptr, _stab_state, _stab_ref, _stab_flags, cops);
+                _cop = MatrixXd(B, 2, std::numeric_limits<double>::quiet_NaN());
+                for (int i = 0; i < B; ++i) {
+                    const int f = _stab_flags[i];
+                    const int which = (f & WBCQP_STAB_COP) ? 0 : (f & WBCQP_STAB_LCOP) ? 1 : (f & WBCQP_STAB_RCOP) ? 2 : -1;
+                    if (which >= 0) { _cop(i, 0) = cops(i, 2 * which); _cop(i, 1) = cops(i, 2 * which + 1); }
+                }
+                for (int i = 0; i < B; ++i) {
+                    if (_stab_flags[i] & WBCQP_STAB_ERR_COP)
+                        IWBC_ERROR("com_admittance : something is wrong with input cop_filtered, check sensor measurment: ", std::fabs(_cop(i, 0)), " ",
+                                   std::fabs(_cop(i, 1)), " [instance ", i, "]");
+                    if (_stab_flags[i] & WBCQP_STAB_ERR_FORCE)
+                        IWBC_ERROR("zmp_distributor_admittance : ground force is more than 10*M*g , check sensor measurment [instance ", i, "]");
+                }
+                tick_references_ = _stab_ref.data();
+                try {
+                    PosTracker::update(sensor_data);
+                }
+                catch (...) {
+                    tick_references_ = nullptr;
+                    throw;
+                }
+                tick_references_ = nullptr;
+            }
+
+            bool stabilizer_activated() const { return _use_stabilizer; }
+            // the valid CoP of the last update per instance (combined, else left, else right), NaN where none is valid: B x 2
+            const MatrixXd& cop() const { return _cop; }
+            // WBCQP_STAB_* of the last update, one per instance
+            const VectorXi& stabilizer_flags() const { return _stab_flags; }
+            // the references the last stabilised tick read: B x nref (empty before the first one)
+            const std::vector<double>& stabilized_references() const { return _stab_ref; }
+
+        protected:
+            struct StabilizerConfig {
+                int filter_size = 1;
+                std::array<double, 6> com{}, ankle{};
+                std::array<double, 3> ffda{};
+                bool use_zmp = false;
+            };
+            // humanoid_pos_tracker.cpp:41-114
+            void parse_stabilizer(const yaml::Node& c)
+            {
+                yaml::Node st = c["stabilizer"];
+                if (!st || !st["activated"] || !st["activated"].as<bool>()) return;
+                if (!st["params_fixed_base"] || !st["params_ss"] || !st["params_ds"])
+                    IWBC_ERROR("humanoid-pos-tracker: stabilizer.activated is true, but stabilizer.params_fixed_base / params_ss / params_ds are missing; "
+                               "default stabilizer gains are not part of this build");
+                _stabilizer_configs[behavior_types::FIXED_BASE] = _parse_file(st["params_fixed_base"].as<std::string>());
+                _stabilizer_configs[behavior_types::SINGLE_SUPPORT] = _parse_file(st["params_ss"].as<std::string>());
+                _stabilizer_configs[behavior_types::DOUBLE_SUPPORT] = _parse_file(st["params_ds"].as<std::string>());
+                _use_stabilizer = true;
+                _check_active(behavior_type_);
+            }
+            StabilizerConfig _parse_file(const std::string& file) const
+            {
+                const std::string path = file.size() && file[0] == '/' ? file : base_path() + "/" + file;
+                yaml::Node n = IWBC_CHECK(yaml::LoadFile(path));
+                StabilizerConfig cfg;
+                cfg.filter_size = IWBC_CHECK(n["filter_size"].as<int>());
+                IWBC_ASSERT(cfg.filter_size >= 1 && cfg.filter_size <= WBCQP_MAX_STAB_WINDOW, path, ": filter_size must be in [1, ", WBCQP_MAX_STAB_WINDOW, "]");
+                auto vec = [&](const char* key, size_t len, double* out) {
+                    auto v = IWBC_CHECK(n[key].as<std::vector<double>>());
+                    IWBC_ASSERT(v.size() == len, path, ": you need ", len, " coefficients in ", key);
+                    std::copy(v.begin(), v.end(), out);
+                };
+                vec("com", 6, cfg.com.data());
+                vec("ankle", 6, cfg.ankle.data());
+                vec("ffda", 3, cfg.ffda.data());
+                cfg.use_zmp = n["use_zmp"] ? n["use_zmp"].as<bool>() : false;
+                return cfg;
+            }
+            const StabilizerConfig& _check_active(const std::string& bt) const
+            {
+                auto it = _stabilizer_configs.find(bt);
+                if (it == _stabilizer_configs.end()) IWBC_ERROR("_stabilizer_configs does not have ", bt);
+                if (it->second.use_zmp)
+                    IWBC_ERROR("humanoid-pos-tracker: use_zmp is true in the stabilizer file of ", bt, ", but the ZMP force distributor is not part of this "
+                               "build; set use_zmp: false");
+                return it->second;
+            }
+            // a sensor of the stabiliser into three columns of the wrench rows: B x 3, or three numbers for every instance
+            void _sensor(const SensorData& sd, const char* key, const char* missing, MatrixXd& wrench, int at) const
+            {
+                auto it = sd.find(key);
+                IWBC_ASSERT(it != sd.end(), missing);
+                const MatrixXd& s = it->second;
+                const bool one = (int)s.data.size() == 3;
+                IWBC_ASSERT(one || (s.rows == wrench.rows && s.cols == 3), key, ": 3 numbers per instance (", wrench.rows, " x 3), or 3 numbers for all");
+                for (int i = 0; i < wrench.rows; ++i)
+                    for (int k = 0; k < 3; ++k) wrench(i, at + k) = one ? s.data[k] : s(i, k);
+            }
+
+            bool _use_stabilizer = false;
+            std::map<std::string, StabilizerConfig> _stabilizer_configs;
+            int _stab_window = 0;
+            std::vector<unsigned char> _stab_state; // [batch][state bytes]: empty or all-zero = fresh filters
+            std::vector<double> _stab_ref;
+            VectorXi _stab_flags;
+            MatrixXd _cop;
         };
 
         class TalosPosTracker : public HumanoidPosTracker {

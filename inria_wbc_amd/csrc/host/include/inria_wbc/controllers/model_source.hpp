@@ -276,6 +276,65 @@ namespace inria_wbc {
                     IWBC_ERROR("wbcqp_observe_host failed: ", wbcqp_last_error(handle_));
             }
 
+            // wbcqp_observe_acom_host (com, acom, the two ankle frames) and wbcqp_stabilize_host on the slot in use.  "The ankle" is the frame the
+            // foot's contact tracks (humanoid_pos_tracker.cpp:163-166), also while that contact is removed; the offsets are found by the reference's
+            // task names com, lf, rf, torso, contact_lfoot, contact_rfoot
+            void stabilize(const StabilizerParams& p, const MatrixXd& q, const MatrixXd& v, const MatrixXd& wrench, const double* feet_forces_prev,
+                           std::vector<unsigned char>& state, std::vector<double>& ref_out, VectorXi& flags, MatrixXd& cop) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                IWBC_BOUND_ALIASES(*cur_)
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq() && v.rows == batch_ && v.cols == robot_->nv(), "one state row per instance");
+                IWBC_ASSERT(wrench.rows == batch_ && wrench.cols == 12, "one row of 12 sensor values per instance");
+                wbcqp_stabilizer s{};
+                s.window = p.window;
+                s.dt = p.dt;
+                const wbcqp_model md = robot_->c_model();
+                for (int b = 0; b < md.nbody; ++b) s.mass += md.inertia[10 * b];
+                std::copy(p.com.begin(), p.com.end(), s.com_gains);
+                std::copy(p.ankle.begin(), p.ankle.end(), s.ankle_gains);
+                std::copy(p.ffda.begin(), p.ffda.end(), s.ffda_gains);
+                std::copy(p.normal.begin(), p.normal.end(), s.normal);
+                s.nref = nref_;
+                s.com_ref = s.lf_ref = s.rf_ref = s.torso_ref = -1;
+                int lf_frame = -1, rf_frame = -1;
+                for (size_t i = 0; i < tasks_.size(); ++i) {
+                    if (tasks_[i].kind == WBCQP_T_COM) s.com_ref = tasks_[i].ref;
+                    if (tasks_[i].kind != WBCQP_T_SE3) continue;
+                    if (names_[i] == "lf") { s.lf_ref = tasks_[i].ref; lf_frame = tasks_[i].frame; }
+                    if (names_[i] == "rf") { s.rf_ref = tasks_[i].ref; rf_frame = tasks_[i].frame; }
+                    if (names_[i] == "torso") s.torso_ref = tasks_[i].ref;
+                }
+                IWBC_ASSERT(s.com_ref >= 0 && s.lf_ref >= 0 && s.rf_ref >= 0 && s.torso_ref >= 0, "the stabilizer needs the tasks com, lf, rf and torso");
+                s.lf_contact_ref = s.rf_contact_ref = -1;
+                for (size_t c = 0; c < contact_names_.size(); ++c) {
+                    ankle_frame_[contact_names_[c]] = contact_frame_[c];
+                    if (contact_names_[c] == "contact_lfoot") s.lf_contact_ref = contact_ref_[c];
+                    if (contact_names_[c] == "contact_rfoot") s.rf_contact_ref = contact_ref_[c];
+                }
+                if (ankle_frame_.count("contact_lfoot")) lf_frame = ankle_frame_["contact_lfoot"];
+                if (ankle_frame_.count("contact_rfoot")) rf_frame = ankle_frame_["contact_rfoot"];
+                s.lf_force_col = 0; // (feet_forces_prev is laid out here: left then right, whatever the previous tick's contact set was)
+                s.rf_force_col = 12;
+                s.lf_pos = 9;
+                s.rf_pos = 21;
+                const size_t bytes = (size_t)wbcqp_stabilizer_state_bytes(&s);
+                IWBC_ASSERT(bytes > 0, "stabilizer: filter_size must be in [1, ", WBCQP_MAX_STAB_WINDOW, "] and every gain finite");
+                if (state.size() != bytes * batch_) state.assign(bytes * batch_, 0); // (fresh filters, also after a change of filter_size)
+                select_frames(observed_, {robot_->frame_names()[lf_frame], robot_->frame_names()[rf_frame]}, wbcqp_set_observed_frames, "wbcqp_set_observed_frames");
+                MatrixXd com(batch_, 3), acom(batch_, 3), place(batch_, 24);
+                const wbcqp_observables obs = {com.data.data(), nullptr, place.data.data(), nullptr};
+                if (wbcqp_observe_acom_host(handle_, slot_, batch_, q.data.data(), v.data.data(), &obs, acom.data.data()) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_observe_acom_host failed: ", wbcqp_last_error(handle_));
+                ref_out.assign(ref_.size(), 0.0);
+                flags.assign(batch_, 0);
+                cop = MatrixXd(batch_, 6);
+                const wbcqp_stab_inputs in = {ref_.data(), wrench.data.data(), com.data.data(), acom.data.data(), place.data.data(), 24, feet_forces_prev, 24};
+                const wbcqp_stab_outputs out = {ref_out.data(), flags.data(), cop.data.data()};
+                if (wbcqp_stabilize_host(handle_, &s, batch_, &in, state.data(), &out) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_stabilize_host failed: ", wbcqp_last_error(handle_));
+            }
+
             // wbcqp_inverse_dynamics_host on the slot in use; the selection of frames goes to the device when it changes, not per call
             void inverse_dynamics(const MatrixXd& q, const MatrixXd& v, const MatrixXd& a, const std::vector<std::string>& frames, const MatrixXd& wrenches,
                                   MatrixXd& tau) override
@@ -454,6 +513,7 @@ namespace inria_wbc {
             std::map<int, std::pair<std::string, std::vector<std::pair<std::string, int>>>> spheres_;
             Bound* cur_ = nullptr;
             std::map<std::string, std::vector<double>> named_;
+            std::map<std::string, int> ankle_frame_; // contact name -> the frame it tracks, kept while the contact is removed
             MatrixXd com_pos_, com_vel_;
         };
 #undef IWBC_BOUND_ALIASES

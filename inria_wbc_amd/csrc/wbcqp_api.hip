@@ -8,7 +8,7 @@
 // This file holds the exported entry points; the host code behind them is in the wbcqp_host_*.hpp headers, included here and nowhere else (the library
 // stays ONE translation unit): the handle, the description of a call's arrays and the staging (handle), structure -> sizes and LDS layouts (derive),
 // arguments -> kernel launches (launch), reference programs (program), the loops over ticks (rollout), the model queries on a fleet's states (queries),
-// the torque monitor on a fleet's streams of joint torques (monitor).
+// the torque monitor on a fleet's streams of joint torques and the stabiliser on its streams of foot wrenches (monitor).
 #include "wbcqp_host_handle.hpp"
 #include "wbcqp_host_derive.hpp"
 #include "wbcqp_host_launch.hpp"
@@ -584,27 +584,42 @@ int wbcqp_set_observed_frames(wbcqp_handle* h, int slot, int n_frames, const int
     return set_frame_selection(h, slot, &Slot::observed, n_frames, frames, WBCQP_MAX_OBSERVED, "an observed frame", "the observed frames");
 }
 
-int wbcqp_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream)
+int wbcqp_observe_acom(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* acom, void* stream)
 {
     const Slot* s = nullptr;
-    WB_TRY(check_observe(h, slot, batch, q, v, out, &s));
+    const wbcqp_observables none = {};
+    if (acom && !out) out = &none; // (acom alone)
+    WB_TRY(check_observe(h, slot, batch, q, v, out, acom, &s));
     if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    return launch_observe(h, *s, batch, q, v, *out, static_cast<hipStream_t>(stream));
+    return launch_observe(h, *s, batch, q, v, *out, acom, static_cast<hipStream_t>(stream));
 }
 
-int wbcqp_observe_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out)
+int wbcqp_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* stream)
+{
+    return wbcqp_observe_acom(h, slot, batch, q, v, out, nullptr, stream);
+}
+
+int wbcqp_observe_acom_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, void* acom)
 {
     const Slot* s = nullptr;
-    WB_TRY(check_observe(h, slot, batch, q, v, out, &s));
+    const wbcqp_observables none = {};
+    if (acom && !out) out = &none;
+    WB_TRY(check_observe(h, slot, batch, q, v, out, acom, &s));
     if (!s) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const size_t es = elem_size(h), B = (size_t)batch, nf = (size_t)s->observed.n;
     Arr up[2] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * s->terms.nv * es, 0}};
-    Arr dn[4] = {{-1, out->com, B * 3 * es, 0}, {-1, out->vcom, B * 3 * es, 0}, {-1, out->placement, B * nf * 12 * es, 0}, {-1, out->velocity, B * nf * 6 * es, 0}};
+    Arr dn[5] = {{-1, out->com, B * 3 * es, 0}, {-1, out->vcom, B * 3 * es, 0}, {-1, out->placement, B * nf * 12 * es, 0}, {-1, out->velocity, B * nf * 6 * es, 0},
+                 {-1, acom, B * 3 * es, 0}};
     return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
-        return launch_observe(h, *s, batch, u[0], u[1], wbcqp_observables{d[0], d[1], d[2], d[3]}, nullptr);
+        return launch_observe(h, *s, batch, u[0], u[1], wbcqp_observables{d[0], d[1], d[2], d[3]}, d[4], nullptr);
     });
+}
+
+int wbcqp_observe_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out)
+{
+    return wbcqp_observe_acom_host(h, slot, batch, q, v, out, nullptr);
 }
 
 int wbcqp_set_collision_spheres(wbcqp_handle* h, int slot, const wbcqp_sphere_model* sm) { return set_collision_spheres(h, slot, sm); }
@@ -701,6 +716,47 @@ int wbcqp_detect_torque_collisions_host(wbcqp_handle* h, const wbcqp_torque_moni
         const wbcqp_torque_checks dev = {static_cast<int32_t*>(d[0]), static_cast<uint64_t*>(d[1]), d[2], d[3], static_cast<int32_t*>(d[4]),
                                          static_cast<int32_t*>(d[5])};
         return launch_torque_monitor(h, D, batch, n_ticks, u[0], ldt, u[1], u[2], d[6], dev, nullptr);
+    });
+}
+
+int64_t wbcqp_stabilizer_state_bytes(const wbcqp_stabilizer* stabilizer)
+{
+    return stabilizer_flaw(stabilizer) ? 0 : (int64_t)(8 * stab_state_doubles(stabilizer->window));
+}
+
+int wbcqp_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state, const wbcqp_stab_outputs* out,
+                    void* stream)
+{
+    StabDev D;
+    bool run = false;
+    WB_TRY(check_stabilize(h, stabilizer, batch, in, state, out, &D, &run));
+    if (!run) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_stabilize(h, D, batch, *in, state, state, out ? *out : wbcqp_stab_outputs{}, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_stabilize_host(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state,
+                         const wbcqp_stab_outputs* out)
+{
+    StabDev D;
+    bool run = false;
+    WB_TRY(check_stabilize(h, stabilizer, batch, in, state, out, &D, &run));
+    if (!run) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const wbcqp_stab_outputs o = out ? *out : wbcqp_stab_outputs{};
+    const size_t es = elem_size(h), B = (size_t)batch, sb = B * 8 * stab_state_doubles(D.window);
+    // (placement and x_prev: rows ldp / ldx apart, the last one read up to the feet's translations / the contacts' forces)
+    const int last_col = std::max(D.lf_col, D.rf_col);
+    const size_t reach_p = (size_t)std::max(D.lf_pos, D.rf_pos) + 3, reach_x = last_col >= 0 ? (size_t)last_col + 12 : 0;
+    Arr up[7] = {{-1, const_cast<void*>(in->ref), B * D.nref * es, 0}, {-1, const_cast<void*>(in->wrench), B * 12 * es, 0},
+                 {-1, const_cast<void*>(in->com), B * 3 * es, 0}, {-1, const_cast<void*>(in->acom), B * 3 * es, 0},
+                 {-1, const_cast<void*>(in->placement), ((B - 1) * (size_t)in->ldp + reach_p) * es, 0},
+                 {-1, const_cast<void*>(reach_x ? in->x_prev : nullptr), reach_x ? ((B - 1) * (size_t)in->ldx + reach_x) * es : 0, 0},
+                 {-1, state, sb, 0}};
+    Arr dn[4] = {{-1, o.ref_out, B * D.nref * es, 0}, {-1, o.flags, B * 4, 0}, {-1, o.cop, B * 6 * es, 0}, {-1, state, sb, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        const wbcqp_stab_inputs din = {u[0], u[1], u[2], u[3], u[4], in->ldp, u[5], in->ldx};
+        return launch_stabilize(h, D, batch, din, u[6], d[3], wbcqp_stab_outputs{d[0], static_cast<int32_t*>(d[1]), d[2]}, nullptr);
     });
 }
 

@@ -106,7 +106,7 @@ int set_collision_spheres(wbcqp_handle* h, int slot, const wbcqp_sphere_model* s
 
 // ---- the checks: what the device-pointer and the host-pointer entry point of a query refuse, before anything is staged or launched ----------------
 // *s: the slot, or null where the call is accepted and there is nothing to do (batch == 0, no output asked for)
-int check_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, const Slot** s)
+int check_observe(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const wbcqp_observables* out, const void* acom, const Slot** s)
 {
     *s = nullptr;
     if (!h) return WBCQP_ERR_INVALID;
@@ -117,7 +117,8 @@ int check_observe(wbcqp_handle* h, int slot, int batch, const void* q, const voi
     if ((out->placement || out->velocity) && sl->observed.n == 0)
         return fail(h, WBCQP_ERR_INVALID, "placement / velocity asked for, but no frames are selected (wbcqp_set_observed_frames)");
     if ((out->vcom || out->velocity) && !v) return fail(h, WBCQP_ERR_INVALID, "vcom / velocity asked for, but v is NULL");
-    if (batch == 0 || (!out->com && !out->vcom && !out->placement && !out->velocity)) return WBCQP_OK;
+    if (acom && !v) return fail(h, WBCQP_ERR_INVALID, "acom asked for, but v is NULL");
+    if (batch == 0 || (!out->com && !out->vcom && !out->placement && !out->velocity && !acom)) return WBCQP_OK;
     if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
     *s = sl;
     return WBCQP_OK;
@@ -153,13 +154,14 @@ int check_inverse_dynamics(wbcqp_handle* h, int slot, int batch, const void* q, 
 }
 
 // ---- the launches: batch > 0, arguments checked, the handle's device current ---------------------------------------------------------------------
-int launch_observe(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, const wbcqp_observables& out, hipStream_t stream)
+int launch_observe(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, const wbcqp_observables& out, void* acom, hipStream_t stream)
 {
     const ObserveDev D = observe_dev(s.terms, s.observed, out.placement || out.velocity);
     return with_dtype(h, [&](auto tag) -> int {
         using TI = WB_TI(tag);
-        const ObserveArgs<TI> a{D, static_cast<const TI*>(q), (out.vcom || out.velocity) ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out.com),
-                                static_cast<TI*>(out.vcom), static_cast<TI*>(out.placement), static_cast<TI*>(out.velocity), batch};
+        const ObserveArgs<TI> a{D, static_cast<const TI*>(q), (out.vcom || out.velocity || acom) ? static_cast<const TI*>(v) : nullptr,
+                                static_cast<TI*>(out.com), static_cast<TI*>(out.vcom), static_cast<TI*>(out.placement), static_cast<TI*>(out.velocity), batch,
+                                static_cast<TI*>(acom)};
         hipLaunchKernelGGL(observe_kernel<TI>, dim3(query_blocks(batch)), dim3(kObserveThreads), observe_lds_bytes(D.n_frames), stream, a);
         HIP_TRY(h, hipGetLastError());
         return WBCQP_OK;

@@ -42,6 +42,7 @@ struct ObserveArgs {
     const TI *q, *v;                       // [batch][nq], [batch][nv] (v: null when no velocity is asked for)
     TI *com, *vcom, *placement, *velocity; // [batch][3], [batch][3], [batch][n_frames][12], [batch][n_frames][6]; each may be null
     int batch;
+    TI* acom;                              // [batch][3] or null: the CoM's acceleration with zero joint accelerations and no gravity
 };
 
 // dynamic LDS of one workgroup: every wave stages its instance's frames
@@ -144,9 +145,12 @@ __global__ __launch_bounds__(kObserveThreads) void observe_kernel(const ObserveA
     }
     // spatial velocity about the world's origin, world-aligned: a path sum of the joints' own velocities
     V3 ov = {0.0, 0.0, 0.0}, ow = {0.0, 0.0, 0.0};
+    V3 jv = ov, jw = ow; // the joint's own velocity, world-aligned
     if (vel) {
         ow = mv(R, wJ);
         ov = mv(R, vJ) + cross(p, ow);
+        jv = ov;
+        jw = ow;
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
             if (r < D.nrounds) {
@@ -157,8 +161,23 @@ __global__ __launch_bounds__(kObserveThreads) void observe_kernel(const ObserveA
             }
         }
     }
-    // ---- centre of mass and its velocity: sums over the bodies in wave_sum's fixed order ----------------------------------------
-    if (args.com || args.vcom) {
+    // bias acceleration (zero joint accelerations, no gravity): a = a_parent + v x vJ, a path sum as in the rows kernel (wbcqp_terms.hpp, phase 1)
+    V3 oa = {0.0, 0.0, 0.0}, oal = {0.0, 0.0, 0.0};
+    if (args.acom) { // wave-uniform; refused on the host without v
+        oa = cross(ow, jv) + cross(ov, jw);
+        oal = cross(ow, jw);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            if (r < D.nrounds) {
+                const int src = anc[r] >= 0 ? anc[r] : lane;
+                const V3 a = {__shfl(oa.x, src, kWave), __shfl(oa.y, src, kWave), __shfl(oa.z, src, kWave)};
+                const V3 b = {__shfl(oal.x, src, kWave), __shfl(oal.y, src, kWave), __shfl(oal.z, src, kWave)};
+                if (anc[r] >= 0) { oa = oa + a; oal = oal + b; }
+            }
+        }
+    }
+    // ---- centre of mass, its velocity and its bias acceleration: sums over the bodies in wave_sum's fixed order ------------------
+    if (args.com || args.vcom || args.acom) {
         const double m = body ? mass_b : 0.0;
         const V3 hc = m * (mv(R, c_b) + p);
         const double mt = wave_sum(m);
@@ -171,6 +190,12 @@ __global__ __launch_bounds__(kObserveThreads) void observe_kernel(const ObserveA
             const V3 hl = m * ov + cross(ow, hc);
             const V3 s = {wave_sum(hl.x), wave_sum(hl.y), wave_sum(hl.z)};
             if (lane < 3) args.vcom[(size_t)inst * 3 + lane] = (TI)(imass * (lane == 0 ? s.x : lane == 1 ? s.y : s.z));
+        }
+        if (args.acom) { // the bodies' bias forces' linear part, f = m a + al x h_c + w x h_l, over the total mass
+            const V3 hl = m * ov + cross(ow, hc);
+            const V3 fl = m * oa + cross(oal, hc) + cross(ow, hl);
+            const V3 s = {wave_sum(fl.x), wave_sum(fl.y), wave_sum(fl.z)};
+            if (lane < 3) args.acom[(size_t)inst * 3 + lane] = (TI)(imass * (lane == 0 ? s.x : lane == 1 ? s.y : s.z));
         }
     }
     // ---- lanes = observed frames ------------------------------------------------------------------------------------------------

@@ -165,6 +165,24 @@ def emit_icub_model_files():
         f.write("BEHAVIOR:\n  name: humanoid::move_com\n  trajectory_duration: 1\n  targets: [[0, 0, -0.05]]\n  mask: 001\n  absolute: false\n  loop: true\n")
 
 
+def emit_stabilizer_files():
+    """The reference's three stabiliser files per humanoid (use_zmp: false: the ZMP distributor is not built) and a CONTROLLER tree on the model
+    that switches the stabiliser on, as etc/talos/talos_pos_tracker.yaml and etc/icub/humanoid_pos_tracker.yaml do."""
+    from inria_wbc_amd import stabilizer as stb
+    for robot, model_file in (("talos", "talos_like.model.yaml"), ("icub", "icub_like.model.yaml")):
+        d = os.path.join(ROOT, "configs", robot)
+        for kind, cfg in stb.STAB_FILES[robot].items():
+            with open(os.path.join(d, "stab_%s.yaml" % kind), "w") as f:
+                f.write("# stabiliser gains, %s (schema and values of inria_wbc's etc/%s/stab_%s.yaml; use_zmp off)\n" % (kind, robot, kind))
+                f.write(stb.stab_file_text(cfg))
+        with open(os.path.join(d, "pos_tracker_stab.yaml"), "w") as f:
+            f.write("# CONTROLLER tree of the humanoid controller with the stabiliser on (the `stabilizer` block of inria_wbc's controller files)\n")
+            f.write("CONTROLLER:\n  name: humanoid-pos-tracker\n  solver: hip-batched\n  base_path: .\n  model: %s\n  frames: frames.yaml\n" % model_file)
+            f.write("  ref_config: inria_start\n  tasks: tasks.yaml\n  dt: 0.001\n  floating_base: true\n  closed_loop: false\n  verbose: false\n  batch: 8\n")
+            f.write("  stabilizer:\n    activated: true\n    params_ss: stab_single_support.yaml\n    params_ds: stab_double_support.yaml\n")
+            f.write("    params_fixed_base: stab_fixed_base.yaml\n")
+
+
 def main():
     from inria_wbc_amd import model as mdl
     ROBOTS["talos"] = (talos_with_avoided(), 50, 44, True)
@@ -172,6 +190,7 @@ def main():
     emit_model_files()
     emit_franka_model_files()
     emit_icub_model_files()
+    emit_stabilizer_files()
     for robot, (tasks, nv, na, fb) in ROBOTS.items():
         d = os.path.join(ROOT, "configs", robot)
         os.makedirs(d, exist_ok=True)
