@@ -61,7 +61,9 @@ extern "C" {
  *        from the discrepancy of model and measured joint torques over a stream of ticks, on the device); wbcqp_observe_acom and wbcqp_observe_acom_host (wbcqp_observe with
  *        the CoM's bias acceleration as one more output); wbcqp_stabilizer, wbcqp_stab_inputs, wbcqp_stab_outputs,
  *        wbcqp_stabilizer_state_bytes, wbcqp_stabilize and wbcqp_stabilize_host (the humanoid controllers' stabiliser: CoP estimator, filters and
- *        admittance laws that rewrite a tick's references, on the device).  151 therefore names more than one set of declarations: every one of them
+ *        admittance laws that rewrite a tick's references, on the device); wbcqp_set_force_references (contact force references carried by a tick's
+ *        reference row), wbcqp_zmp_distributor, wbcqp_stabilize_zmp, wbcqp_stabilize_zmp_host, WBCQP_STAB_ZMP and WBCQP_STAB_ERR_ZMP (the stabiliser's
+ *        ZMP force distributor).  151 therefore names more than one set of declarations: every one of them
  *        contains the one before it unchanged (nothing was removed or resized), so a caller checks for a symbol, not for the number
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
@@ -438,6 +440,17 @@ typedef struct {
  * n_sel, n_bound).  A later wbcqp_set_structure on the slot drops the model with the old structure: bind it again (a
  * contact added or removed changes both, pos_tracker.cpp:246-263). */
 int wbcqp_set_model(wbcqp_handle* handle, int slot, const wbcqp_model* model, const wbcqp_taskmap* map);
+/* Contact force references carried by a tick's reference row (tsid's Contact6d::setForceReference; the stabiliser's ZMP distributor writes them).
+ * After wbcqp_set_model, dropped with the model.  force_ref: HOST [nc] offset of contact c's 6-number force reference in a reference row, -1: none (that
+ * contact's entries of b1 stay +0).  weight: HOST [nc][6], the w_f the slot's forcereg_mat = diag(w_f) T was made with (T: force_gen).
+ * With it the rows kernel writes b1[n_dense + n_sel + 6 c + k] = weight[c][k] * ref[force_ref[c] + k] -- one product, in double -- through every path
+ * that runs it: wbcqp_problem_data, wbcqp_tick, wbcqp_tick_host, wbcqp_tick_mixed, the roll-outs (a captured wbcqp_tick_graph keeps what was set when
+ * it was created).  The solve consumes it as any right-hand side: the block's cost is |forcereg_mat f - b1|^2 = |diag(w_f) (T f - f_ref)|^2.
+ * A slot on which the call was never made, or made with every offset -1, produces the bits it produced before this call existed.
+ * WBCQP_ERR_INVALID: a slot without a model; force_ref or weight NULL (nc > 0); an offset below -1; a block [offset, offset + 6) that runs past nref or
+ * overlaps another of these blocks; a weight that is not finite; a weight with weight[c][k] * T[c][k][j] != forcereg_mat[c][k][j] for some j, exactly
+ * (no tolerance; zeros of either sign are equal; a slot whose weights the caller misstates must not solve silently against the wrong right-hand side). */
+int wbcqp_set_force_references(wbcqp_handle* handle, int slot, const int32_t* force_ref, const double* weight);
 /* The checks of wbcqp_set_model without a device (pure host computation, like wbcqp_layout_of): is this tree + these task
  * bindings a valid companion of that structure, and how much LDS does one instance of the rows kernel need.  Error text through
  * wbcqp_last_error(NULL). */
@@ -807,14 +820,16 @@ int wbcqp_detect_torque_collisions_host(wbcqp_handle* handle, const wbcqp_torque
  * frame f).  The reference reads them from the state the PREVIOUS tick's rows were formed at.
  * Every product, sum and quotient rounds once, in the reference's association; rotations go through atan2 / sin / cos and are the only entries that depend
  * on the device's libm.  No atomics, an instance's results depend on its own rows alone (F32 handles read float, compute in double, write float).
- * Not here: the ZMP force distributor (use_zmp: it sets force references and regularisation weights, which live in the slot), the momentum / IMU
- * admittances (the reference's controller never calls them), the torso-roll clamp of TalosPosTracker, a roll-out form (a stabilised tick needs that
- * tick's sensors).  A mixed fleet: one call per contact set on that set's rows. */
+ * Not here: the momentum / IMU admittances and direct_zmp_distributor_admittance (the reference's controller never calls them), the torso-roll clamp
+ * of TalosPosTracker, a roll-out form (a stabilised tick needs that tick's sensors).  The ZMP force distributor (use_zmp) is wbcqp_stabilize_zmp below.
+ * A mixed fleet: one call per contact set on that set's rows. */
 #define WBCQP_MAX_STAB_WINDOW 64
 enum {
     WBCQP_STAB_COP = 1, WBCQP_STAB_LCOP = 2, WBCQP_STAB_RCOP = 4,                               /* the combined / left / right filtered CoP is valid */
     WBCQP_STAB_COM = 8, WBCQP_STAB_LANKLE = 16, WBCQP_STAB_RANKLE = 32, WBCQP_STAB_FFDA = 64, /* the law was applied */
-    WBCQP_STAB_ERR_COP = 128, WBCQP_STAB_ERR_FORCE = 256
+    WBCQP_STAB_ERR_COP = 128, WBCQP_STAB_ERR_FORCE = 256,
+    WBCQP_STAB_ZMP = 512,      /* wbcqp_stabilize_zmp: the ZMP force distributor ran (the force references were formed) */
+    WBCQP_STAB_ERR_ZMP = 1024  /* ... or met the reference's "this case should not exists" */
 };
 typedef struct {
     int32_t window;                              /* filter_size, 1 .. WBCQP_MAX_STAB_WINDOW */
@@ -857,6 +872,45 @@ int wbcqp_stabilize(wbcqp_handle* handle, const wbcqp_stabilizer* stabilizer, in
 /* Same with HOST pointers, state included (staged both ways): through device buffers owned by the handle, blocks until done. */
 int wbcqp_stabilize_host(wbcqp_handle* handle, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state,
                          const wbcqp_stab_outputs* out);
+
+/* ---- The stabiliser's ZMP force distributor (use_zmp: true in the reference's Talos support files) ----
+ * stabilizer.cpp:277-311, 340-440 and humanoid_pos_tracker.cpp:212-224 there: the robot's weight is split between the feet by where the ZMP lies between
+ * them, the split becomes a 6-D force reference per foot, and the contacts' force-regularisation weights become zmp_w.  wbcqp_stabilize_zmp is
+ * wbcqp_stabilize with that law compiled in (a second instantiation of stabilize_kernel: same state, same layout, same
+ * wbcqp_stabilizer_state_bytes); zmp == NULL IS wbcqp_stabilize, bit for bit.
+ *   distribute(z), both contacts active (PL, PR: the xy of the left / right CONTACT reference's translation as it lies in `ref`; all at height 0):
+ *             u = PR - PL, e = u / |u| (u itself where u.u is not > 0: Eigen's normalized()), proj = PR + e ((z - PR) . e),
+ *             L = |PR - PL|, a1 = |proj - PL|, a2 = |PR - proj|;  alpha = a1 / L if |(L - a1) - a2| < 1e-10, else 0 if a1 < a2, else 1 if a1 > a2,
+ *             else the reference throws (only non-finite inputs get there).  Coincident feet: alpha = 0 / 0 = NaN and no throw.
+ *             only the right contact active: alpha = 1, PL = (0, 0); only the left: alpha = 0, PR = (0, 0)
+ *             f_r = ((-alpha) mass) 9.81, f_l = ((-(1 - alpha)) mass) 9.81, tau0 = (-(PR - z)) f_r - (PL - z) f_l  (per coordinate),
+ *             tauR.y = alpha tau0.y, tauL.y = (1 - alpha) tau0.y; tau0.x < 0: tauR.x = tau0.x, tauL.x = 0, otherwise tauR.x = 0, tauL.x = tau0.x
+ *             left = (0, 0, f_l, tauL.y, -tauL.x, 0), right = (0, 0, f_r, tauR.y, -tauR.x, 0); signed zeros as the arithmetic leaves them
+ *   ZMP law   exactly when the CoM law runs (a valid_cop, no guard tripped), after it and before the ankles: t = distribute(zmp) with the CoM law's
+ *             zmp = com.xy - com.z / 9.81 * acom.xy, s = distribute(valid_cop); per foot and entry e = t - s, fref = (t - p e) - (d e) / dt.
+ *             fref of the left / right foot is written at lf_force_ref / rf_force_ref of ref_out (an offset -1: not written), whether or not that
+ *             foot's contact is active, and WBCQP_STAB_ZMP is set.  On a tick where the law does not run the two blocks pass through from `ref`
+ *             (the caller's base row holds zeros there: the reference's "put the force references back").
+ *   guards    far CoP (the CoM law's own, the same valid_cop), then the throw above in either distribute (WBCQP_STAB_ERR_ZMP), then the torso law's
+ *             force guard: the first that trips ends the tick as the guards of wbcqp_stabilize do (ref_out is ref, no law's bit, filters advanced).
+ * Additions, products, quotients and one square root, each rounded once: the force references have no libm tolerance.
+ * The latch.  The reference sets zmp_w on BOTH contact objects the first time the law runs for a robot and never sets it back.  A slot's forcereg_mat is
+ * diag(w_f) T, so the caller keeps two slots per contact set -- one made with the default w_f, one with forcereg_mat = diag(zmp_w) T -- both with
+ * wbcqp_set_force_references, and ticks the fleet through wbcqp_tick_mixed: from the first tick whose flags carry WBCQP_STAB_ZMP robot i is ticked in
+ * the zmp_w slot, for good (three contact sets x two weightings: 6 of the 8 slots). */
+typedef struct {
+    double p[6], d[6];                  /* zmp_p, zmp_d */
+    int32_t lf_force_ref, rf_force_ref; /* offsets of the feet's 6-number force references in a reference row, -1: not written */
+} wbcqp_zmp_distributor;                /* HOST, read before the call returns */
+/* wbcqp_stabilize with the distributor.  alpha (DEVICE, the handle's dtype) [batch][2] or NULL: alpha of the model's ZMP, of the measured one; NaN where
+ * the law did not run.  Refused with WBCQP_ERR_INVALID before anything is launched: everything wbcqp_stabilize refuses; with zmp, a p or d that is not
+ * finite, a force reference offset below -1, a block [offset, offset + 6) that runs past nref or overlaps one of the stabiliser's six blocks or the other
+ * force reference, lf_contact_ref < 0 && rf_contact_ref < 0 (the reference's "is talos jumping ?").  An alpha alone counts as an output. */
+int wbcqp_stabilize_zmp(wbcqp_handle* handle, const wbcqp_stabilizer* stabilizer, const wbcqp_zmp_distributor* zmp, int batch, const wbcqp_stab_inputs* in,
+                        void* state, const wbcqp_stab_outputs* out, void* alpha, void* stream);
+/* Same with HOST pointers (state and alpha included), blocks until done; the same refusals. */
+int wbcqp_stabilize_zmp_host(wbcqp_handle* handle, const wbcqp_stabilizer* stabilizer, const wbcqp_zmp_distributor* zmp, int batch,
+                             const wbcqp_stab_inputs* in, void* state, const wbcqp_stab_outputs* out, void* alpha);
 
 /* ---- References generated on the device from a reference program ----
  * wbcqp_rollout and its companions read the references of n_ticks ticks as one array [n_ticks][batch][nref] (2.44 KB per Talos instance and tick) that the

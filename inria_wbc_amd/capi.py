@@ -35,7 +35,8 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host",
            "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host",
            "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host",
-           "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host")
+           "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host",
+           "wbcqp_set_force_references", "wbcqp_stabilize_zmp", "wbcqp_stabilize_zmp_host")
 OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe writes (wbcqp_observables); per instance 3, 3, n_frames x 12, n_frames x 6
 # (a fifth output, acom [3], comes from wbcqp_observe_acom: asked for by name -- observe(acom=...), observe_host(acom=True))
 STAB_INPUTS = ("ref", "wrench", "com", "acom", "placement", "x_prev")  # the arrays of wbcqp_stab_inputs
@@ -215,6 +216,16 @@ class CStabOutputs(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in STAB_OUTPUTS]
 
 
+class CZmpDistributor(C.Structure):
+    _fields_ = [("p", C.c_double * 6), ("d", C.c_double * 6), ("lf_force_ref", C.c_int32), ("rf_force_ref", C.c_int32)]
+
+
+def c_zmp_distributor(zmp) -> CZmpDistributor:
+    """wbcqp_zmp_distributor from a stabilizer.ZmpDistributor (anything with its attributes)."""
+    vec = lambda a: (C.c_double * 6)(*[float(x) for x in np.asarray(a, dtype=np.float64).reshape(6)])  # noqa: E731
+    return CZmpDistributor(vec(zmp.p), vec(zmp.d), int(zmp.lf_force_ref), int(zmp.rf_force_ref))
+
+
 def c_stabilizer(stab) -> CStabilizer:
     """wbcqp_stabilizer from a stabilizer.Stabilizer (anything with its attributes)."""
     vec = lambda a, n: (C.c_double * n)(*[float(x) for x in np.asarray(a, dtype=np.float64).reshape(n)])  # noqa: E731
@@ -309,6 +320,11 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_stabilizer_state_bytes.restype = C.c_int64
     lib.wbcqp_stabilize.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.c_int, C.POINTER(CStabInputs), C.c_void_p, C.POINTER(CStabOutputs), C.c_void_p]
     lib.wbcqp_stabilize_host.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.c_int, C.POINTER(CStabInputs), C.c_void_p, C.POINTER(CStabOutputs)]
+    lib.wbcqp_set_force_references.argtypes = [C.c_void_p, C.c_int, c_i32_p, c_f64_p]
+    lib.wbcqp_stabilize_zmp.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.POINTER(CZmpDistributor), C.c_int, C.POINTER(CStabInputs), C.c_void_p,
+                                        C.POINTER(CStabOutputs), C.c_void_p, C.c_void_p]
+    lib.wbcqp_stabilize_zmp_host.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.POINTER(CZmpDistributor), C.c_int, C.POINTER(CStabInputs), C.c_void_p,
+                                             C.POINTER(CStabOutputs), C.c_void_p]
     _lib = lib
     return lib
 
@@ -564,6 +580,14 @@ class Handle:
         self._check(self.lib.wbcqp_set_model(self._h, slot, C.byref(mb.model), C.byref(mb.taskmap)))
         self._companions_of(slot, reset=True)["model"] = (model, tm)
 
+    def set_force_references(self, slot: int, force_ref: Optional[Sequence[int]], weight):
+        """wbcqp_set_force_references: force_ref [nc] offsets of the contacts' 6-number force references in a reference row (TaskMap.contact_fref;
+        -1: none), weight [nc, 6] the w_f the slot's forcereg_mat was made with.  After set_model, dropped with the model."""
+        fr = None if force_ref is None else np.ascontiguousarray(force_ref, dtype=np.int32).reshape(-1)
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64).reshape(-1)
+        self._check(self.lib.wbcqp_set_force_references(self._h, slot, fr.ctypes.data_as(c_i32_p) if fr is not None else None,
+                                                        w.ctypes.data_as(c_f64_p) if w is not None else None))
+
     def _select_frames(self, slot: int, frames: Sequence[int], setter, what: str):
         fr = np.ascontiguousarray(frames, dtype=np.int32).reshape(-1)
         self._check(setter(self._h, slot, int(fr.size), fr.ctypes.data_as(c_i32_p)))
@@ -681,6 +705,40 @@ class Handle:
         cin = CStabInputs(ptr(ref), ptr(wrench), ptr(com), ptr(acom), ptr(placement), width(placement, ldp), ptr(x_prev), width(x_prev, ldx))
         out = CStabOutputs(ptr(ref_out), ptr(flags), ptr(cop))
         self._check(self.lib.wbcqp_stabilize(self._h, C.byref(cs), int(batch), C.byref(cin), ptr(state), C.byref(out), C.c_void_p(stream)))
+
+    def stabilize_zmp(self, stab, zmp, batch: int, ref, wrench, com, acom, placement, ldp: int = 0, x_prev=None, ldx: int = 0, state=None,
+                      ref_out=None, flags=None, cop=None, alpha=None, stream: int = 0):
+        """stabilize with the ZMP force distributor (wbcqp_stabilize_zmp).  zmp: a stabilizer.ZmpDistributor, or None (then this IS stabilize);
+        alpha [batch, 2]: one more optional output."""
+        ptr = lambda t: (t if isinstance(t, int) else t.data_ptr()) if t is not None else None  # noqa: E731
+        width = lambda t, ld: int(ld) if ld or t is None or isinstance(t, int) else int(t.numel() // max(int(t.shape[0]), 1))  # noqa: E731
+        cs = c_stabilizer(stab)
+        cz = c_zmp_distributor(zmp) if zmp is not None else None
+        cin = CStabInputs(ptr(ref), ptr(wrench), ptr(com), ptr(acom), ptr(placement), width(placement, ldp), ptr(x_prev), width(x_prev, ldx))
+        out = CStabOutputs(ptr(ref_out), ptr(flags), ptr(cop))
+        self._check(self.lib.wbcqp_stabilize_zmp(self._h, C.byref(cs), C.byref(cz) if cz is not None else None, int(batch), C.byref(cin), ptr(state),
+                                                 C.byref(out), ptr(alpha), C.c_void_p(stream)))
+
+    def stabilize_zmp_host(self, stab, zmp, inputs: Dict[str, np.ndarray], state: Optional[np.ndarray] = None,
+                           outputs: Sequence[str] = STAB_OUTPUTS + ("alpha",)) -> Dict[str, np.ndarray]:
+        """wbcqp_stabilize_zmp_host: stabilize_host with the distributor (zmp None: stabilize_host's bits); `alpha` [B, 2] is one more output."""
+        a = {k: (np.ascontiguousarray(inputs[k], dtype=self.np_dtype) if inputs.get(k) is not None else None) for k in STAB_INPUTS}
+        B = a["ref"].shape[0]
+        a = {k: (t.reshape(B, -1) if t is not None else None) for k, t in a.items()}
+        if state is not None:
+            assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"], "state: a contiguous uint8 array [B, state_bytes]"
+        shapes = {"ref_out": ((B, int(stab.nref)), self.np_dtype), "flags": ((B,), np.int32), "cop": ((B, 3, 2), self.np_dtype),
+                  "alpha": ((B, 2), self.np_dtype)}
+        res = {k: np.zeros(*shapes[k]) for k in outputs}
+        dat = lambda t: t.ctypes.data if t is not None else None  # noqa: E731
+        cs = c_stabilizer(stab)
+        cz = c_zmp_distributor(zmp) if zmp is not None else None
+        cin = CStabInputs(dat(a["ref"]), dat(a["wrench"]), dat(a["com"]), dat(a["acom"]), dat(a["placement"]), int(a["placement"].shape[1]),
+                          dat(a["x_prev"]), int(a["x_prev"].shape[1]) if a["x_prev"] is not None else 0)
+        out = CStabOutputs(*[res[k].ctypes.data if k in res else None for k in STAB_OUTPUTS])
+        self._check(self.lib.wbcqp_stabilize_zmp_host(self._h, C.byref(cs), C.byref(cz) if cz is not None else None, B, C.byref(cin), dat(state),
+                                                      C.byref(out), res["alpha"].ctypes.data if "alpha" in res else None))
+        return res
 
     def stabilize_host(self, stab, inputs: Dict[str, np.ndarray], state: Optional[np.ndarray] = None,
                        outputs: Sequence[str] = STAB_OUTPUTS) -> Dict[str, np.ndarray]:

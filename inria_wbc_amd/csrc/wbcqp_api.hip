@@ -259,6 +259,7 @@ int wbcqp_set_structure(wbcqp_handle* h, int slot, const wbcqp_structure* st)
     s.host = D;
     s.sel_col_h.assign(st->sel_col, st->sel_col + D.n_sel);
     s.force_gen_h.assign(st->force_gen, st->force_gen + (size_t)nc * 72);
+    s.forcereg_h.assign(st->forcereg_mat, st->forcereg_mat + (size_t)nc * 72);
     s.lds_full = D.lds_doubles * 8;
     s.lds_cp = 0;
     s.host_cp = DevStruct{};
@@ -579,6 +580,25 @@ int wbcqp_set_model(wbcqp_handle* h, int slot, const wbcqp_model* md, const wbcq
     return WBCQP_OK;
 }
 
+int wbcqp_set_force_references(wbcqp_handle* h, int slot, const int32_t* force_ref, const double* weight)
+{
+    if (!h) return WBCQP_ERR_INVALID;
+    Slot* s = slot_with_model(h, slot);
+    if (!s) return WBCQP_ERR_INVALID;
+    std::vector<int> off;
+    WB_TRY(check_force_references(h, *s, force_ref, weight, &off));
+    TermsDev& T = s->terms;
+    const int nc = T.nc;
+    if (nc == 0) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    // (the two tables were given room by wbcqp_set_model; a blocking copy: launches already queued have finished reading the old ones)
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemcpy(const_cast<int*>(T.ipool) + T.i_fref, off.data(), (size_t)nc * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(h, hipMemcpy(const_cast<double*>(T.dpool) + T.d_fref_w, weight, (size_t)6 * nc * sizeof(double), hipMemcpyHostToDevice));
+    T.n_fref = std::any_of(off.begin(), off.end(), [](int o) { return o >= 0; }) ? 6 * nc : 0;
+    return WBCQP_OK;
+}
+
 int wbcqp_set_observed_frames(wbcqp_handle* h, int slot, int n_frames, const int32_t* frames)
 {
     return set_frame_selection(h, slot, &Slot::observed, n_frames, frames, WBCQP_MAX_OBSERVED, "an observed frame", "the observed frames");
@@ -724,23 +744,35 @@ int64_t wbcqp_stabilizer_state_bytes(const wbcqp_stabilizer* stabilizer)
     return stabilizer_flaw(stabilizer) ? 0 : (int64_t)(8 * stab_state_doubles(stabilizer->window));
 }
 
-int wbcqp_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state, const wbcqp_stab_outputs* out,
-                    void* stream)
+int wbcqp_stabilize_zmp(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, const wbcqp_zmp_distributor* zmp, int batch, const wbcqp_stab_inputs* in,
+                        void* state, const wbcqp_stab_outputs* out, void* alpha, void* stream)
 {
     StabDev D;
     bool run = false;
-    WB_TRY(check_stabilize(h, stabilizer, batch, in, state, out, &D, &run));
+    WB_TRY(check_stabilize(h, stabilizer, zmp, batch, in, state, out, alpha, &D, &run));
     if (!run) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    return launch_stabilize(h, D, batch, *in, state, state, out ? *out : wbcqp_stab_outputs{}, static_cast<hipStream_t>(stream));
+    return launch_stabilize(h, D, zmp, batch, *in, state, state, out ? *out : wbcqp_stab_outputs{}, alpha, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state, const wbcqp_stab_outputs* out,
+                    void* stream)
+{
+    return wbcqp_stabilize_zmp(h, stabilizer, nullptr, batch, in, state, out, nullptr, stream);
 }
 
 int wbcqp_stabilize_host(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, int batch, const wbcqp_stab_inputs* in, void* state,
                          const wbcqp_stab_outputs* out)
 {
+    return wbcqp_stabilize_zmp_host(h, stabilizer, nullptr, batch, in, state, out, nullptr);
+}
+
+int wbcqp_stabilize_zmp_host(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, const wbcqp_zmp_distributor* zmp, int batch, const wbcqp_stab_inputs* in,
+                             void* state, const wbcqp_stab_outputs* out, void* alpha)
+{
     StabDev D;
     bool run = false;
-    WB_TRY(check_stabilize(h, stabilizer, batch, in, state, out, &D, &run));
+    WB_TRY(check_stabilize(h, stabilizer, zmp, batch, in, state, out, alpha, &D, &run));
     if (!run) return WBCQP_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     const wbcqp_stab_outputs o = out ? *out : wbcqp_stab_outputs{};
@@ -753,10 +785,11 @@ int wbcqp_stabilize_host(wbcqp_handle* h, const wbcqp_stabilizer* stabilizer, in
                  {-1, const_cast<void*>(in->placement), ((B - 1) * (size_t)in->ldp + reach_p) * es, 0},
                  {-1, const_cast<void*>(reach_x ? in->x_prev : nullptr), reach_x ? ((B - 1) * (size_t)in->ldx + reach_x) * es : 0, 0},
                  {-1, state, sb, 0}};
-    Arr dn[4] = {{-1, o.ref_out, B * D.nref * es, 0}, {-1, o.flags, B * 4, 0}, {-1, o.cop, B * 6 * es, 0}, {-1, state, sb, 0}};
+    Arr dn[5] = {{-1, o.ref_out, B * D.nref * es, 0}, {-1, o.flags, B * 4, 0}, {-1, o.cop, B * 6 * es, 0}, {-1, state, sb, 0},
+                 {-1, zmp ? alpha : nullptr, B * 2 * es, 0}};
     return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
         const wbcqp_stab_inputs din = {u[0], u[1], u[2], u[3], u[4], in->ldp, u[5], in->ldx};
-        return launch_stabilize(h, D, batch, din, u[6], d[3], wbcqp_stab_outputs{d[0], static_cast<int32_t*>(d[1]), d[2]}, nullptr);
+        return launch_stabilize(h, D, zmp, batch, din, u[6], d[3], wbcqp_stab_outputs{d[0], static_cast<int32_t*>(d[1]), d[2]}, d[4], nullptr);
     });
 }
 

@@ -363,6 +363,11 @@ int derive_terms(wbcqp_handle* h, const DevStruct& D, const int* sel_host, const
     T.i_blk_row = puti(blk_row.data(), blk_row.size()); T.i_blk_ref = puti(blk_ref.data(), blk_ref.size());
     T.i_blk_pair0 = puti(blk_pair0.data(), blk_pair0.size());
     T.i_blk_npair = puti(blk_npair.data(), blk_npair.size()); T.i_sel_col = puti(sel.data(), sel.size());
+    // room for the contacts' force references (wbcqp_set_force_references fills it in place): none yet
+    const std::vector<int> no_fref(D.nc, -1);
+    const std::vector<double> no_fref_w((size_t)6 * D.nc, 0.0);
+    T.n_fref = 0;
+    T.i_fref = puti(no_fref.data(), no_fref.size());
     T.d_place = putd(md->placement, (size_t)nb * 12); T.d_inertia = putd(md->inertia, (size_t)nb * 10);
     T.d_law_place = putd(law_place.data(), law_place.size()); T.d_law_kp = putd(law_kp.data(), law_kp.size());
     T.d_law_kd = putd(law_kd.data(), law_kd.size());
@@ -370,6 +375,7 @@ int derive_terms(wbcqp_handle* h, const DevStruct& D, const int* sel_host, const
     T.d_pair_par = putd(pair_par.data(), pair_par.size());
     T.d_blk_kp = putd(blk_kp.data(), blk_kp.size()); T.d_blk_kd = putd(blk_kd.data(), blk_kd.size());
     T.d_cop_pts = putd(cop_pts.data(), cop_pts.size());
+    T.d_fref_w = putd(no_fref_w.data(), no_fref_w.size());
     T.d_qlb = putd(md->q_lb, D.n_bound ? na : 0); T.d_qub = putd(md->q_ub, D.n_bound ? na : 0); T.d_dqmax = putd(md->dq_max, D.n_bound ? na : 0);
     int o = 0;
     auto take = [&](int count) { int at = o; o += (count + 1) & ~1; return at; };

@@ -50,6 +50,7 @@ struct Slot {
     int spec = 0;               // 1-based index of the compact kernel's instantiation for this very layout (kSpecDims), 0: the generic kernel
     std::vector<int> sel_col_h;       // host copies of what wbcqp_set_model needs of the structure: the posture task's columns
     std::vector<double> force_gen_h;  // and the contacts' force generators (the contact points sit in their skew blocks)
+    std::vector<double> forcereg_h;   // forcereg_mat [nc][6][12]: what wbcqp_set_force_references holds the caller's weights against
     double* ffc_dev = nullptr;  // the force blocks' factor for one weight (DevStruct::ffc; owned through `allocs`), null: none (no contacts, not compact, disabled)
     bool ffc_built = false;     // ... made from the first QP of the slot's first compact launch (solve_ragged)
     bool has_model = false;     // wbcqp_set_model: tree + task bindings for wbcqp_problem_data

@@ -1,7 +1,7 @@
 // wbcqp_host_monitor.hpp -- host side of wbcqp_detect_torque_collisions and of wbcqp_stabilize (wbcqp_api.hip), the two calls that process a fleet's
 // sensor streams with a state of the caller's: per call ONE check that the device-pointer and the host-pointer entry point share (nothing is staged or
-// launched before it has passed) and ONE launch of its kernel (torque_monitor_kernel, csrc/wbcqp_monitor.hpp; stabilize_kernel,
-// csrc/wbcqp_stabilize.hpp), one wavefront per instance.  The monitor / the stabiliser travels in the kernel's arguments: no slot, no model, no device
+// launched before it has passed) and ONE launch of its kernel (torque_monitor_kernel, csrc/wbcqp_monitor.hpp; stabilize_kernel, with a ZMP
+// distributor its second instantiation, csrc/wbcqp_stabilize.hpp), one wavefront per instance.  The monitor / the stabiliser travels in the kernel's arguments: no slot, no model, no device
 // table.  Host code only; included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_host_handle.hpp"
@@ -84,7 +84,8 @@ int launch_torque_monitor(wbcqp_handle* h, const MonitorDev& D, int batch, int n
 static_assert(WBCQP_MAX_STAB_WINDOW == kStabMaxWindow, "the header and the kernel agree on the stabiliser's window");
 static_assert(WBCQP_STAB_COP == kStabCop && WBCQP_STAB_LCOP == kStabLcop && WBCQP_STAB_RCOP == kStabRcop && WBCQP_STAB_COM == kStabCom &&
                   WBCQP_STAB_LANKLE == kStabLankle && WBCQP_STAB_RANKLE == kStabRankle && WBCQP_STAB_FFDA == kStabFfda &&
-                  WBCQP_STAB_ERR_COP == kStabErrCop && WBCQP_STAB_ERR_FORCE == kStabErrForce,
+                  WBCQP_STAB_ERR_COP == kStabErrCop && WBCQP_STAB_ERR_FORCE == kStabErrForce && WBCQP_STAB_ZMP == kStabZmp &&
+                  WBCQP_STAB_ERR_ZMP == kStabErrZmp,
               "... and on the bits of its flags");
 
 // what is wrong with the stabiliser's own fields (ldp and ldx are the call's), or null
@@ -114,13 +115,34 @@ const char* stabilizer_flaw(const wbcqp_stabilizer* s)
     return nullptr;
 }
 
-// *run: false where the call is accepted and there is nothing to do
-int check_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* s, int batch, const wbcqp_stab_inputs* in, const void* state, const wbcqp_stab_outputs* out,
-                    StabDev* D, bool* run)
+// what is wrong with a ZMP distributor on a stabiliser that has passed stabilizer_flaw, or null
+const char* zmp_flaw(const wbcqp_stabilizer* s, const wbcqp_zmp_distributor* z)
+{
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(z->p[k]) || !std::isfinite(z->d[k])) return "a ZMP distributor gain is not finite";
+    if (s->lf_contact_ref < 0 && s->rf_contact_ref < 0) return "the ZMP distributor needs an active foot contact (lf_contact_ref and rf_contact_ref are both -1)";
+    const int off[kStabBlocks] = {s->com_ref, s->lf_ref, s->rf_ref, s->torso_ref, s->lf_contact_ref, s->rf_contact_ref};
+    const int foff[2] = {z->lf_force_ref, z->rf_force_ref};
+    for (int f = 0; f < 2; ++f) {
+        if (foff[f] < -1) return "a force reference offset is below -1";
+        if (foff[f] < 0) continue;
+        if ((int64_t)foff[f] + 6 > s->nref) return "a force reference runs past nref";
+        for (int b = 0; b < kStabBlocks; ++b)
+            if (off[b] >= 0 && off[b] < foff[f] + 6 && foff[f] < off[b] + (b == 0 ? 9 : 24)) return "a force reference overlaps a reference block";
+    }
+    if (foff[0] >= 0 && foff[1] >= 0 && foff[0] < foff[1] + 6 && foff[1] < foff[0] + 6) return "the two force references overlap";
+    return nullptr;
+}
+
+// *run: false where the call is accepted and there is nothing to do.  z: the ZMP distributor of wbcqp_stabilize_zmp, or null; alpha: its extra output
+int check_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* s, const wbcqp_zmp_distributor* z, int batch, const wbcqp_stab_inputs* in, const void* state,
+                    const wbcqp_stab_outputs* out, const void* alpha, StabDev* D, bool* run)
 {
     *run = false;
     if (!h) return WBCQP_ERR_INVALID;
     if (const char* flaw = stabilizer_flaw(s)) return fail(h, WBCQP_ERR_INVALID, flaw);
+    if (z)
+        if (const char* flaw = zmp_flaw(s, z)) return fail(h, WBCQP_ERR_INVALID, flaw);
     if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
     if (!in) return fail(h, WBCQP_ERR_INVALID, "stabilizer inputs struct is NULL");
     if (!in->ref || !in->wrench || !in->com || !in->acom || !in->placement) return fail(h, WBCQP_ERR_INVALID, "ref, wrench, com, acom and placement are required");
@@ -129,7 +151,7 @@ int check_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* s, int batch, const
     if (in->x_prev && last_col >= 0 && (int64_t)in->ldx < (int64_t)last_col + 12)
         return fail(h, WBCQP_ERR_INVALID, "ldx is too small for a force column + 12");
     if (batch == 0) return WBCQP_OK;
-    if (!state && (!out || (!out->ref_out && !out->flags && !out->cop))) return WBCQP_OK;
+    if (!state && (!out || (!out->ref_out && !out->flags && !out->cop)) && !(z && alpha)) return WBCQP_OK;
     *D = StabDev{};
     D->window = s->window;
     D->nref = s->nref;
@@ -149,9 +171,10 @@ int check_stabilize(wbcqp_handle* h, const wbcqp_stabilizer* s, int batch, const
     return WBCQP_OK;
 }
 
-// batch > 0, arguments checked, the handle's device current; state_in / state_out: the caller's one block, or its two staged copies
-int launch_stabilize(wbcqp_handle* h, const StabDev& D, int batch, const wbcqp_stab_inputs& in, const void* state_in, void* state_out,
-                     const wbcqp_stab_outputs& out, hipStream_t stream)
+// batch > 0, arguments checked, the handle's device current; state_in / state_out: the caller's one block, or its two staged copies.
+// z null: stabilize_kernel; otherwise stabilize_kernel<TI, true>, which also writes alpha (may be null)
+int launch_stabilize(wbcqp_handle* h, const StabDev& D, const wbcqp_zmp_distributor* z, int batch, const wbcqp_stab_inputs& in, const void* state_in,
+                     void* state_out, const wbcqp_stab_outputs& out, void* alpha, hipStream_t stream)
 {
     return with_dtype(h, [&](auto tag) -> int {
         using TI = WB_TI(tag);
@@ -159,8 +182,19 @@ int launch_stabilize(wbcqp_handle* h, const StabDev& D, int batch, const wbcqp_s
                              static_cast<const TI*>(in.acom), static_cast<const TI*>(in.placement), static_cast<const TI*>(in.x_prev),
                              static_cast<const double*>(state_in), static_cast<double*>(state_out), static_cast<TI*>(out.ref_out), out.flags,
                              static_cast<TI*>(out.cop), in.ldp, in.ldx, batch};
-        hipLaunchKernelGGL(stabilize_kernel<TI>, dim3((batch + kObservePerBlock - 1) / kObservePerBlock), dim3(kObserveThreads),
-                           kObservePerBlock * stab_lds_doubles(D.window) * 8, stream, a);
+        const dim3 grid((batch + kObservePerBlock - 1) / kObservePerBlock), block(kObserveThreads);
+        if (z) {
+            StabZmpArgs<TI> az{};
+            static_cast<StabArgs<TI>&>(az) = a;
+            std::copy(z->p, z->p + 6, az.p);
+            std::copy(z->d, z->d + 6, az.d);
+            az.foff[0] = z->lf_force_ref;
+            az.foff[1] = z->rf_force_ref;
+            az.alpha = static_cast<TI*>(alpha);
+            hipLaunchKernelGGL((stabilize_kernel<TI, true>), grid, block, kObservePerBlock * stab_lds_doubles(D.window, true) * 8, stream, az);
+        }
+        else
+            hipLaunchKernelGGL(stabilize_kernel<TI>, grid, block, kObservePerBlock * stab_lds_doubles(D.window) * 8, stream, a);
         HIP_TRY(h, hipGetLastError());
         return WBCQP_OK;
     });

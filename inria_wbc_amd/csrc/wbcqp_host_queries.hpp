@@ -14,6 +14,35 @@ static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the k
 inline int query_blocks(int batch) { return (batch + kObservePerBlock - 1) / kObservePerBlock; }
 
 // the tree of the slot's model as the observe and the collide kernel read it, with `frames` frames of the selection (0: none are read)
+// wbcqp_set_force_references' one check on a slot with a model; *off: the offsets as the rows kernel's table holds them
+int check_force_references(wbcqp_handle* h, const Slot& s, const int32_t* force_ref, const double* weight, std::vector<int>* off)
+{
+    const int nc = s.terms.nc, nref = s.terms.nref;
+    off->assign(nc, -1);
+    if (nc == 0) return WBCQP_OK;
+    if (!force_ref || !weight) return fail(h, WBCQP_ERR_INVALID, "force_ref / weight is NULL");
+    for (int c = 0; c < nc; ++c) {
+        const int o = force_ref[c];
+        if (o < -1) return fail(h, WBCQP_ERR_INVALID, "a force reference offset is below -1");
+        if (o >= 0 && (int64_t)o + 6 > nref) return fail(h, WBCQP_ERR_INVALID, "a force reference runs past nref");
+        for (int a = 0; a < c; ++a)
+            if (o >= 0 && force_ref[a] >= 0 && o < force_ref[a] + 6 && force_ref[a] < o + 6) return fail(h, WBCQP_ERR_INVALID, "two force references overlap");
+        (*off)[c] = o;
+    }
+    for (int c = 0; c < nc; ++c)
+        for (int k = 0; k < 6; ++k) {
+            const double w = weight[6 * c + k];
+            if (!std::isfinite(w)) return fail(h, WBCQP_ERR_INVALID, "a force regularisation weight is not finite");
+            for (int j = 0; j < 12; ++j) {
+                volatile double prod = w * s.force_gen_h[(size_t)c * 72 + k * 12 + j]; // (one rounding: the product the caller formed)
+                const double have = s.forcereg_h[(size_t)c * 72 + k * 12 + j], got = prod;
+                if (!(got == have)) // (exact, no tolerance; a zero of either sign is a zero)
+                    return fail(h, WBCQP_ERR_INVALID, "weight[c][k] * force_gen[c][k][j] is not the slot's forcereg_mat[c][k][j]: the weights are not the ones the slot was made with");
+            }
+        }
+    return WBCQP_OK;
+}
+
 ObserveDev observe_dev(const TermsDev& T, const FrameSel& sel, bool frames)
 {
     return ObserveDev{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_idxq, T.i_idxv, T.i_anc, T.d_place, T.d_inertia,

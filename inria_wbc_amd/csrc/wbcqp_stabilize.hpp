@@ -22,6 +22,12 @@
 // One wavefront per instance, four per workgroup, nothing shared between the waves: no workgroup barrier, no atomics.  Every product, sum and quotient
 // below is a statement of its own or a __d*_rn call, so -ffp-contract=on has nothing to fuse: the arithmetic equals inria_wbc_amd/stabilizer.py bit for
 // bit, except through atan2 / sin / cos (the rotation entries).  F32 handles read float, compute in double, write float.
+//
+// stabilize_kernel<TI, true> is the same body with the ZMP force distributor compiled in (wbcqp_stabilize_zmp; stabilizer.cpp:277-311, 340-440 there): between the
+// CoM law and the ankle laws, exactly when the CoM law runs, the robot's weight is split between the feet by where the ZMP lies between the contacts'
+// references (once for the model's ZMP, once for the measured one), and the admittance of the two splits leaves as a 6-number force reference per foot in
+// two more blocks of the row.  The patch grows by those twelve numbers (stab_lds_doubles(window, true)); additions, products, quotients and one square
+// root, all correctly rounded: the force references are the transcription's bit for bit.  stabilize_kernel<TI> (ZMP false) is the body WITHOUT that code.
 #pragma once
 
 #include "wbcqp_observe.hpp"
@@ -34,7 +40,9 @@ constexpr int kStabFilters = 5;
 constexpr int kStabBlocks = 6;   // com, lf, rf, torso, left contact, right contact
 constexpr int kStabPatch = 136;  // LDS doubles of the patch: 9 + 5 * 24 = 129, rounded up
 constexpr double kStabFmin = 30.0; // Cop::fmin(): a float compared as 30.0
-enum { kStabCop = 1, kStabLcop = 2, kStabRcop = 4, kStabCom = 8, kStabLankle = 16, kStabRankle = 32, kStabFfda = 64, kStabErrCop = 128, kStabErrForce = 256 };
+constexpr int kStabZmpPatch = 12; // ... and of the distributor's two force references behind it: left 6, right 6
+enum { kStabCop = 1, kStabLcop = 2, kStabRcop = 4, kStabCom = 8, kStabLankle = 16, kStabRankle = 32, kStabFfda = 64, kStabErrCop = 128, kStabErrForce = 256,
+       kStabZmp = 512, kStabErrZmp = 1024 };
 
 // the stabiliser as the kernel reads it, by value in the kernel's arguments
 struct StabDev {
@@ -47,7 +55,7 @@ struct StabDev {
 };
 
 constexpr size_t stab_state_doubles(int window) { return kStabFilters + (size_t)kStabChannels * window; }
-constexpr size_t stab_lds_doubles(int window) { return (size_t)kStabChannels * window + kStabPatch; } // per wave
+constexpr size_t stab_lds_doubles(int window, bool zmp = false) { return (size_t)kStabChannels * window + kStabPatch + (zmp ? kStabZmpPatch : 0); } // per wave
 
 template <typename TI>
 struct StabArgs {
@@ -60,6 +68,16 @@ struct StabArgs {
     TI* cop;                // [batch][3][2] or null
     int ldp, ldx, batch;
 };
+
+// the distributor's share of the arguments (stabilize_kernel<TI, true>)
+template <typename TI>
+struct StabZmpArgs : StabArgs<TI> {
+    double p[6], d[6]; // zmp_p, zmp_d
+    int foff[2];       // the left / right foot's force reference in a row; -1: not written
+    TI* alpha;         // [batch][2] alpha of the model's ZMP, of the measured one (NaN where the law did not run), or null
+};
+template <typename TI, bool ZMP>
+using StabKernelArgs = std::conditional_t<ZMP, StabZmpArgs<TI>, StabArgs<TI>>;
 
 #ifdef __HIPCC__
 
@@ -139,8 +157,74 @@ __device__ inline int stab_off(const StabDev& S, int b)
     return b == 0 ? S.off[0] : b == 1 ? S.off[1] : b == 2 ? S.off[2] : b == 3 ? S.off[3] : b == 4 ? S.off[4] : S.off[5];
 }
 
-template <typename TI>
-__global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabArgs<TI> args)
+__device__ inline double stab_norm2(double x, double y) { return __dsqrt_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y))); }
+
+// zmp_distributor (stabilizer.cpp:340-429) with closest_point_on_line (431-440), everything projected to z = 0: alpha and the entries 2, 3, 4 of the left
+// and right force reference (the others are +0).  la / ra: the foot's contact is active (one at least).  false: the reference's "this case should not
+// exists" (only non-finite inputs get there).
+__device__ inline bool stab_zmp_distribute(double mass, const double* z, const double* pl, const double* pr, bool la, bool ra, double* alpha_out,
+                                           double* left, double* right)
+{
+    double PL[2] = {0.0, 0.0}, PR[2] = {0.0, 0.0};
+    double alpha = ra ? 1.0 : 0.0;
+    bool ok = true;
+    if (la) {
+        PL[0] = pl[0];
+        PL[1] = pl[1];
+    }
+    if (ra) {
+        PR[0] = pr[0];
+        PR[1] = pr[1];
+    }
+    if (la && ra) {
+        const double ux = __dsub_rn(PR[0], PL[0]), uy = __dsub_rn(PR[1], PL[1]);
+        const double sq = __dadd_rn(__dmul_rn(ux, ux), __dmul_rn(uy, uy));
+        const double L = __dsqrt_rn(sq);
+        double ex = ux, ey = uy; // Eigen's normalized() [UPSTREAM-RECALL] Eigen/src/Core/Dot.h: divided by the norm only where the squared norm is > 0
+        if (sq > 0.0) {
+            ex = __ddiv_rn(ux, L);
+            ey = __ddiv_rn(uy, L);
+        }
+        const double dd = __dadd_rn(__dmul_rn(__dsub_rn(z[0], PR[0]), ex), __dmul_rn(__dsub_rn(z[1], PR[1]), ey));
+        const double px = __dadd_rn(PR[0], __dmul_rn(ex, dd)), py = __dadd_rn(PR[1], __dmul_rn(ey, dd));
+        const double a1 = stab_norm2(__dsub_rn(px, PL[0]), __dsub_rn(py, PL[1]));
+        const double a2 = stab_norm2(__dsub_rn(PR[0], px), __dsub_rn(PR[1], py));
+        if (fabs(__dsub_rn(__dsub_rn(L, a1), a2)) < 1e-10) alpha = __ddiv_rn(a1, L);
+        else if (a1 < a2) alpha = 0.0;
+        else if (a1 > a2) alpha = 1.0;
+        else {
+            alpha = __longlong_as_double(0x7ff8000000000000LL);
+            ok = false;
+        }
+    }
+    const double f_r = __dmul_rn(__dmul_rn(-alpha, mass), 9.81);
+    const double f_l = __dmul_rn(__dmul_rn(-__dsub_rn(1.0, alpha), mass), 9.81);
+    double tau0[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) tau0[k] = __dsub_rn(__dmul_rn(-__dsub_rn(PR[k], z[k]), f_r), __dmul_rn(__dsub_rn(PL[k], z[k]), f_l));
+    const double tauR1 = __dmul_rn(alpha, tau0[1]), tauL1 = __dmul_rn(__dsub_rn(1.0, alpha), tau0[1]);
+    const bool neg = tau0[0] < 0.0;
+    const double tauR0 = neg ? tau0[0] : 0.0, tauL0 = neg ? 0.0 : tau0[0];
+    left[0] = f_l;
+    left[1] = tauL1;
+    left[2] = -tauL0;
+    right[0] = f_r;
+    right[1] = tauR1;
+    right[2] = -tauR0;
+    *alpha_out = alpha;
+    return ok;
+}
+
+// one entry of zmp_distributor_admittance (stabilizer.cpp:307-308): t - p (t - s) - d (t - s) / dt
+__device__ inline double stab_zmp_entry(double t, double s, double p, double d, double dt)
+{
+    const double e = __dsub_rn(t, s);
+    return __dsub_rn(__dsub_rn(t, __dmul_rn(p, e)), __ddiv_rn(__dmul_rn(d, e), dt));
+}
+
+// ZMP false: stabilize_kernel<TI>, what wbcqp_stabilize launches; ZMP true: the second instantiation, with the distributor compiled in
+template <typename TI, bool ZMP = false>
+__global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabKernelArgs<TI, ZMP> args)
 {
     extern __shared__ double stab_lds[];
     const StabDev& S = args.S;
@@ -149,7 +233,7 @@ __global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabAr
     const long long inst = (long long)blockIdx.x * kObservePerBlock + wave;
     if (inst >= args.batch) return; // the whole wave leaves: nothing below waits for another wave
     const int W = S.window, nref = S.nref;
-    double* ring = stab_lds + (size_t)wave * stab_lds_doubles(W);
+    double* ring = stab_lds + (size_t)wave * stab_lds_doubles(W, ZMP);
     double* patch = ring + (size_t)kStabChannels * W;
     const size_t state_doubles = stab_state_doubles(W);
     const bool mine = lane < kStabChannels;
@@ -246,11 +330,45 @@ __global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabAr
     const bool do_l = ok_l && S.off[4] >= 0, do_r = ok_r && S.off[5] >= 0;
     const bool do_f = args.x_prev != nullptr && S.lf_col >= 0 && S.rf_col >= 0 && ready_fl && ready_fr;
     const bool err_cop = (any && stab_far(vx, vy)) || (do_l && stab_far(cp[2], cp[3])) || (do_r && stab_far(cp[4], cp[5]));
+    // the distributor (every lane forms it: a few dozen wave-uniform operations, and the flags need its guard): after the far-CoP guard, before the force guard
+    [[maybe_unused]] double fref[12] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    [[maybe_unused]] double alpha_t = __longlong_as_double(0x7ff8000000000000LL), alpha_s = alpha_t;
+    bool err_zmp = false;
+    [[maybe_unused]] bool do_z = false;
+    if constexpr (ZMP) {
+        if (any && !err_cop) {
+            const TI* gc = args.com + (size_t)inst * 3;
+            const TI* ga = args.acom + (size_t)inst * 3;
+            const double k = __ddiv_rn((double)gc[2], 9.81);
+            const double zref[2] = {__dsub_rn((double)gc[0], __dmul_rn(k, (double)ga[0])), __dsub_rn((double)gc[1], __dmul_rn(k, (double)ga[1]))};
+            const double zcop[2] = {vx, vy};
+            const bool la = S.off[4] >= 0, ra = S.off[5] >= 0; // (the host refuses a call with neither)
+            const double* pl = patch + stab_base_of(4); // the contacts' references as they lie in ref: no law has run yet
+            const double* pr = patch + stab_base_of(5);
+            double tl[3], tr[3], sl[3], sr[3];
+            const bool ok_t = stab_zmp_distribute(S.mass, zref, pl, pr, la, ra, &alpha_t, tl, tr);
+            const bool ok_s = stab_zmp_distribute(S.mass, zcop, pl, pr, la, ra, &alpha_s, sl, sr);
+            err_zmp = !(ok_t && ok_s);
+            do_z = !err_zmp;
+#pragma unroll
+            for (int e = 0; e < 6; ++e) { // entries 0, 1, 5: both splits hold +0 there
+                const bool mid = e >= 2 && e <= 4;
+                fref[e] = stab_zmp_entry(mid ? tl[e - 2] : 0.0, mid ? sl[e - 2] : 0.0, args.p[e], args.d[e], S.dt);
+                fref[6 + e] = stab_zmp_entry(mid ? tr[e - 2] : 0.0, mid ? sr[e - 2] : 0.0, args.p[e], args.d[e], S.dt);
+            }
+        }
+    }
     const double ten_mg = __dmul_rn(10.0, __dmul_rn(S.mass, 9.81));
-    const bool err_force = !err_cop && do_f && fabs(__dadd_rn(fz_l, fz_r)) > ten_mg;
-    const bool apply = !err_cop && !err_force;
+    const bool err_force = !err_cop && !err_zmp && do_f && fabs(__dadd_rn(fz_l, fz_r)) > ten_mg;
+    const bool apply = !err_cop && !err_zmp && !err_force;
     int flags = (ok_c ? kStabCop : 0) | (ok_l ? kStabLcop : 0) | (ok_r ? kStabRcop : 0) | (err_cop ? kStabErrCop : 0) | (err_force ? kStabErrForce : 0);
     if (apply) flags |= (any ? kStabCom : 0) | (do_l ? kStabLankle : 0) | (do_r ? kStabRankle : 0) | (do_f ? kStabFfda : 0);
+    if constexpr (ZMP) {
+        flags |= err_zmp ? kStabErrZmp : 0;
+        do_z = do_z && apply; // (the force guard tripped: the law did not run)
+        if (do_z) flags |= kStabZmp;
+        else alpha_t = alpha_s = __longlong_as_double(0x7ff8000000000000LL);
+    }
 
     // ---- 3. the laws, on lane 0 -------------------------------------------------------------------------------------------------------------
     if (lane == 0 && apply && args.ref_out) {
@@ -267,6 +385,12 @@ __global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabAr
                 patch[c] = __dsub_rn(patch[c], __dmul_rn(S.com_gains[c], cor));
                 patch[3 + c] = __dsub_rn(patch[3 + c], __ddiv_rn(__dmul_rn(S.com_gains[2 + c], cor), dt));
                 patch[6 + c] = __dsub_rn(patch[6 + c], __ddiv_rn(__dmul_rn(S.com_gains[4 + c], cor), dt2));
+            }
+        }
+        if constexpr (ZMP) { // stabilizer.cpp:277-311: the two force references (a block that is not written keeps what ref holds)
+            if (do_z) {
+#pragma unroll
+                for (int e = 0; e < kStabZmpPatch; ++e) patch[kStabPatch + e] = fref[e];
             }
         }
         for (int side = 0; side < 2; ++side) { // stabilizer.cpp:168-224
@@ -321,10 +445,20 @@ __global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabAr
                 const int off = S.off[b], len = b == 0 ? 9 : 24;
                 if (off >= 0 && e >= off && e < off + len) v = patch[stab_base_of(b) + (e - off)];
             }
+            if constexpr (ZMP) {
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    const int off = args.foff[f];
+                    if (do_z && off >= 0 && e >= off && e < off + 6) v = patch[kStabPatch + 6 * f + (e - off)];
+                }
+            }
             out[e] = (TI)v;
         }
     }
     if (lane == 0 && args.flags) args.flags[inst] = flags;
+    if constexpr (ZMP) {
+        if (lane < 2 && args.alpha) args.alpha[(size_t)inst * 2 + lane] = (TI)(lane == 0 ? alpha_t : alpha_s);
+    }
     if (lane < 6 && args.cop) {
         const bool ok = fi == 0 ? ok_c : fi == 1 ? ok_l : ok_r;
         args.cop[(size_t)inst * 6 + lane] = (TI)(ok ? fv : __longlong_as_double(0x7ff8000000000000LL));

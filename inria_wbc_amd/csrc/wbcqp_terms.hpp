@@ -45,6 +45,7 @@ struct TermsDev {
     int nlaw, npair, nscf, nblock, nc, n_dense, n_sel, n_bound, r1, nref;
     int posture_ref;
     int cop;                                                // 1: the structure has a cop task -- the contact lanes also write its rows
+    int n_fref;                                             // 6 nc where a contact carries a force reference (wbcqp_set_force_references), else 0
     double posture_kp, posture_kd, dt;
     double g[3];
     const int* ipool;
@@ -58,6 +59,7 @@ struct TermsDev {
     int i_scf_body;                                         // [nscf] distinct frames the self-collision tasks touch
     int i_blk_kind, i_blk_mask, i_blk_row, i_blk_ref, i_blk_pair0, i_blk_npair; // [nblock]
     int i_sel_col;                                          // [n_sel]
+    int i_fref;                                             // [nc] offset of the contact's force reference in a reference row, -1: none
     // double pool offsets
     int d_place, d_inertia;                                  // [nb][12], [nb][10]
     int d_law_place, d_law_kp, d_law_kd;                     // [nlaw][12], [nlaw], [nlaw]
@@ -65,6 +67,7 @@ struct TermsDev {
     int d_blk_kp, d_blk_kd;                                  // [nblock]
     int d_qlb, d_qub, d_dqmax;                               // [na]
     int d_cop_pts;                                           // [nc][4][3] contact points in the contact frame (cop task)
+    int d_fref_w;                                            // [nc][6] the force regularisation's weights w_f (forcereg_mat = diag(w_f) T)
     // LDS layout (doubles)
     int o_state, o_kin, o_scan, o_tot, o_sf, o_law, o_pair, o_scf, o_b1, o_bc;
     int lds_doubles;
@@ -561,6 +564,11 @@ __device__ __forceinline__ void terms_one(const TermsArgs<TI>& args, const TI* g
         for (int r = lane; r < T.n_sel; r += kWave) {
             const int c = ip[T.i_sel_col + r], ja = c - (nv - na);
             b1s[T.n_dense + r] = -T.posture_kp * (q[nq - na + ja] - ref[T.posture_ref + ja]) - T.posture_kd * v[c];
+        }
+        // the contacts' force references (wbcqp_set_force_references): b1 = w_f f_ref, one product; a contact without one keeps the +0 of the fill
+        for (int r = lane; r < T.n_fref; r += kWave) {
+            const int c = r / 6, off = ip[T.i_fref + c];
+            if (off >= 0) b1s[T.n_dense + T.n_sel + r] = __dmul_rn(dp[T.d_fref_w + r], ref[off + (r - 6 * c)]);
         }
         // joint bounds: tsid TaskJointPosVelAccBounds::computeAccLimits [UPSTREAM-RECALL, as oracle/rbd_oracle.c]
         for (int j = lane; j < T.n_bound; j += kWave) {

@@ -207,6 +207,10 @@ class TaskMap:
     n_acteq: int = 0  # rows of a `torque` task (tasks.cpp:227-271): zero right-hand sides, nothing to compute per tick
     cop: bool = False  # a `cop` task (tasks.cpp:156-178): three rows over the contact forces from the contact frames' placements
     contact_points: np.ndarray = field(default_factory=lambda: np.zeros(0))  # [ncontact][4][3] (tasks.cpp:353-358)
+    # build_taskmap(force_refs=True): offsets of the contacts' 6-number force references in a reference row (wbcqp_set_force_references), of this
+    # map's contacts [ncontact] and of every contact of the whole stack (contact_set_maps: the same in every set's map); None: the row carries none
+    contact_fref: Optional[np.ndarray] = None
+    contact_fref_all: Optional[np.ndarray] = None
 
     @property
     def n_dense(self) -> int:
@@ -237,10 +241,11 @@ def _mask_bits(s: str) -> int:
     return sum(1 << i for i, ch in enumerate(s) if ch != "0")
 
 
-def build_taskmap(model: Model, st: Structure, stack: Sequence[dict], dt: float = 1e-3) -> TaskMap:
+def build_taskmap(model: Model, st: Structure, stack: Sequence[dict], dt: float = 1e-3, force_refs: bool = False) -> TaskMap:
     """`stack` lists the task nodes of a tasks.yaml in file order (dicts with the yaml's own keys).  Gains follow the
     factories: Kd = 2 sqrt(Kp) for se3 / com / posture / momentum / contact (tasks.cpp:57,107,140,204,360), kp and kd both
-    given for self-collision (tasks.cpp:398-399)."""
+    given for self-collision (tasks.cpp:398-399).  force_refs: the row also carries a 6-number force reference per contact, behind
+    everything else (TaskMap.contact_fref)."""
     blocks: List[TaskBlock] = []
     sc: List[TaskBlock] = []
     off = 0
@@ -288,12 +293,17 @@ def build_taskmap(model: Model, st: Structure, stack: Sequence[dict], dt: float 
     for _ in contacts:
         cref.append(off)
         off += 24  # a full sample: placement 12, velocity 6, acceleration 6
+    fref = None
+    if force_refs:
+        fref = np.array([off + 6 * i for i in range(len(contacts))], dtype=np.int32)
+        off += 6 * len(contacts)
     ckp = np.array([float(c["kp"]) for c in contacts], dtype=np.float64)
     tm = TaskMap(blocks=blocks, sel_col=st.sel_col.copy(), posture_kp=pkp, posture_kd=2.0 * np.sqrt(pkp), posture_ref=posture_ref,
                  contact_frame=np.array([model.frame(c["joint"]) for c in contacts], dtype=np.int32),
                  contact_kp=ckp, contact_kd=2.0 * np.sqrt(ckp), contact_ref=np.array(cref, dtype=np.int32),
                  n_bound=model.na if has_bounds else 0, dt=dt, nref=off, n_acteq=st.n_acteq, cop=st.cop_task >= 0,
-                 contact_points=np.ascontiguousarray(np.stack([c.points.T for c in st.contacts])) if st.nc else np.zeros(0))
+                 contact_points=np.ascontiguousarray(np.stack([c.points.T for c in st.contacts])) if st.nc else np.zeros(0),
+                 contact_fref=fref, contact_fref_all=fref)
     assert st.n_acteq == sum(int(np.sum(np.asarray([ch != "0" for ch in n.get("mask", "1" * model.na)]))) for n in stack if n["type"] == "torque")
     assert (st.cop_task >= 0) == any(n["type"] == "cop" for n in stack)
     # the structure (which rows exist) and the map (how they are computed) must describe the same stack
@@ -735,11 +745,13 @@ def random_stack(model: Model, seed: int, n_contacts: int = 2) -> Tuple[Structur
 
 # ---- a fleet in different contact sets (wbcqp_tick_mixed / wbcqp_rollout_mixed) ---------------------------------------
 
-def contact_set_maps(model: Model, stack: Sequence[dict], sets: Dict[str, Tuple[Structure, Sequence[str]]], dt: float = 1e-3) -> Dict[str, TaskMap]:
+def contact_set_maps(model: Model, stack: Sequence[dict], sets: Dict[str, Tuple[Structure, Sequence[str]]], dt: float = 1e-3,
+                     force_refs: bool = False) -> Dict[str, TaskMap]:
     """Task maps of a stack's contact subsets, all on the FULL stack's reference layout: sets = {name: (structure, contact names kept)}.
     A subset keeps the tasks of the stack and the contacts named; its contacts' references point at the offsets they have in the map of
     the whole stack, and its nref is the whole stack's -- so one reference row serves every set (what wbcqp_tick_mixed needs; the
-    reference's remove_contact / add_contact change the QP, not the task references, pos_tracker.cpp:246-263)."""
+    reference's remove_contact / add_contact change the QP, not the task references, pos_tracker.cpp:246-263).  force_refs: 6 numbers
+    per contact of the WHOLE stack behind everything else, a contact's block at one offset in every set's map."""
     contact_names = [n["name"] for n in stack if n["type"] == "contact"]
     maps = {}
     for name, (st, kept) in sets.items():
@@ -752,31 +764,37 @@ def contact_set_maps(model: Model, stack: Sequence[dict], sets: Dict[str, Tuple[
     c0 = some.posture_ref + (model.na if some.sel_col.size else 0)
     full_off = {nm: c0 + 24 * i for i, nm in enumerate(contact_names)}
     nref = c0 + 24 * len(contact_names)
+    full_fref = {nm: nref + 6 * i for i, nm in enumerate(contact_names)}
+    if force_refs:
+        nref += 6 * len(contact_names)
     for name, (st, kept) in sets.items():
         tm = maps[name]
         kept_in_order = [nm for nm in contact_names if nm in kept]
         tm.contact_ref = np.array([full_off[nm] for nm in kept_in_order], dtype=np.int32)
         tm.nref = nref
+        if force_refs:
+            tm.contact_fref = np.array([full_fref[nm] for nm in kept_in_order], dtype=np.int32)
+            tm.contact_fref_all = np.array([full_fref[nm] for nm in contact_names], dtype=np.int32)
         assert [b.ref for b in tm.blocks] == [b.ref for b in some.blocks] and tm.posture_ref == some.posture_ref
     return maps
 
 
-def talos_contact_sets(model: Model, dt: float = 1e-3) -> Dict[str, Tuple[Structure, TaskMap]]:
+def talos_contact_sets(model: Model, dt: float = 1e-3, force_refs: bool = False) -> Dict[str, Tuple[Structure, TaskMap]]:
     """Talos's three contact sets under a walk: both feet, no left foot, no right foot (the single-support structure keeps ONE contact;
     the stack without the right one has the same shape)."""
     from . import structure as S
     sets = {"both": (S.talos_structure(), ["contact_lfoot", "contact_rfoot"]),
             "no_l": (S.talos_structure(single_support=True), ["contact_rfoot"]),
             "no_r": (S.talos_structure(single_support=True), ["contact_lfoot"])}
-    maps = contact_set_maps(model, talos_stack(), sets, dt)
+    maps = contact_set_maps(model, talos_stack(), sets, dt, force_refs)
     return {k: (sets[k][0], maps[k]) for k in sets}
 
 
-def icub_contact_sets(model: Model, dt: float = 1e-3) -> Dict[str, Tuple[Structure, TaskMap]]:
+def icub_contact_sets(model: Model, dt: float = 1e-3, force_refs: bool = False) -> Dict[str, Tuple[Structure, TaskMap]]:
     """iCub's: both feet, and one foot (the right one, as structure.icub_structure(single_support=True))."""
     from . import structure as S
     sets = {"both": (S.icub_structure(), ["contact_lfoot", "contact_rfoot"]), "no_l": (S.icub_structure(single_support=True), ["contact_rfoot"])}
-    maps = contact_set_maps(model, icub_stack(), sets, dt)
+    maps = contact_set_maps(model, icub_stack(), sets, dt, force_refs)
     return {k: (sets[k][0], maps[k]) for k in sets}
 
 

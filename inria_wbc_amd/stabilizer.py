@@ -3,6 +3,8 @@
     step(stab, state, inputs)      one tick for a batch: CoP estimator (src/estimators/cop.cpp there), its moving averages
                                    (include/inria_wbc/estimators/filtering.hpp), the force filters and the admittance laws
                                    (src/controllers/humanoid_pos_tracker.cpp:134-302, src/stabilizers/stabilizer.cpp) on a reference row
+    zmp_distribute, zmp_admittance the ZMP force distributor (stabilizer.cpp:277-311, 340-440): the weight split between the feet, a 6-D force reference each
+    ZmpDistributor, ZmpLatch       its gains and reference-row offsets (capi.Handle.stabilize_zmp); which robots have moved to the zmp_w slot of a mixed tick
     euler_012 / recompose          Eigen's eulerAngles(0, 1, 2) [UPSTREAM-RECALL] and Rx Ry Rz back, in any float type (np.longdouble for a scale)
     Stabilizer, from_taskmap       what describes a stabiliser to the library (capi.Handle.stabilize), offsets found by task name
     TALOS_GAINS                    the gains of the reference's shipped stabiliser files, as constants
@@ -22,19 +24,25 @@ import numpy as np
 MAX_WINDOW = 64
 FMIN = 30.0  # Cop::fmin(): a float compared as 30.0
 COP, LCOP, RCOP, COM, LANKLE, RANKLE, FFDA, ERR_COP, ERR_FORCE = 1, 2, 4, 8, 16, 32, 64, 128, 256
+ZMP, ERR_ZMP = 512, 1024
 N_FILTERS, N_CHANNELS = 5, 8
 F_COP, F_LCOP, F_RCOP, F_LFORCE, F_RFORCE = range(5)
 _CHANNELS = ((0, 1), (2, 3), (4, 5), (6,), (7,))  # a filter's channels in the ring
 
 # The reference's shipped stabiliser files (etc/<robot>/stab_fixed_base.yaml, stab_single_support.yaml, stab_double_support.yaml): filter_size, com,
-# ankle, ffda per behaviour type.  Its use_zmp (true in Talos' support files) is not built: tools/emit_configs.py writes use_zmp: false.
+# ankle, ffda per behaviour type, and zmp_p, zmp_d, zmp_w where the file has use_zmp: true (Talos' support files).  The C ABI runs that law
+# (wbcqp_stabilize_zmp); the C++ facade does not, so tools/emit_configs.py keeps writing use_zmp: false.
 _COM = (0.001, 0.001, 0.0003, 0.0003, 0.00000003, 0.00000003)
 _ANKLE = (0.25, 0.25, 0.0001, 0.001, 0.00001, 0.00001)
 _ZERO6, _ZERO3 = (0.0,) * 6, (0.0,) * 3
+_ZMP_P, _ZMP_D = (0.0, 0.0, 2.0, 10.0, 10.0, 0.0), (0.0, 0.0, 0.0005, 0.0001, 0.002, 0.0)
+_ZMP_SS = dict(zmp_p=_ZMP_P, zmp_d=_ZMP_D, zmp_w=(1.0, 1.0, 0.01, 2.0, 2.0, 2.0))
+_ZMP_DS = dict(zmp_p=_ZMP_P, zmp_d=_ZMP_D, zmp_w=(1.0, 1.0, 1.0, 2.0, 2.0, 2.0))
+_ZMP_OFF = dict(zmp_p=_ZERO6, zmp_d=_ZERO6, zmp_w=_ZERO6)
 STAB_FILES = {
-    "talos": {"fixed_base": dict(window=7, com_gains=_ZERO6, ankle_gains=_ZERO6, ffda_gains=_ZERO3),
-              "single_support": dict(window=5, com_gains=_COM, ankle_gains=_ANKLE, ffda_gains=_ZERO3),
-              "double_support": dict(window=7, com_gains=_COM, ankle_gains=_ANKLE, ffda_gains=(0.0003, 0.0, 0.0))},
+    "talos": {"fixed_base": dict(window=7, com_gains=_ZERO6, ankle_gains=_ZERO6, ffda_gains=_ZERO3, **_ZMP_OFF),
+              "single_support": dict(window=5, com_gains=_COM, ankle_gains=_ANKLE, ffda_gains=_ZERO3, **_ZMP_SS),
+              "double_support": dict(window=7, com_gains=_COM, ankle_gains=_ANKLE, ffda_gains=(0.0003, 0.0, 0.0), **_ZMP_DS)},
     "icub": {"fixed_base": dict(window=7, com_gains=_ZERO6, ankle_gains=_ZERO6, ffda_gains=_ZERO3),
              "single_support": dict(window=7, com_gains=_COM, ankle_gains=_ZERO6, ffda_gains=_ZERO3),
              "double_support": dict(window=7, com_gains=_COM, ankle_gains=_ZERO6, ffda_gains=(0.0003, 0.0, 0.0))},
@@ -70,6 +78,44 @@ class Stabilizer:
     normal: Sequence[float] = (0.0, 0.0, 1.0)
     lf_pos: int = 9   # observed frame 0's translation in a row of wbcqp_observables.placement
     rf_pos: int = 21  # observed frame 1's
+
+
+@dataclass
+class ZmpDistributor:
+    """wbcqp_zmp_distributor, member for member: zmp_p, zmp_d and where the two feet's 6-number force references lie in a reference row (-1: not
+    written)."""
+    p: Sequence[float]
+    d: Sequence[float]
+    lf_force_ref: int = -1
+    rf_force_ref: int = -1
+
+
+def zmp_from_taskmap(tm, stack: Sequence[dict], p, d, names: Optional[Dict[str, str]] = None) -> ZmpDistributor:
+    """The distributor of a task map built with force_refs=True: the feet's blocks of TaskMap.contact_fref by the contacts' names in the WHOLE
+    stack's order (the blocks sit at one offset in every contact set's map)."""
+    nm = dict(lf_contact="contact_lfoot", rf_contact="contact_rfoot")
+    nm.update(names or {})
+    contacts = [n["name"] for n in stack if n["type"] == "contact"]
+    fref = tm.contact_fref_all if getattr(tm, "contact_fref_all", None) is not None else tm.contact_fref
+    assert fref is not None and len(fref) == len(contacts), "build the task map with force_refs=True"
+    at = lambda name: int(fref[contacts.index(name)]) if name in contacts else -1  # noqa: E731
+    return ZmpDistributor(p=tuple(p), d=tuple(d), lf_force_ref=at(nm["lf_contact"]), rf_force_ref=at(nm["rf_contact"]))
+
+
+class ZmpLatch:
+    """Which slot of a mixed tick every robot is ticked in: the reference sets zmp_w on the contacts the first time the law runs for a robot and never
+    sets it back.  update(flags) after a tick's stabilize_zmp; which(default, zmp) -> the int32 `which` array of the next wbcqp_tick_mixed, where
+    default / zmp are the indices into wbcqp_mix.slots (scalars, or arrays per robot: three contact sets x two weightings)."""
+
+    def __init__(self, batch: int):
+        self.latched = np.zeros(int(batch), bool)
+
+    def update(self, flags) -> np.ndarray:
+        self.latched |= (np.asarray(flags).astype(np.int64).reshape(-1) & ZMP) != 0
+        return self.latched
+
+    def which(self, default=0, zmp=1) -> np.ndarray:
+        return np.where(self.latched, zmp, default).astype(np.int32)
 
 
 def state_bytes(window: int) -> int:
@@ -217,11 +263,111 @@ def _bump(x, g, angle, den):
     return x + t / den
 
 
-def step(stab: Stabilizer, state: Optional[np.ndarray], inputs: Dict[str, np.ndarray], margins: Optional[list] = None) -> Dict[str, np.ndarray]:
+def _div(a, b):
+    """a / b as IEEE 754 has it (Python raises on a zero divisor)."""
+    if b != 0.0:
+        return a / b
+    if a == 0.0 or math.isnan(a):
+        return math.nan
+    return math.copysign(math.inf, a) * math.copysign(1.0, b)
+
+
+def _norm2(x, y):
+    a, b = x * x, y * y
+    return math.sqrt(a + b)
+
+
+def zmp_distribute(mass, z, PL, PR, left_active=True, right_active=True, margins: Optional[list] = None):
+    """stabilizer.cpp:340-440 (zmp_distributor) with closest_point_on_line: -> (alpha, left [6], right [6], ok).  z: the ZMP (2), PL / PR: the xy of
+    the left / right contact reference's translation.  Everything is projected to z = 0, so every 3-term sum of the reference has one zero term.
+    ok False: the reference throws ("this case should not exists": only non-finite inputs get there); alpha is then NaN and the forces mean nothing."""
+    z = [float(z[0]), float(z[1])]
+    mass = float(mass)
+    ok = True
+    if left_active and right_active:
+        PL, PR = [float(PL[0]), float(PL[1])], [float(PR[0]), float(PR[1])]
+        ux, uy = PR[0] - PL[0], PR[1] - PL[1]
+        sq = ux * ux
+        t = uy * uy
+        sq = sq + t
+        if sq > 0.0:  # [UPSTREAM-RECALL: Eigen/src/Core/Dot.h, normalized(): divided by the norm only where the squared norm is > 0]
+            ln = math.sqrt(sq)
+            ex, ey = ux / ln, uy / ln
+        else:
+            ex, ey = ux, uy
+        a = (z[0] - PR[0]) * ex
+        b = (z[1] - PR[1]) * ey
+        dd = a + b
+        px = PR[0] + ex * dd
+        py = PR[1] + ey * dd
+        L = _norm2(ux, uy)
+        a1 = _norm2(px - PL[0], py - PL[1])
+        a2 = _norm2(PR[0] - px, PR[1] - py)
+        res = abs((L - a1) - a2)
+        if margins is not None:
+            margins.append(("on segment", res, 1e-10, 0.0))
+        if res < 1e-10:
+            alpha = _div(a1, L)  # (coincident feet: 0 / 0, a NaN alpha and no throw)
+        else:
+            if margins is not None:
+                margins.append(("a1 < a2", a1, a2, 0.0))
+            if a1 < a2:
+                alpha = 0.0
+            elif a1 > a2:
+                alpha = 1.0
+            else:
+                alpha, ok = math.nan, False
+    elif right_active:
+        alpha, PL, PR = 1.0, [0.0, 0.0], [float(PR[0]), float(PR[1])]
+    elif left_active:
+        alpha, PL, PR = 0.0, [float(PL[0]), float(PL[1])], [0.0, 0.0]
+    else:
+        raise ValueError("no active foot contact (the reference: is talos jumping ?)")
+    f_r = ((-alpha) * mass) * 9.81
+    f_l = ((-(1.0 - alpha)) * mass) * 9.81
+    tau0 = []
+    for k in range(2):
+        a = (-(PR[k] - z[k])) * f_r
+        b = (PL[k] - z[k]) * f_l
+        tau0.append(a - b)
+    tauR1 = alpha * tau0[1]
+    tauL1 = (1.0 - alpha) * tau0[1]
+    if margins is not None:
+        margins.append(("tau0[0] < 0", tau0[0], 0.0, mass * 9.81))
+    if tau0[0] < 0:
+        tauR0, tauL0 = tau0[0], 0.0
+    else:
+        tauR0, tauL0 = 0.0, tau0[0]
+    return alpha, [0.0, 0.0, f_l, tauL1, -tauL0, 0.0], [0.0, 0.0, f_r, tauR1, -tauR0, 0.0], ok
+
+
+def zmp_admittance(dt, p, d, mass, zmp_ref, cop, PL, PR, left_active=True, right_active=True, margins: Optional[list] = None):
+    """stabilizer.cpp:277-311 (zmp_distributor_admittance) without its far-CoP throw (the CoM law's own, on the same CoP): the distribution t of the
+    model's ZMP, s of the measured one, fref = (t - p e) - (d e) / dt with e = t - s, per foot and entry.
+    -> (left_fref [6], right_fref [6], alpha of the model's ZMP, alpha of the measured one, ok)."""
+    at, tl, tr, ok_t = zmp_distribute(mass, zmp_ref, PL, PR, left_active, right_active, margins)
+    am, sl, sr, ok_s = zmp_distribute(mass, cop, PL, PR, left_active, right_active, margins)
+    out = []
+    for t, s in ((tl, sl), (tr, sr)):
+        f = []
+        for k in range(6):
+            e = t[k] - s[k]
+            a = float(p[k]) * e
+            b = float(d[k]) * e
+            f.append((t[k] - a) - b / float(dt))
+        out.append(f)
+    return out[0], out[1], at, am, ok_t and ok_s
+
+
+def step(stab: Stabilizer, state: Optional[np.ndarray], inputs: Dict[str, np.ndarray], margins: Optional[list] = None,
+         zmp: Optional[ZmpDistributor] = None, zmp_margins: Optional[list] = None) -> Dict[str, np.ndarray]:
     """One tick of the stabiliser for B instances.  inputs: ref [B, nref], wrench [B, 12] (lf_force, lf_torque, rf_force, rf_torque), com [B, 3],
     acom [B, 3], placement [B, ldp], x_prev [B, ldx] or absent / None.  state: a contiguous uint8 array [B, state_bytes(window)], updated in place
     (all-zero bytes: fresh), or None (fresh, discarded).  -> dict(ref_out [B, nref], flags [B] int32, cop [B, 3, 2] with NaN where not valid).
-    margins: a list that receives (decision, value, threshold, scale) of every comparison a result depends on."""
+    margins: a list that receives (decision, value, threshold, scale) of every comparison a result depends on.
+    zmp: the ZMP force distributor (use_zmp), run exactly when the CoM law runs, after it and before the ankle laws: it writes the two feet's force
+    references into their blocks of the row (ZMP), or trips ERR_ZMP like the other guards; the result gains alpha [B, 2] (of the model's ZMP, of the
+    measured one; NaN where the law did not run).  zmp_margins: receives the distributor's own decisions ("on segment", "a1 < a2", "tau0[0] < 0")."""
     ref = np.asarray(inputs["ref"], dtype=np.float64)
     B, W = ref.shape[0], int(stab.window)
     wrench, com, acom, place = (np.asarray(inputs[k], dtype=np.float64).reshape(B, -1) for k in ("wrench", "com", "acom", "placement"))
@@ -236,6 +382,9 @@ def step(stab: Stabilizer, state: Optional[np.ndarray], inputs: Dict[str, np.nda
     dt = float(stab.dt)
     dt2 = dt * dt
     pc, pa, g, nrm = ([float(x) for x in v] for v in (stab.com_gains, stab.ankle_gains, stab.ffda_gains, stab.normal))
+    if zmp is not None:
+        assert stab.lf_contact_ref >= 0 or stab.rf_contact_ref >= 0, "no active foot contact (the reference: is talos jumping ?)"
+        out["alpha"] = np.full((B, 2), np.nan)
     for i in range(B):
         F = _Filters(rows[i], W)
         lf, lt, rf, rt = ([float(x) for x in wrench[i, 3 * k:3 * k + 3]] for k in range(4))
@@ -289,15 +438,27 @@ def step(stab: Stabilizer, state: Optional[np.ndarray], inputs: Dict[str, np.nda
         err_cop = bool(valid and _far(valid[0], valid[1], margins))
         err_cop = bool(do_l and _far(cops[1][0], cops[1][1], margins)) or err_cop
         err_cop = bool(do_r and _far(cops[2][0], cops[2][1], margins)) or err_cop
+        fz = None
+        if zmp is not None and valid and not err_cop:  # zmp_distributor_admittance, on the contacts' references as they lie in ref
+            la, ra = stab.lf_contact_ref >= 0, stab.rf_contact_ref >= 0
+            PL = [float(x) for x in ref[i, stab.lf_contact_ref:stab.lf_contact_ref + 2]] if la else [0.0, 0.0]
+            PR = [float(x) for x in ref[i, stab.rf_contact_ref:stab.rf_contact_ref + 2]] if ra else [0.0, 0.0]
+            k = float(com[i, 2]) / 9.81
+            zref = []
+            for c in range(2):
+                t = k * float(acom[i, c])
+                zref.append(float(com[i, c]) - t)
+            fz = zmp_admittance(dt, zmp.p, zmp.d, stab.mass, zref, valid, PL, PR, la, ra, zmp_margins)
+        err_zmp = fz is not None and not fz[4]
         err_force = False
-        if do_f and not err_cop:
+        if do_f and not err_cop and not err_zmp:
             mg = stab.mass * 9.81
             ten_mg = 10.0 * mg
             if margins is not None:
                 margins.append(("10 M g", abs(fz_l + fz_r), ten_mg, ten_mg))
             err_force = abs(fz_l + fz_r) > ten_mg
-        if err_cop or err_force:
-            out["flags"][i] = flags | (ERR_COP if err_cop else 0) | (ERR_FORCE if err_force else 0)
+        if err_cop or err_zmp or err_force:
+            out["flags"][i] = flags | (ERR_COP if err_cop else 0) | (ERR_ZMP if err_zmp else 0) | (ERR_FORCE if err_force else 0)
             continue
         r = out["ref_out"][i]
         if valid:  # com_admittance
@@ -313,6 +474,12 @@ def step(stab: Stabilizer, state: Optional[np.ndarray], inputs: Dict[str, np.nda
                 t = pc[4 + c] * cor
                 r[o + 6 + c] = float(r[o + 6 + c]) - t / dt2
             flags |= COM
+        if fz is not None:
+            for o, f in ((zmp.lf_force_ref, fz[0]), (zmp.rf_force_ref, fz[1])):
+                if o >= 0:
+                    r[o:o + 6] = f
+            out["alpha"][i] = (fz[2], fz[3])
+            flags |= ZMP
         for do, cop, pos, o, oc, bit in ((do_l, cops[1], lp, stab.lf_ref, stab.lf_contact_ref, LANKLE), (do_r, cops[2], rp, stab.rf_ref, stab.rf_contact_ref, RANKLE)):
             if not do:  # ankle_admittance
                 continue

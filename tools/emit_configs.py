@@ -166,7 +166,7 @@ def emit_icub_model_files():
 
 
 def emit_stabilizer_files():
-    """The reference's three stabiliser files per humanoid (use_zmp: false: the ZMP distributor is not built) and a CONTROLLER tree on the model
+    """The reference's three stabiliser files per humanoid (use_zmp: false: the facade does not run the ZMP distributor) and a CONTROLLER tree on the model
     that switches the stabiliser on, as etc/talos/talos_pos_tracker.yaml and etc/icub/humanoid_pos_tracker.yaml do."""
     from inria_wbc_amd import stabilizer as stb
     for robot, model_file in (("talos", "talos_like.model.yaml"), ("icub", "icub_like.model.yaml")):
