@@ -1033,7 +1033,9 @@ class Handle:
         self._check(self.lib.wbcqp_sync(self._h, C.c_void_p(stream)))
 
     # ---- host-pointer path ----
-    def solve_batch_host(self, slot: int, inputs: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    def solve_batch_host(self, slot: int, inputs: Dict[str, np.ndarray], hint=None) -> Dict[str, np.ndarray]:
+        """wbcqp_solve_batch_host.  hint: [batch, 8] words (any 32-bit integer type) that fill outputs.active_mask before the call -- under
+        FLAG_WARM_START the library reads them as the pick hint (include/wbcqp.h); None: zeros, no hint."""
         st = self._structs[slot]
         L = st.field_lengths()
         batch = int(np.asarray(inputs["h"]).reshape(-1, st.nv).shape[0])
@@ -1050,6 +1052,8 @@ class Handle:
                    status=np.full(batch, -99, np.int32), iters=np.zeros(batch, np.int32),
                    objective=np.zeros(batch, self.np_dtype), n_active=np.zeros(batch, np.int32),
                    active_mask=np.zeros((batch, 8), np.uint32))  # (in/out: zeros = no warm-start hint; out = the solution's active rows)
+        if hint is not None:
+            out["active_mask"][:] = np.ascontiguousarray(hint).view(np.uint32).reshape(batch, 8)
         cout = COutputs(*[out[k].ctypes.data for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask")])
         self._check(self.lib.wbcqp_solve_batch_host(self._h, slot, batch, C.byref(cin), C.byref(cout)))
         out["tau"] = out["tau"][:, :st.na]

@@ -176,8 +176,24 @@ def assemble(st, inputs: Dict[str, np.ndarray], index: int = 0):
     return H, g, CE[:neq], ce0[:neq], CI[:nin2], ci0[:nin2]
 
 
-def eiquadprog(H, g, CE, ce0, CI, ci0, max_iter: int = 1000):
-    """eiquadprog-fast solve_quadprog on a generic dense QP. Returns dict(x,u,A,iq,iters,fval,status)."""
+c_uint32_p = C.POINTER(C.c_uint32)
+
+
+def _hint_words(hint, batch: Optional[int] = None):
+    """A warm-start hint as the C side takes it: None -> a null pointer; else 8 uint32 words per QP (bit r % 32 of word r / 32 = one-sided CI
+    row r, wbcqp_outputs.active_mask's numbering), any integer type.  Returns (array kept alive by the caller or None, pointer or None)."""
+    if hint is None:
+        return None, None
+    a = np.ascontiguousarray(hint)
+    a = (a.view(np.uint32) if a.dtype.itemsize == 4 else a.astype(np.uint32)).reshape((-1, 8) if batch is not None else (8,))
+    assert batch is None or a.shape[0] == batch, (a.shape, batch)
+    a = np.ascontiguousarray(a)
+    return a, a.ctypes.data_as(c_uint32_p)
+
+
+def eiquadprog(H, g, CE, ce0, CI, ci0, max_iter: int = 1000, hint=None):
+    """eiquadprog-fast solve_quadprog on a generic dense QP. Returns dict(x,u,A,iq,iters,fval,status).
+    hint: WBCQP_FLAG_WARM_START's 8 mask words (wbco_eiquadprog_fast_hint); None: eiquadprog's own rule."""
     H = np.ascontiguousarray(H, np.float64); g = np.ascontiguousarray(g, np.float64)
     n = g.size
     CE = np.ascontiguousarray(CE, np.float64).reshape(-1, n); ce0 = np.ascontiguousarray(ce0, np.float64).reshape(-1)
@@ -187,9 +203,15 @@ def eiquadprog(H, g, CE, ce0, CI, ci0, max_iter: int = 1000):
     iq = C.c_int(0); it = C.c_int(0); fv = C.c_double(0.0)
     CEp = CE if neq else np.zeros((1, n)); ce0p = ce0 if neq else np.zeros(1)
     CIp = CI if nin2 else np.zeros((1, n)); ci0p = ci0 if nin2 else np.zeros(1)
-    status = lib().wbco_eiquadprog_fast(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
-                                        _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
-                                        int(max_iter), None)
+    keep, hp = _hint_words(hint)
+    if hp is None:
+        status = lib().wbco_eiquadprog_fast(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
+                                            _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
+                                            int(max_iter), None)
+    else:
+        status = lib().wbco_eiquadprog_fast_hint(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
+                                                 _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
+                                                 int(max_iter), None, hp)
     return dict(x=x, u=u[:iq.value].copy(), A=A[:iq.value].copy(), iq=iq.value, iters=it.value, fval=fv.value, status=status)
 
 
@@ -202,9 +224,10 @@ EV_PICK, EV_FULL_ADD, EV_DEPENDENT, EV_PARTIAL_DROP, EV_DUAL_DROP, EV_EXIT_PSI, 
 EV_NAMES = ("PICK", "FULL_ADD", "DEPENDENT", "PARTIAL_DROP", "DUAL_DROP", "EXIT_PSI", "EXIT_NONE", "UNBOUNDED", "MAX_ITER")
 
 
-def eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter: int = 1000, cap: int = 8192):
+def eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter: int = 1000, cap: int = 8192, hint=None):
     """eiquadprog() through wbco_eiquadprog_fast_log: the same dict plus `events`, an int32 [count, 4] array of
-    (code, row, position, iq) records (EV_*; row / position -1 where an event has none; iq before the event takes effect)."""
+    (code, row, position, iq) records (EV_*; row / position -1 where an event has none; iq before the event takes effect).
+    hint: as eiquadprog()'s (wbco_eiquadprog_fast_hint_log)."""
     H = np.ascontiguousarray(H, np.float64); g = np.ascontiguousarray(g, np.float64)
     n = g.size
     CE = np.ascontiguousarray(CE, np.float64).reshape(-1, n); ce0 = np.ascontiguousarray(ce0, np.float64).reshape(-1)
@@ -216,23 +239,30 @@ def eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter: int = 1000, cap: int = 8192
     CIp = CI if nin2 else np.zeros((1, n)); ci0p = ci0 if nin2 else np.zeros(1)
     rec = np.zeros((cap, 4), np.int32)
     log = _EventLog(cap, 0, _ip(rec))
-    status = lib().wbco_eiquadprog_fast_log(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
-                                            _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
-                                            int(max_iter), None, C.byref(log))
+    keep, hp = _hint_words(hint)
+    if hp is None:
+        status = lib().wbco_eiquadprog_fast_log(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
+                                                _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
+                                                int(max_iter), None, C.byref(log))
+    else:
+        status = lib().wbco_eiquadprog_fast_hint_log(n, neq, nin2, _dp(H), _dp(g), _dp(CEp), _dp(ce0p), _dp(CIp), _dp(ci0p),
+                                                     _dp(x), _dp(u), _ip(A), C.byref(iq), C.byref(it), C.byref(fv),
+                                                     int(max_iter), None, hp, C.byref(log))
     assert log.count <= cap, ("event log overflow", log.count, cap)
     return dict(x=x, u=u[:iq.value].copy(), A=A[:iq.value].copy(), iq=iq.value, iters=it.value, fval=fv.value, status=status,
                 events=rec[:log.count].copy())
 
 
-def tick_log(st, inputs: Dict[str, np.ndarray], index: int = 0, ref: Optional[dict] = None):
+def tick_log(st, inputs: Dict[str, np.ndarray], index: int = 0, ref: Optional[dict] = None, hint=None):
     """The event log of QP `index` of a structured input set: assemble() then eiquadprog_log() with the structure's max_iter.
     x and the iteration count are asserted BITWISE those of tick_batch (`ref`: its outputs for the whole set, if the caller has them),
-    so a log always describes the run the parity tests compare against.  Returns eiquadprog_log's dict."""
+    so a log always describes the run the parity tests compare against.  Returns eiquadprog_log's dict.
+    hint: THIS QP's 8 mask words (then `ref`, if given, is tick_batch's output under the whole set's hints)."""
     H, g, CE, ce0, CI, ci0 = assemble(st, inputs, index)
-    out = eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter=st.max_iter)
+    out = eiquadprog_log(H, g, CE, ce0, CI, ci0, max_iter=st.max_iter, hint=hint)
     if ref is None:
         one = {k: np.asarray(v)[index:index + 1] for k, v in inputs.items() if not k.startswith("_")}
-        ref, index = tick_batch(st, one), 0
+        ref, index = tick_batch(st, one, hint=hint), 0
     assert out["iters"] == int(ref["iters"][index]), ("logged run took another path", out["iters"], int(ref["iters"][index]))
     assert out["x"].tobytes() == np.ascontiguousarray(ref["x"][index]).tobytes(), "logged run's x is not tick_batch's, bit for bit"
     return out
@@ -272,10 +302,11 @@ def active_to_mask(active: np.ndarray, n_active: np.ndarray, words: int = 8) -> 
     return m
 
 
-def tick_batch(st, inputs: Dict[str, np.ndarray], nthreads: int = 1):
+def tick_batch(st, inputs: Dict[str, np.ndarray], nthreads: int = 1, hint=None):
     """P1..P4 for every QP of a [B, len] input set. Returns dict(x, tau, status, iters, active, n_active, fval, active_mask):
     `active` [B, neq + nin2] is eiquadprog's A (equality i tagged -i-1, else the one-sided CI row), padded with ACTIVE_PAD
-    beyond n_active; `active_mask` the same set in the C ABI's form; `fval` the objective."""
+    beyond n_active; `active_mask` the same set in the C ABI's form; `fval` the objective.
+    hint: [B, 8] mask words, one warm-start hint per QP (wbco_tick_batch_hint); None: wbco_tick_batch."""
     ost = OracleStructure(st)
     batch = np.asarray(inputs["h"]).reshape(-1, st.nv).shape[0]
     arrs = _prep_inputs(st, inputs, batch)
@@ -284,7 +315,11 @@ def tick_batch(st, inputs: Dict[str, np.ndarray], nthreads: int = 1):
     active = np.full((batch, max(st.neq + st.nin2, 1)), ACTIVE_PAD, np.int32); n_active = np.zeros(batch, np.int32); fval = np.zeros(batch)
     bin_ = _BatchInputs(*[_dp(arrs[k]) for k in _FIELDS])
     bout = _BatchOutputs(_dp(x), _dp(tau), _ip(status), _ip(iters), _ip(active), _ip(n_active), _dp(fval))
-    lib().wbco_tick_batch(C.byref(ost.c), int(batch), C.byref(bin_), C.byref(bout), int(nthreads))
+    keep, hp = _hint_words(hint, batch)
+    if hp is None:
+        lib().wbco_tick_batch(C.byref(ost.c), int(batch), C.byref(bin_), C.byref(bout), int(nthreads))
+    else:
+        lib().wbco_tick_batch_hint(C.byref(ost.c), int(batch), C.byref(bin_), C.byref(bout), int(nthreads), hp)
     return dict(x=x, tau=tau[:, :st.na], status=status, iters=iters, active=active, n_active=n_active, fval=fval,
                 active_mask=active_to_mask(active, n_active))
 

@@ -406,7 +406,7 @@ int wbco_eiquadprog_fast(int n, int neq, int nin2,
                          double* x, double* u_out, int* A_out, int* iq_out, int* iter_out, double* fval,
                          int max_iter, double* ws_in)
 {
-    return wbco_eiquadprog_fast_log(n, neq, nin2, H, g, CE, ce0, CI, ci0, x, u_out, A_out, iq_out, iter_out, fval, max_iter, ws_in, NULL);
+    return wbco_eiquadprog_fast_hint_log(n, neq, nin2, H, g, CE, ce0, CI, ci0, x, u_out, A_out, iq_out, iter_out, fval, max_iter, ws_in, NULL, NULL);
 }
 
 int wbco_eiquadprog_fast_log(int n, int neq, int nin2,
@@ -415,6 +415,27 @@ int wbco_eiquadprog_fast_log(int n, int neq, int nin2,
                              const double* CI, const double* ci0,
                              double* x, double* u_out, int* A_out, int* iq_out, int* iter_out, double* fval,
                              int max_iter, double* ws_in, wbco_event_log* log)
+{
+    return wbco_eiquadprog_fast_hint_log(n, neq, nin2, H, g, CE, ce0, CI, ci0, x, u_out, A_out, iq_out, iter_out, fval, max_iter, ws_in, NULL, log);
+}
+
+int wbco_eiquadprog_fast_hint(int n, int neq, int nin2,
+                              const double* H, const double* g,
+                              const double* CE, const double* ce0,
+                              const double* CI, const double* ci0,
+                              double* x, double* u_out, int* A_out, int* iq_out, int* iter_out, double* fval,
+                              int max_iter, double* ws_in, const uint32_t* hint)
+{
+    return wbco_eiquadprog_fast_hint_log(n, neq, nin2, H, g, CE, ce0, CI, ci0, x, u_out, A_out, iq_out, iter_out, fval, max_iter, ws_in, hint, NULL);
+}
+
+/* The one body of the solver: every entry point above comes here (hint and log may each be NULL). */
+int wbco_eiquadprog_fast_hint_log(int n, int neq, int nin2,
+                                  const double* H, const double* g,
+                                  const double* CE, const double* ce0,
+                                  const double* CI, const double* ci0,
+                                  double* x, double* u_out, int* A_out, int* iq_out, int* iter_out, double* fval,
+                                  int max_iter, double* ws_in, const uint32_t* hint, wbco_event_log* log)
 {
     double* ws = ws_in ? ws_in : (double*)malloc(sizeof(double) * (size_t)wbco_ws_size(n, neq, nin2));
     const long m = neq + nin2 + 2;
@@ -560,10 +581,25 @@ l2:
      * in place when it comes back here after a failed add_constraint, which re-selects the
      * just-excluded constraint; the evident intent (GI step 2 over the non-excluded set) is kept. */
     ss = 0.0;
-    for (int i = 0; i < nin2; ++i) {
-        if (s[i] < ss && iai[i] != -1 && iaexcl[i]) {
-            ss = s[i];
-            ip = i;
+    if (hint) {
+        /* WBCQP_FLAG_WARM_START's rule (include/wbcqp.h), stated here once: among the rows whose hint bit is set (bit i % 32 of word i / 32;
+         * the mask has 256 bits, bits at and beyond nin2 mean nothing) that are violated, not active and not excluded, the most violated is
+         * the pick (first index wins ties).  Only when there is none does eiquadprog's scan below run.  A rejected (dependent) hinted row is
+         * excluded like any other; the psi exit at step 1 does not know about the hint. */
+        const int nh = nin2 < 256 ? nin2 : 256;
+        for (int i = 0; i < nh; ++i) {
+            if (((hint[i >> 5] >> (i & 31)) & 1u) && s[i] < ss && iai[i] != -1 && iaexcl[i]) {
+                ss = s[i];
+                ip = i;
+            }
+        }
+    }
+    if (ss >= 0.0) { /* (no hint, or no hinted row stands: eiquadprog's rule, unchanged) */
+        for (int i = 0; i < nin2; ++i) {
+            if (s[i] < ss && iai[i] != -1 && iaexcl[i]) {
+                ss = s[i];
+                ip = i;
+            }
         }
     }
     if (ss >= 0.0) {
@@ -703,6 +739,12 @@ long wbco_tick_ws_size(const wbco_structure* st)
 /* One control tick of the path: Controller::_solve lines 244-251 (controller.cpp). */
 int wbco_tick(const wbco_structure* st, const wbco_inputs* in, wbco_outputs* out, double* ws_in)
 {
+    return wbco_tick_hint(st, in, out, ws_in, NULL);
+}
+
+/* wbco_tick with the warm start's hint (8 words; NULL: none -- then it IS wbco_tick) */
+int wbco_tick_hint(const wbco_structure* st, const wbco_inputs* in, wbco_outputs* out, double* ws_in, const uint32_t* hint)
+{
     int n, neq, nin2, r1;
     wbco_sizes(st, &n, &neq, &nin2, &r1);
     double* ws = ws_in ? ws_in : (double*)malloc(sizeof(double) * (size_t)wbco_tick_ws_size(st));
@@ -718,8 +760,8 @@ int wbco_tick(const wbco_structure* st, const wbco_inputs* in, wbco_outputs* out
     wbco_assemble_ws(st, in, H, g, CE, ce0, CI, ci0, aws);
     int iq = 0, iter = 0;
     double fval = 0.0;
-    int est = wbco_eiquadprog_fast(n, neq, nin2, H, g, CE, ce0, CI, ci0, out->x, out->lambda, out->active,
-                                   &iq, &iter, &fval, st->max_iter, qws);
+    int est = wbco_eiquadprog_fast_hint(n, neq, nin2, H, g, CE, ce0, CI, ci0, out->x, out->lambda, out->active,
+                                        &iq, &iter, &fval, st->max_iter, qws, hint);
     /* SolverHQuadProgFast::solve status map */
     int status;
     switch (est) {
@@ -769,6 +811,7 @@ typedef struct {
     long total;
     atomic_long* next;
     pthread_barrier_t* start;
+    const uint32_t* hint; /* [batch][8] or NULL */
 } batch_job;
 
 enum { WBCO_CHUNK = 4 };
@@ -817,7 +860,7 @@ static void* batch_worker(void* arg)
             out.tau = first ? job->out->tau + (size_t)i * na : stau;
             out.lambda = NULL;
             out.active = (first && job->out->active) ? job->out->active + (size_t)i * (neq + nin2) : NULL;
-            wbco_tick(st, &in, &out, ws);
+            wbco_tick_hint(st, &in, &out, ws, job->hint ? job->hint + (size_t)i * 8 : NULL);
             if (first) {
                 job->out->status[i] = out.status;
                 job->out->iters[i] = out.iters;
@@ -832,8 +875,17 @@ static void* batch_worker(void* arg)
 
 /* reps passes over the batch on nthreads threads; returns the seconds between the start line and the last thread's end
  * (negative on error).  reps <= 1: one pass. */
+static double tick_batch_run(const wbco_structure* st, int batch, const wbco_batch_inputs* in,
+                             const wbco_batch_outputs* out, int nthreads, int reps, const uint32_t* hint);
+
 double wbco_tick_batch_timed(const wbco_structure* st, int batch, const wbco_batch_inputs* in,
                              const wbco_batch_outputs* out, int nthreads, int reps)
+{
+    return tick_batch_run(st, batch, in, out, nthreads, reps, NULL);
+}
+
+static double tick_batch_run(const wbco_structure* st, int batch, const wbco_batch_inputs* in,
+                             const wbco_batch_outputs* out, int nthreads, int reps, const uint32_t* hint)
 {
     if (batch <= 0) return 0.0;
     if (reps < 1) reps = 1;
@@ -842,7 +894,7 @@ double wbco_tick_batch_timed(const wbco_structure* st, int batch, const wbco_bat
     if ((long)nthreads * WBCO_CHUNK > total) nthreads = (int)((total + WBCO_CHUNK - 1) / WBCO_CHUNK);
     atomic_long next;
     atomic_init(&next, 0);
-    batch_job job = {st, in, out, batch, total, &next, NULL};
+    batch_job job = {st, in, out, batch, total, &next, NULL, hint};
     if (nthreads == 1) {
         const double t0 = now_s();
         batch_worker(&job);
@@ -872,6 +924,13 @@ int wbco_tick_batch(const wbco_structure* st, int batch, const wbco_batch_inputs
                     const wbco_batch_outputs* out, int nthreads)
 {
     return wbco_tick_batch_timed(st, batch, in, out, nthreads, 1) < 0.0 ? -1 : 0;
+}
+
+/* wbco_tick_batch with one hint per QP: hint [batch][8] (NULL: none) */
+int wbco_tick_batch_hint(const wbco_structure* st, int batch, const wbco_batch_inputs* in,
+                         const wbco_batch_outputs* out, int nthreads, const uint32_t* hint)
+{
+    return tick_batch_run(st, batch, in, out, nthreads, 1, hint) < 0.0 ? -1 : 0;
 }
 
 

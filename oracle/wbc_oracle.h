@@ -22,6 +22,8 @@
 #ifndef WBC_ORACLE_H
 #define WBC_ORACLE_H
 
+#include <stdint.h>
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -155,6 +157,22 @@ int wbco_eiquadprog_fast_log(int n, int neq, int nin2,
                              const double* CI, const double* ci0,
                              double* x, double* u, int* A, int* iq_out, int* iter_out, double* fval,
                              int max_iter, double* ws, wbco_event_log* log);
+/* The same with WBCQP_FLAG_WARM_START's pick rule (include/wbcqp.h; stated at step 2 of wbc_oracle.c): hint = 8 words, bit i % 32 of word
+ * i / 32 names one-sided CI row i; NULL = no hint, and then these ARE the functions above (which pass NULL through the same code).  An
+ * all-zero and an all-ones hint give the cold run too: with no row hinted the first scan finds nothing, with every row hinted the two
+ * scans coincide. */
+int wbco_eiquadprog_fast_hint(int n, int neq, int nin2,
+                              const double* H, const double* g,
+                              const double* CE, const double* ce0,
+                              const double* CI, const double* ci0,
+                              double* x, double* u, int* A, int* iq_out, int* iter_out, double* fval,
+                              int max_iter, double* ws, const uint32_t* hint);
+int wbco_eiquadprog_fast_hint_log(int n, int neq, int nin2,
+                                  const double* H, const double* g,
+                                  const double* CE, const double* ce0,
+                                  const double* CI, const double* ci0,
+                                  double* x, double* u, int* A, int* iq_out, int* iter_out, double* fval,
+                                  int max_iter, double* ws, const uint32_t* hint, wbco_event_log* log);
 int wbco_eiquadprog_fast(int n, int neq, int nin2,
                          const double* H, const double* g,
                          const double* CE, const double* ce0,
@@ -170,6 +188,7 @@ double wbco_eiquadprog_timed(int n, int neq, int nin2, const double* H, const do
 /* P1+P2+P3+P4 for one QP. ws may be NULL (malloc) or wbco_tick_ws_size(st) doubles. */
 long wbco_tick_ws_size(const wbco_structure* st);
 int wbco_tick(const wbco_structure* st, const wbco_inputs* in, wbco_outputs* out, double* ws);
+int wbco_tick_hint(const wbco_structure* st, const wbco_inputs* in, wbco_outputs* out, double* ws, const uint32_t* hint);
 
 /* Batched driver over contiguous [B][len] arrays, nthreads pthreads (one QP per work item,
  * in the style of qp_timer_test.cpp:55-63 / utest.hpp:62-96). Returns 0. */
@@ -195,6 +214,8 @@ double wbco_tick_batch_timed(const wbco_structure* st, int batch, const wbco_bat
 long wbco_assemble_ws_size(const wbco_structure* st);
 int wbco_tick_batch(const wbco_structure* st, int batch, const wbco_batch_inputs* in,
                     const wbco_batch_outputs* out, int nthreads);
+int wbco_tick_batch_hint(const wbco_structure* st, int batch, const wbco_batch_inputs* in,
+                         const wbco_batch_outputs* out, int nthreads, const uint32_t* hint); /* hint [batch][8], NULL: none */
 
 /* After the path: what Controller::_solve does with an optimal solution,
  * src/controllers/controller.cpp:250-272:  v = dq + dt dv;  q = pinocchio::integrate(model, q, dt v);  and, for a

@@ -238,11 +238,12 @@ def _moves(st, a: dict, b: dict, i: int, j: int) -> float:
     return m
 
 
-def classify(st, inp: Dict[str, np.ndarray], seed: int, oracle, base: Optional[dict] = None) -> Tuple[str, dict]:
-    """('A' | 'B' | 'unused', figures) of one QP.  `base`: oracle.tick_log of the unperturbed QP if the caller has it."""
+def classify(st, inp: Dict[str, np.ndarray], seed: int, oracle, base: Optional[dict] = None, hint=None) -> Tuple[str, dict]:
+    """('A' | 'B' | 'unused', figures) of one QP.  `base`: oracle.tick_log of the unperturbed QP if the caller has it.
+    hint: the QP's warm-start hint (8 words), held fixed under the perturbations (tests/warm_hints.py); None: the cold oracle."""
     pert = [perturbed(inp, k, seed) for k in range(N_PERTURB)]
     both = {k: np.concatenate([inp[k]] + [q[k] for q in pert], axis=0) for k in synth.FIELDS}
-    ref = oracle.tick_batch(st, both)
+    ref = oracle.tick_batch(st, both, hint=None if hint is None else np.tile(np.asarray(hint, np.uint32).reshape(1, 8), (N_PERTURB + 1, 1)))
     status, iters = ref["status"], ref["iters"]
     fig = dict(status=int(status[0]), iters=int(iters[0]), iters_seen=sorted(set(int(v) for v in iters)))
     if not (status == status[0]).all() or status[0] not in (OPTIMAL, INFEASIBLE):
@@ -253,9 +254,9 @@ def classify(st, inp: Dict[str, np.ndarray], seed: int, oracle, base: Optional[d
     fig["max_move_x"] = float(np.abs(ref["x"][1:] - ref["x"][0]).max() / max(1.0, np.abs(ref["x"][0]).max())) if status[0] == OPTIMAL else 0.0
     same_path = bool((iters == iters[0]).all())
     if same_path:
-        base = base or oracle.tick_log(st, both, 0, ref)
+        base = base or oracle.tick_log(st, both, 0, ref, hint=hint)
         for k in range(1, N_PERTURB + 1):
-            if not np.array_equal(oracle.tick_log(st, both, k, ref)["events"], base["events"]):
+            if not np.array_equal(oracle.tick_log(st, both, k, ref, hint=hint)["events"], base["events"]):
                 same_path = False
                 break
     if same_path:

@@ -20,14 +20,28 @@ EPS = np.finfo(float).eps
 OPTIMAL, INFEASIBLE, MAX_ITER, ERROR = 0, 1, 3, 4
 
 
-def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, store=None, round5=False):
+def hint_rows(hint, m):
+    """bool [m]: the rows a warm-start hint names -- bit r % 32 of word r / 32 of its 8 words, for r < min(m, 256); the rest mean nothing."""
+    w = np.ascontiguousarray(hint).astype(np.uint64).astype(np.uint32).reshape(8)
+    bits = np.unpackbits(w.view(np.uint8), bitorder="little").astype(bool)
+    out = np.zeros(m, bool)
+    k = min(m, 256)
+    out[:k] = bits[:k]
+    return out
+
+
+def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, store=None, round5=False, hint=None):
     """round5=True: the loop as round 5 runs it (csrc/wbcqp_compact.hpp) -- a drop's rotations in CLOSED FORM (with rho = row p of Ri from column p on,
     S_l = sum_{i<=l} rho_i^2 and P_l = sum_{i<=l} rho_i x_i, the new element of column l of any row x is a_l P_l + b_l x_{l+1}, a_l = -rho_{l+1} / sqrt(S_l S_{l+1}),
     b_l = sqrt(S_l / S_{l+1}), and -P_L / sqrt(S_L) leaves the active block: one running sum per row instead of a chain of rotations), and a constraint's
     reflector kept PENDING: J is left as it is when a constraint is added, the next pick forms d = J_old'n - v (w'n) and applies J <- J - w v' only then.
 
     store=np.float32: SURVEY section 7's "fp32 storage, fp64 accumulate" option, modelled: J and Ri -- the two arrays that live in LDS for
-    the whole loop -- are rounded to `store` after every update, every product and sum stays in f64 (tools/f32_storage_probe.py)."""
+    the whole loop -- are rounded to `store` after every update, every product and sum stays in f64 (tools/f32_storage_probe.py).
+
+    hint: WBCQP_FLAG_WARM_START's 8 mask words (include/wbcqp.h) or None.  At every pick, the hinted rows that are violated, inactive and not
+    excluded go first, the most violated of them (first index on a tie); with none of them standing, the most violated row of all.  Nothing else
+    changes: the psi exit, the exclusion of a rejected row (hinted or not), the steps.  trace["hinted"] lists, per pick, whether the hint decided it."""
     n = g.size
     rnd = (lambda a: a) if store is None else (lambda a: a.astype(store).astype(np.float64))
     neq, m = CE.shape[0], CI.shape[0]
@@ -60,6 +74,7 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
     partial_steps = 0
     psi_tol = m * EPS * c1 * c2 * 100.0
     excl = np.ones(m, bool)
+    hinted = hint_rows(hint, m) if hint is not None else None
     while True:
         it += 1
         if it >= max_iter:
@@ -77,6 +92,12 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
             if cand[ip] >= 0.0:
                 done = True
                 break
+            by_hint = False
+            if hinted is not None:
+                hc = np.where(hinted, cand, 0.0)
+                ih = int(np.argmin(hc))
+                if hc[ih] < 0.0:
+                    ip, by_hint = ih, True
             npv = CI[ip]
             sip = s[ip]
             if trace is not None:
@@ -84,6 +105,8 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
                 c2 = cand.copy(); c2[ip] = 0.0
                 j2 = int(np.argmin(c2))  # the runner-up and how far behind it is: a near tie is decided by the last bits of s
                 trace.setdefault("picks", []).append((ip, float(s[ip]), j2, float(c2[j2])))
+                trace.setdefault("hinted", []).append(by_hint)
+                trace.setdefault("iterates", []).append((x.copy(), act.copy(), excl.copy()))
             u[iq] = 0.0
             A = A[:iq] + [ip]
             if round5 and pend is not None:
@@ -113,6 +136,9 @@ def solve(H, g, CE, ce0, CI, ci0, max_iter=1000, trace=None, projector=False, st
                         t1, lpos = u[neq + kk] / r[kk], kk
                 t2 = -sip / znp if abs(zz) > EPS else np.inf
                 t = min(t1, t2)
+                if trace is not None:  # the step lengths in the running: a near tie among them is decided by the last bits of u / r and s / z'n
+                    lens = sorted([u[neq + kk] / r[kk] for kk in range(mi) if r[kk] > 0.0] + [t2, np.inf])
+                    trace.setdefault("steps", []).append((len(trace.get("picks", [])) - 1, float(lens[0]), float(lens[1]), float(zz)))  # (pick, t, runner-up, z'z)
                 if t == np.inf:
                     if trace is not None:
                         trace["partial_steps"] = partial_steps
