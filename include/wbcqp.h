@@ -74,7 +74,9 @@ extern "C" {
 #define WBCQP_VERSION 151
 #define WBCQP_MAX_STRUCTURES 16
 #define WBCQP_MAX_INEQ_BLOCKS 16
-#define WBCQP_MAX_VARS 126 /* n = nv + 12*nc: every per-QP vector fits one 128-entry LDS slot, n + 2 <= 128 */
+#define WBCQP_MAX_VARS 126 /* n = nv + 12*nc: every per-QP vector fits one 128-entry LDS slot, n + 2 <= 128.  A task stack meets another limit first: it is
+                            * admitted only if its full layout (WBCQP_FLAG_FULL_LDS) fits one CU's 160 KiB of LDS, which no stack with n > 77 does (nv 29 and
+                            * four contacts on a fixed base); with a floating base and two contacts that ends at Talos' size, nv 50, n 74 */
 
 /* ---- return codes of the API itself ---- */
 typedef enum {
@@ -317,7 +319,8 @@ int wbcqp_solve_ragged(wbcqp_handle* handle, int n_groups, const wbcqp_group* gr
  * H [n][n] (symmetric, the lower triangle is read), g [n], CE [neq][n], ce0 [neq], CI [nin][n], ci0 [nin], all row-major,
  * nin = the rows eiquadprog sees (tsid stacks every two-sided row twice: [A; -A], ci0 = [-lb; ub]).  No structure is
  * assumed and none is needed: this is the compatibility path for a caller that owns its HQPData (INTEGRATION.md section
- * 3 shows the tsid SolverHQPBase subclass); wbcqp_solve_batch on a task stack is the fast path.  n <= 96 (J, R and the vectors of one QP must fit one CU's 160 KiB of LDS), nin <= 512.
+ * 3 shows the tsid SolverHQPBase subclass); wbcqp_solve_batch on a task stack is the fast path.  n <= 99 (J, R and the vectors of one QP must fit one CU's 160 KiB of LDS:
+ * 163 392 bytes at n = 99, whatever neq), nin <= 512.
  * Status values are tsid's (wbcqp_hqp_status: eiquadprog UNBOUNDED -> INFEASIBLE, REDUNDANT_EQUALITIES -> ERROR). */
 typedef struct {
     const void *H, *g, *CE, *ce0, *CI, *ci0; /* [batch][...] of the handle's dtype; CE / ce0 may be NULL when neq == 0, CI / ci0 when nin == 0 */

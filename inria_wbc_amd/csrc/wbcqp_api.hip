@@ -380,7 +380,7 @@ int wbcqp_solve_dense(wbcqp_handle* h, int batch, int n, int neq, int nin, int m
     a.o_int = o;
     o += kIntCount / 2 + 2;
     const int lds_bytes = o * 8;
-    if (lds_bytes > 160 * 1024) return fail(h, WBCQP_ERR_UNSUPPORTED, "dense QP does not fit the 160 KiB LDS of one CU (n <= 96)");
+    if (lds_bytes > 160 * 1024) return fail(h, WBCQP_ERR_UNSUPPORTED, "dense QP does not fit the 160 KiB LDS of one CU (n <= 99)");
     a.max_iter = max_iter > 0 ? max_iter : 1000;
     a.count = batch;
     a.H = in->H; a.g = in->g; a.CE = in->CE; a.ce0 = in->ce0; a.CI = in->CI; a.ci0 = in->ci0;

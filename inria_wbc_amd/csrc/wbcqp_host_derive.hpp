@@ -54,7 +54,7 @@ int derive(const wbcqp_structure* st, DevStruct& D, HostBlocks& HB, wbcqp_layout
         }
     }
     D.dense_h = (D.n_acteq > 0 || D.cop_task >= 0) ? 1 : 0;
-    if (D.dense_h && D.n > 80) { why = "a torque / cop task makes H dense: supported for n <= 80 (the dense seam, wbcqp_solve_dense, carries n <= 96)"; return WBCQP_ERR_UNSUPPORTED; }
+    if (D.dense_h && D.n > 80) { why = "a torque / cop task makes H dense: supported for n <= 80 (the dense seam, wbcqp_solve_dense, carries n <= 99)"; return WBCQP_ERR_UNSUPPORTED; }
     if (D.cop_task >= 0 && 3 * D.k > kSlot) { why = "cop rows exceed one 128-entry slot"; return WBCQP_ERR_UNSUPPORTED; }
     D.r1 = D.n_dense + D.n_sel + 6 * D.nc + D.n_acteq + (D.cop_task >= 0 ? 3 : 0);
     HB.n_blocks = st->n_ineq_blocks;
@@ -152,6 +152,10 @@ bool derive_compact(const DevStruct& F, DevStruct& D)
     if (!(n <= 78 && F.neq <= 22 && nv <= 52 && F.nc <= 2 && F.nu <= 8 && F.na <= 64 && F.n_bound <= 64 && F.nin2 <= 256 &&
           F.r1 <= 128 && F.n_tasks <= 64 && (!F.act_bounds || F.act_off >= 0) && n - F.neq <= 64))
         return false;
+    // The loop publishes an actuation row into np with its force padding, up to entry nv + 23.  With 64-entry slots (n <= 62) and nv > 40 that runs into the
+    // slot behind np, d, whose entries from neq on are live: zeros land on the pending v (a fixed base at nv = 52: dv off by twice |x|,
+    // tests/size_edges.py: fixed52).  Such a stack keeps the full layout.
+    if (F.act_bounds && cp::vec_stride(n, nv) == 64 && nv + 23 - 64 >= F.neq) return false;
     int o = 0;
     auto take = [&](int count) { int at = o; o += (count + 1) & ~1; return at; };
     // rows of J: 16-byte aligned, a zero pad pair behind column n, and 2 x odd long -- sixteen rows then start in sixteen

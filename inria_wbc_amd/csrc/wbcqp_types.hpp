@@ -14,7 +14,7 @@ constexpr int kMaxGroups = 8;
 // All small per-QP vectors live at FIXED offsets (multiples of kSlot doubles) from one LDS base, so that the compiler
 // addresses them with immediates instead of keeping ~40 wave-uniform pointers alive in SGPRs (they spilled).
 // Limits that make this legal are checked on the host: n <= 126, n_tasks, n_dense, n_bound, na, 6 nc <= 128,
-// level-1 rows <= 256, one-sided inequality rows <= 512.
+// level-1 rows <= 256, one-sided inequality rows <= 512.  (n <= 126 bounds the slots; the 160 KiB of LDS end a task stack at n = 77, derive.)
 constexpr int kSlot = 128;
 enum VecSlot {
     V_H = 0, V_X, V_NP, V_D, V_Z, V_XOLD, V_R, V_U, V_UOLD, V_Q, V_G, V_W, V_WROW, V_BLB, V_BUB, V_TL, V_TU, V_BC,

@@ -8,19 +8,10 @@ stack runs the generic compact kernel -- through the queue, three per CU where i
 import numpy as np
 import pytest
 
+from tests.size_edges import stack as _stack
 from tests.util import assert_parity, device_outputs, host_outputs
 
 pytestmark = pytest.mark.gpu
-
-
-def _stack(name, nv, na, n_contacts, act):
-    from inria_wbc_amd import structure as S
-    pts = S.contact6d_points(lxn=0.06, lyn=0.045, lxp=0.14, lyp=0.045, lz=0.065)
-    contacts = [S.Contact("contact_%d" % c, pts, (0.0, 0.0, 1.0), 0.3, 5.0, 1500.0) for c in range(n_contacts)]
-    dense = [("lh", 6, 1.0), ("rh", 6, 1.0), ("lf", 6, 100.0), ("com", 3, 1000.0), ("momentum", 2, 100.0), ("__posture__", "posture", 0.5), ("torso", 3, 1.0),
-             ("__contacts__",)]
-    level0 = [(S.INEQ_BOUNDS, 0)] + ([(S.INEQ_ACTUATION, 0)] if act else []) + [(S.INEQ_FORCE, c) for c in range(n_contacts)]
-    return S._mk(name, nv, na, contacts, dense, None, [("self_collision-a", 500.0)], True, act, level0, {"com": 30.0, "posture": 10.0})
 
 
 CASES = [("slots64_with_actuation", 38, 32, 2, True),      # n 62 (aliased rows, table in J), VS 64, TL / TU present
