@@ -63,7 +63,8 @@ extern "C" {
  *        wbcqp_stabilizer_state_bytes, wbcqp_stabilize and wbcqp_stabilize_host (the humanoid controllers' stabiliser: CoP estimator, filters and
  *        admittance laws that rewrite a tick's references, on the device); wbcqp_set_force_references (contact force references carried by a tick's
  *        reference row), wbcqp_zmp_distributor, wbcqp_stabilize_zmp, wbcqp_stabilize_zmp_host, WBCQP_STAB_ZMP and WBCQP_STAB_ERR_ZMP (the stabiliser's
- *        ZMP force distributor).  151 therefore names more than one set of declarations: every one of them
+ *        ZMP force distributor); wbcqp_spd, wbcqp_mass_matrix, wbcqp_forward_dynamics, wbcqp_spd_commands and their _host forms (M(q), the
+ *        accelerations joint torques produce, and the reference's stable-PD torque commands, on the device).  151 therefore names more than one set of declarations: every one of them
  *        contains the one before it unchanged (nothing was removed or resized), so a caller checks for a symbol, not for the number
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
@@ -732,6 +733,55 @@ int wbcqp_inverse_dynamics(wbcqp_handle* handle, int slot, int batch, const void
 /* Same with HOST pointers: stages through device buffers owned by the handle, blocks until done.  `a` is read up to its last row's nv-th entry. */
 int wbcqp_inverse_dynamics_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
                                 void* tau);
+
+/* ---- Which accelerations joint torques produce: M(q), forward dynamics, stable-PD commands ----
+ * The reference's RobotModel::inertia_matrix() (include/inria_wbc/utils/robot_model.hpp:41) and inria_wbc::robot_dart::compute_spd
+ * (include/inria_wbc/robot_dart/cmd.hpp:10-38), the law by which its drivers turn the controller's position targets into torque commands
+ * (--actuators spd).  One wavefront per instance (fdyn_kernel, csrc/wbcqp_fdyn.hpp): the composite-rigid-body algorithm in rnea_kernel's frame, a
+ * Cholesky factorisation of M + diag(damping) in wave-private LDS and two triangular solves.  The slot needs a model (nb <= 64, nv <= 64: what
+ * wbcqp_inverse_dynamics admits).  No atomics, every sum in a fixed order, an instance's result depends on its own rows alone: the same bits from run
+ * to run and at whatever index or batch size the rows arrive.
+ *
+ * wbcqp_mass_matrix:       M [batch][nv][nv], both triangles (the same bits in both), exact zeros between unrelated branches; a floating base's six
+ *                          rows and columns come first, in the base's own axes (pinocchio's convention, as everywhere in this header).
+ * wbcqp_forward_dynamics:  (M(q) + diag(damping)) a = tau - nle(q, v) + sum_k J_k(q)' w_k
+ *       q [batch][nq]; v [batch][nv] or NULL (zero); tau: row i at tau + i * ldt, ALL nv entries (a floating base's six first), or NULL (zero);
+ *       ldt >= nv.  A tick's decoded tau ([batch][na], the actuated joints alone) is not such a row on a floating base: the caller zero-pads it to nv
+ *       (six zeros in front).  Passing pointer - 6 elements with ldt = na is NOT admitted (ldt < nv is refused, and the six entries read in front of
+ *       row 0 would not be the caller's).
+ *       wrench [batch][n_frames][6] or NULL: as for wbcqp_inverse_dynamics -- the frames of wbcqp_set_wrench_frames, linear then angular, in each
+ *       frame's own axes.  damping: HOST [nv] or NULL (zero), finite and >= 0, copied into the kernel's arguments by the call.
+ *       a [batch][nv]; info [batch] or NULL: 0, or k + 1 when the k-th pivot of the factorisation was not > 0 (LAPACK's potrf convention; a NaN in
+ *       q ends here with info = 1): that instance's row of a is all NaN, and no other instance notices.
+ *       The bias nle(q, v) - sum_k J_k' w_k is formed by rnea_kernel INTO the row of a and read back from it: on an F32 handle it passes through
+ *       a float.
+ * wbcqp_spd_commands:      compute_spd.  p = -kp (q + v dt - target), d = -kd v on every dof but a floating base's six (zero there: the
+ *       reference's default floating_base = true), qddot = (M + diag(kd) dt)^-1 (p + d - nle(q, v) + sum_k J_k' w_k), commands = p + d - kd qddot dt.
+ *       target: row i at target + i * ldtarget, na entries (the actuated joints); a q array serves as pointer + 7 elements with ldtarget = nq on a
+ *       floating base.  The reference's robot->constraint_forces() are the `wrench` argument here (the contact wrenches at the selected frames).
+ *       commands [batch][nv]; qddot [batch][nv] or NULL; info as above (a failed instance: both rows NaN).
+ *       The reference's gains are float(10000 / (dt * 1000)) and float(100 / (dt * 1000)).
+ * The output rows (a; commands, qddot) must not overlap any input of the call (q, v, tau, target, wrench) nor each other: the bias is written
+ * into the output row BEFORE tau, v and target are read, so a == tau (in place) or commands over target gives wrong results without a word.
+ * Refused with WBCQP_ERR_INVALID before anything is launched: a slot without a model, batch < 0, q or the required output (M, a, commands) NULL,
+ * ldt < nv with tau given, target NULL or ldtarget < na, wrench given while no frames are selected, a non-finite or negative damping, law NULL,
+ * dt not finite or <= 0, a non-finite kp or kd.  batch == 0: WBCQP_OK, nothing launched. */
+typedef struct {
+    double dt, kp, kd;
+} wbcqp_spd;
+/* DEVICE pointers of the handle's dtype (info: int32), asynchronous on `stream`, ordered like wbcqp_observe. */
+int wbcqp_mass_matrix(wbcqp_handle* handle, int slot, int batch, const void* q, void* M, void* stream);
+int wbcqp_forward_dynamics(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* tau, int ldt, const void* wrench,
+                           const double* damping, void* a, int32_t* info, void* stream);
+int wbcqp_spd_commands(wbcqp_handle* handle, int slot, int batch, const wbcqp_spd* law, const void* q, const void* v, const void* target, int ldtarget,
+                       const void* wrench, void* commands, void* qddot, int32_t* info, void* stream);
+/* Same with HOST pointers: stage through device buffers owned by the handle, block until done.  tau / target are read up to their last row's
+ * nv-th / na-th entry. */
+int wbcqp_mass_matrix_host(wbcqp_handle* handle, int slot, int batch, const void* q, void* M);
+int wbcqp_forward_dynamics_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* tau, int ldt, const void* wrench,
+                                const double* damping, void* a, int32_t* info);
+int wbcqp_spd_commands_host(wbcqp_handle* handle, int slot, int batch, const wbcqp_spd* law, const void* q, const void* v, const void* target,
+                            int ldtarget, const void* wrench, void* commands, void* qddot, int32_t* info);
 
 /* ---- Did a robot hit something: model torques against measured torques over a stream of ticks ----
  * The reference's inria_wbc::safety::TorqueCollisionDetection (src/safety/torque_collision_detection.cpp) with the filters of

@@ -34,6 +34,8 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_set_observed_frames", "wbcqp_observe", "wbcqp_observe_host", "wbcqp_observe_acom", "wbcqp_observe_acom_host",
            "wbcqp_set_collision_spheres", "wbcqp_check_collisions", "wbcqp_check_collisions_host",
            "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host",
+           "wbcqp_mass_matrix", "wbcqp_mass_matrix_host", "wbcqp_forward_dynamics", "wbcqp_forward_dynamics_host",
+           "wbcqp_spd_commands", "wbcqp_spd_commands_host",
            "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host",
            "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host",
            "wbcqp_set_force_references", "wbcqp_stabilize_zmp", "wbcqp_stabilize_zmp_host")
@@ -168,6 +170,10 @@ class CProgram(C.Structure):
 
 class CObservables(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in OBSERVABLES]
+
+
+class CSpd(C.Structure):
+    _fields_ = [("dt", C.c_double), ("kp", C.c_double), ("kd", C.c_double)]
 
 
 class CSphereModel(C.Structure):
@@ -310,6 +316,14 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_set_wrench_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
     lib.wbcqp_inverse_dynamics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.wbcqp_inverse_dynamics_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    lib.wbcqp_mass_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wbcqp_mass_matrix_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.wbcqp_forward_dynamics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+    lib.wbcqp_forward_dynamics_host.argtypes = lib.wbcqp_forward_dynamics.argtypes[:-1]
+    lib.wbcqp_spd_commands.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.wbcqp_spd_commands_host.argtypes = lib.wbcqp_spd_commands.argtypes[:-1]
     lib.wbcqp_torque_monitor_state_bytes.argtypes = [C.POINTER(CTorqueMonitor)]
     lib.wbcqp_torque_monitor_state_bytes.restype = C.c_int64
     lib.wbcqp_detect_torque_collisions.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -659,6 +673,76 @@ class Handle:
         self._check(self.lib.wbcqp_inverse_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(a), int(a.shape[-1]) if a is not None else 0,
                                                          dat(wrench), tau.ctypes.data))
         return tau
+
+    def mass_matrix(self, slot: int, batch: int, q, M, stream: int = 0):
+        """M(q) of `batch` states on device tensors (wbcqp_mass_matrix): q [batch, nq], M [batch, nv, nv], both triangles."""
+        self._check(self.lib.wbcqp_mass_matrix(self._h, slot, int(batch), self._dptr(q), self._dptr(M), C.c_void_p(stream)))
+
+    def mass_matrix_host(self, slot: int, q: np.ndarray) -> np.ndarray:
+        """wbcqp_mass_matrix_host: M [B, nv, nv]."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B, nv = q.shape[0], self._companions_of(slot)["model"][0].nv
+        M = np.zeros((B, nv, nv), self.np_dtype)
+        self._check(self.lib.wbcqp_mass_matrix_host(self._h, slot, B, q.ctypes.data, M.ctypes.data))
+        return M
+
+    @staticmethod
+    def _dptr(t):
+        return t.data_ptr() if t is not None else None  # (an empty tensor stays a given one: the library says what is wrong with it)
+
+    @staticmethod
+    def _damping(damping):
+        """(the array to keep alive, its pointer) of a HOST damping [nv], or (None, None)."""
+        if damping is None:
+            return None, None
+        d = np.ascontiguousarray(damping, dtype=np.float64).reshape(-1)
+        return d, d.ctypes.data
+
+    def forward_dynamics(self, slot: int, batch: int, q, a, v=None, tau=None, ldt: int = 0, wrench=None, damping=None, info=None, stream: int = 0):
+        """(M(q) + diag(damping)) a = tau - nle(q, v) + sum_k J_k' w_k of `batch` states on device tensors (wbcqp_forward_dynamics): q [batch, nq],
+        a [batch, nv]; v [batch, nv] or None (zero); tau or None (zero): ALL nv entries per row, row i ldt elements after row i - 1 (ldt = 0:
+        tau.shape[-1]); wrench [batch, n_frames, 6] or None, as for inverse_dynamics; damping: a HOST array [nv] or None; info: int32 [batch] or None."""
+        if tau is not None and ldt == 0:
+            ldt = int(tau.shape[-1])
+        keep, dptr = self._damping(damping)  # (keep: holds the converted array alive until the call has copied it)
+        self._check(self.lib.wbcqp_forward_dynamics(self._h, slot, int(batch), self._dptr(q), self._dptr(v), self._dptr(tau), int(ldt), self._dptr(wrench),
+                                                    dptr, self._dptr(a), self._dptr(info), C.c_void_p(stream)))
+
+    def forward_dynamics_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, tau: Optional[np.ndarray] = None,
+                              wrench: Optional[np.ndarray] = None, damping=None):
+        """wbcqp_forward_dynamics_host: (a [B, nv], info [B]).  tau [B, ldt] with ldt >= nv: its first nv columns are the torques."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B, nv = q.shape[0], self._companions_of(slot)["model"][0].nv
+        v, tau, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, tau, wrench))
+        a, info = np.zeros((B, nv), self.np_dtype), np.zeros(B, np.int32)
+        dat = lambda t: t.ctypes.data if t is not None else None
+        keep, dptr = self._damping(damping)  # (keep: holds the converted array alive until the call has copied it)
+        self._check(self.lib.wbcqp_forward_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(tau), int(tau.shape[-1]) if tau is not None else 0,
+                                                         dat(wrench), dptr, a.ctypes.data, info.ctypes.data))
+        return a, info
+
+    def spd_commands(self, slot: int, batch: int, law, q, target, commands, v=None, ldtarget: int = 0, wrench=None, qddot=None, info=None,
+                     stream: int = 0):
+        """The reference's compute_spd on device tensors (wbcqp_spd_commands).  law: (dt, kp, kd) -- forward_dynamics.spd_gains(dt) gives the
+        reference's gains; q [batch, nq]; target: na entries per row, ldtarget apart (0: target.shape[-1]); commands [batch, nv]; qddot
+        [batch, nv] or None; wrench as for inverse_dynamics (the reference's constraint forces)."""
+        if ldtarget == 0:
+            ldtarget = int(target.shape[-1])
+        c = CSpd(*[float(x) for x in law])
+        self._check(self.lib.wbcqp_spd_commands(self._h, slot, int(batch), C.byref(c), self._dptr(q), self._dptr(v), self._dptr(target), int(ldtarget),
+                                                self._dptr(wrench), self._dptr(commands), self._dptr(qddot), self._dptr(info), C.c_void_p(stream)))
+
+    def spd_commands_host(self, slot: int, law, q: np.ndarray, v: Optional[np.ndarray], target: np.ndarray, wrench: Optional[np.ndarray] = None):
+        """wbcqp_spd_commands_host: dict(commands [B, nv], qddot [B, nv], info [B]).  target [B, ldtarget] with ldtarget >= na."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B, nv = q.shape[0], self._companions_of(slot)["model"][0].nv
+        v, target, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, target, wrench))
+        res = {"commands": np.zeros((B, nv), self.np_dtype), "qddot": np.zeros((B, nv), self.np_dtype), "info": np.zeros(B, np.int32)}
+        dat = lambda t: t.ctypes.data if t is not None else None
+        c = CSpd(*[float(x) for x in law])
+        self._check(self.lib.wbcqp_spd_commands_host(self._h, slot, B, C.byref(c), q.ctypes.data, dat(v), dat(target), int(target.shape[-1]), dat(wrench),
+                                                     res["commands"].ctypes.data, res["qddot"].ctypes.data, res["info"].ctypes.data))
+        return res
 
     def detect_torque_collisions(self, monitor, batch: int, n_ticks: int, tau_model, ldt: int, tau_sensor, state=None, detected=None, invalid=None,
                                  discrepancy=None, filtered=None, first_tick=None, n_detected=None, stream: int = 0):

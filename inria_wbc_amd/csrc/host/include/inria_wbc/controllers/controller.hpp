@@ -112,6 +112,25 @@ namespace inria_wbc {
             {
                 IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
             }
+            // M(q), B x nv*nv (row-major per instance, both triangles) -- wbcqp_mass_matrix_host.  Only a source that holds a model can tell
+            virtual void mass_matrix(const MatrixXd&, MatrixXd&)
+            {
+                IWBC_ERROR("this problem source has no model: inertia_matrix needs a model-driven source (CONTROLLER.model)");
+            }
+            // a (B x nv) with (M(q) + diag(damping)) a = tau - nle(q, v) + sum_k J_k' w_k: tau B x nv (all dofs), the n named frames and their
+            // wrenches as for inverse_dynamics, damping nv entries or none; info (B): 0, or k + 1 for a pivot that is not > 0 --
+            // wbcqp_forward_dynamics_host.  Only a source that holds a model can tell
+            virtual void forward_dynamics(const MatrixXd&, const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, const MatrixXd&,
+                                          const std::vector<double>&, MatrixXd&, VectorXi&)
+            {
+                IWBC_ERROR("this problem source has no model: forward_dynamics needs a model-driven source (CONTROLLER.model)");
+            }
+            // the reference's compute_spd (robot_dart/cmd.hpp:10-38) for every instance: commands B x nv from q, dq, the targets of the actuated
+            // joints (the last na columns of targetpos), dt, kp, kd -- wbcqp_spd_commands_host.  Only a source that holds a model can tell
+            virtual void spd_commands(const MatrixXd&, const MatrixXd&, const MatrixXd&, double, double, double, MatrixXd&)
+            {
+                IWBC_ERROR("this problem source has no model: compute_spd needs a model-driven source (CONTROLLER.model)");
+            }
             // the foot's own mass added to a measured wrench (robot_model.cpp:171-186 of the reference), per instance, at the states q: force -= m g
             // with m the mass of the body that carries ft_frame, torque += (ankle - sole) x force with the world positions of that body's joint
             // frame and of sole_frame.  Only a source that holds a model can tell
@@ -354,6 +373,43 @@ namespace inria_wbc {
                 if (a_tsid_.rows == B && a_tsid_.cols == nv) a = a_tsid_; // (before the first tick: no acceleration yet)
                 source_->inverse_dynamics(q_tsid_, v_tsid_, a, frames, w, tau);
                 return tau;
+            }
+
+            // The reference's RobotModel::inertia_matrix() (utils/robot_model.hpp:41) for every instance: M(q_tsid()), B x nv*nv (instance i's
+            // matrix row-major in row i, both triangles), computed on the device (wbcqp_mass_matrix_host) when somebody asks and kept with the
+            // state like com_now(): a tick, qp_step_back() or a new problem source makes the next call fetch again.
+            const MatrixXd& inertia_matrix() const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: inertia_matrix needs a model-driven source (CONTROLLER.model)");
+                if (!mass_at_.current(source_.get(), q_tsid_, nullptr)) {
+                    auto self = const_cast<Controller*>(this);
+                    self->mass_at_ = ComputedAt{};
+                    self->source_->mass_matrix(q_tsid_, self->mass_);
+                    self->mass_at_.set(source_.get(), q_tsid_, nullptr);
+                }
+                return mass_;
+            }
+            // The accelerations joint torques produce at the controller's current q_tsid(), dq(false): tau B x nv (all dofs; a floating base's six
+            // first), no wrenches, no damping -- wbcqp_forward_dynamics_host.  info (B): 0, or k + 1 where the k-th pivot was not > 0.
+            MatrixXd forward_dynamics(const MatrixXd& tau, VectorXi* info = nullptr) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: forward_dynamics needs a model-driven source (CONTROLLER.model)");
+                MatrixXd a;
+                VectorXi flags;
+                source_->forward_dynamics(q_tsid_, v_tsid_, tau, {}, MatrixXd(), {}, a, flags);
+                if (info) *info = flags;
+                return a;
+            }
+            // compute_spd of inria_wbc/robots/cmd.hpp goes through here: the states are the caller's (a simulator's), not the controller's
+            MatrixXd spd_commands(const MatrixXd& q, const MatrixXd& dq, const MatrixXd& targetpos, double dt, double kp, double kd) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: compute_spd needs a model-driven source (CONTROLLER.model)");
+                MatrixXd commands;
+                source_->spd_commands(q, dq, targetpos, dt, kp, kd, commands);
+                return commands;
             }
 
             // The reference's self-collision check of the solver's own model (CONTROLLER.check_model_collisions, collision_path;
@@ -630,6 +686,8 @@ namespace inria_wbc {
             std::vector<std::string> obs_names_;
             MatrixXd obs_com_, obs_vcom_, obs_place_, obs_vel_;
             ComputedAt obs_at_; // the state and the source the four above were made for
+            MatrixXd mass_;
+            ComputedAt mass_at_; // the state (q alone) and the source mass_ was made for
 
             std::shared_ptr<ProblemSource> source_;
             const double* tick_references_ = nullptr; // [batch][nref] read by the next tick instead of the source's stored references (the stabiliser's ref_out)

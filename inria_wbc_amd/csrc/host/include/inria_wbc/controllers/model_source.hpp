@@ -351,6 +351,49 @@ namespace inria_wbc {
                                                 tau.data.data()) != WBCQP_OK)
                     IWBC_ERROR("wbcqp_inverse_dynamics_host failed: ", wbcqp_last_error(handle_));
             }
+            // wbcqp_mass_matrix_host on the slot in use
+            void mass_matrix(const MatrixXd& q, MatrixXd& M) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                const int nv = robot_->nv();
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq(), "one state row per instance");
+                M = MatrixXd(batch_, nv * nv);
+                if (wbcqp_mass_matrix_host(handle_, slot_, batch_, q.data.data(), M.data.data()) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_mass_matrix_host failed: ", wbcqp_last_error(handle_));
+            }
+            // wbcqp_forward_dynamics_host on the slot in use.  The wrench frames are inverse_dynamics' selection ON THE SLOT: a call with other
+            // frames -- or none, as Controller::forward_dynamics makes it -- replaces (clears) it there; wrench_frames_ remembers, so the next
+            // inverse_dynamics selects its own again
+            void forward_dynamics(const MatrixXd& q, const MatrixXd& v, const MatrixXd& tau, const std::vector<std::string>& frames, const MatrixXd& wrenches,
+                                  const std::vector<double>& damping, MatrixXd& a, VectorXi& info) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                const int n = (int)frames.size(), nv = robot_->nv();
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq() && v.rows == batch_ && v.cols == nv && tau.rows == batch_ && tau.cols >= nv,
+                            "one state row per instance");
+                IWBC_ASSERT(n <= WBCQP_MAX_WRENCH_FRAMES, "at most ", WBCQP_MAX_WRENCH_FRAMES, " wrench frames");
+                IWBC_ASSERT(n == 0 || (wrenches.rows == batch_ && wrenches.cols == 6 * n), "six numbers per frame and instance");
+                IWBC_ASSERT(damping.empty() || (int)damping.size() == nv, "damping holds nv entries, or none");
+                select_frames(wrench_frames_, frames, wbcqp_set_wrench_frames, "wbcqp_set_wrench_frames");
+                a = MatrixXd(batch_, nv);
+                info.assign(batch_, 0);
+                if (wbcqp_forward_dynamics_host(handle_, slot_, batch_, q.data.data(), v.data.data(), tau.data.data(), tau.cols, n ? wrenches.data.data() : nullptr,
+                                                damping.empty() ? nullptr : damping.data(), a.data.data(), info.data()) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_forward_dynamics_host failed: ", wbcqp_last_error(handle_));
+            }
+            // wbcqp_spd_commands_host on the slot in use, without constraint forces; targetpos: B x na, or B x nv with a floating base's six in front
+            void spd_commands(const MatrixXd& q, const MatrixXd& dq, const MatrixXd& targetpos, double dt, double kp, double kd, MatrixXd& commands) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                const int nv = robot_->nv(), na = robot_->na();
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq() && dq.rows == batch_ && dq.cols == nv, "one state row per instance");
+                IWBC_ASSERT(targetpos.rows == batch_ && (targetpos.cols == na || targetpos.cols == nv), "targetpos holds na or nv entries per instance");
+                commands = MatrixXd(batch_, nv);
+                const wbcqp_spd law = {dt, kp, kd};
+                if (wbcqp_spd_commands_host(handle_, slot_, batch_, &law, q.data.data(), dq.data.data(), targetpos.data.data() + (targetpos.cols - na),
+                                            targetpos.cols, nullptr, commands.data.data(), nullptr, nullptr) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_spd_commands_host failed: ", wbcqp_last_error(handle_));
+            }
             void add_foot_mass(const MatrixXd& q, const std::string& ft_frame, const std::string& sole_frame, MatrixXd& force, MatrixXd& torque) const override
             {
                 if (!robot_->existFrame(ft_frame)) IWBC_ERROR("Frame name ", ft_frame, "is not in model"); // robot_model.cpp:173-176

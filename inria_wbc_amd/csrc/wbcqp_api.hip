@@ -700,6 +700,81 @@ int wbcqp_inverse_dynamics_host(wbcqp_handle* h, int slot, int batch, const void
     });
 }
 
+int wbcqp_mass_matrix(wbcqp_handle* h, int slot, int batch, const void* q, void* M, void* stream)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_mass_matrix(h, slot, batch, q, M, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_mass_matrix(h, *s, batch, q, M, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_mass_matrix_host(wbcqp_handle* h, int slot, int batch, const void* q, void* M)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_mass_matrix(h, slot, batch, q, M, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv;
+    Arr up[1] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}};
+    Arr dn[1] = {{-1, M, B * nv * nv * es, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) { return launch_mass_matrix(h, *s, batch, u[0], d[0], nullptr); });
+}
+
+int wbcqp_forward_dynamics(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* tau, int ldt, const void* wrench,
+                           const double* damping, void* a, int32_t* info, void* stream)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_forward_dynamics(h, slot, batch, q, tau, ldt, wrench, damping, a, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_forward_dynamics(h, *s, batch, q, v, tau, ldt, wrench, damping, a, info, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_forward_dynamics_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* tau, int ldt, const void* wrench,
+                                const double* damping, void* a, int32_t* info)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_forward_dynamics(h, slot, batch, q, tau, ldt, wrench, damping, a, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv;
+    // (tau: rows ldt apart, the last one nv long -- nothing behind it is the caller's to give)
+    Arr up[4] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * nv * es, 0},
+                 {-1, const_cast<void*>(tau), ((B - 1) * (size_t)(tau ? ldt : 0) + nv) * es, 0}, {-1, const_cast<void*>(wrench), B * s->wrench.n * 6 * es, 0}};
+    Arr dn[2] = {{-1, a, B * nv * es, 0}, {-1, info, B * 4, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_forward_dynamics(h, *s, batch, u[0], u[1], u[2], ldt, u[3], damping, d[0], static_cast<int32_t*>(d[1]), nullptr);
+    });
+}
+
+int wbcqp_spd_commands(wbcqp_handle* h, int slot, int batch, const wbcqp_spd* law, const void* q, const void* v, const void* target, int ldtarget,
+                       const void* wrench, void* commands, void* qddot, int32_t* info, void* stream)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_spd_commands(h, slot, batch, law, q, target, ldtarget, wrench, commands, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_spd_commands(h, *s, batch, *law, q, v, target, ldtarget, wrench, commands, qddot, info, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_spd_commands_host(wbcqp_handle* h, int slot, int batch, const wbcqp_spd* law, const void* q, const void* v, const void* target, int ldtarget,
+                            const void* wrench, void* commands, void* qddot, int32_t* info)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_spd_commands(h, slot, batch, law, q, target, ldtarget, wrench, commands, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv, na = nv - (s->terms.floating_base ? 6 : 0);
+    // (target: rows ldtarget apart, the last one na long)
+    Arr up[4] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * nv * es, 0},
+                 {-1, const_cast<void*>(target), ((B - 1) * (size_t)ldtarget + na) * es, 0}, {-1, const_cast<void*>(wrench), B * s->wrench.n * 6 * es, 0}};
+    Arr dn[3] = {{-1, commands, B * nv * es, 0}, {-1, qddot, B * nv * es, 0}, {-1, info, B * 4, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_spd_commands(h, *s, batch, *law, u[0], u[1], u[2], ldtarget, u[3], d[0], d[1], static_cast<int32_t*>(d[2]), nullptr);
+    });
+}
+
 int64_t wbcqp_torque_monitor_state_bytes(const wbcqp_torque_monitor* monitor)
 {
     return monitor_flaw(monitor) ? 0 : (int64_t)monitor_state_bytes(monitor->n_joints, monitor->filter, monitor->window);

@@ -1,13 +1,16 @@
 // wbcqp_host_queries.hpp -- host side of the model queries on a fleet's states (wbcqp_api.hip): wbcqp_observe, wbcqp_check_collisions and
-// wbcqp_inverse_dynamics, each with the set-up call that puts its table on the slot.  Per query: ONE check_* that the device-pointer and the
+// wbcqp_inverse_dynamics, each with the set-up call that puts its table on the slot, and wbcqp_mass_matrix, wbcqp_forward_dynamics and
+// wbcqp_spd_commands (fdyn_kernel, csrc/wbcqp_fdyn.hpp, behind rnea_kernel for the bias).  Per query: ONE check_* that the device-pointer and the
 // host-pointer entry point share (nothing is staged or launched before it has passed) and ONE launch_* of its kernel (csrc/wbcqp_observe.hpp,
 // wbcqp_collide.hpp, wbcqp_rnea.hpp), one wavefront per instance.  Host code only; included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_host_handle.hpp"
+#include "wbcqp_fdyn.hpp"
 
 namespace {
 
 static_assert(kObservePerBlock == kRneaPerBlock, "the three query kernels hold the same number of instances per workgroup");
+static_assert(kFdynPerBlock == kRneaPerBlock && kFdynMaxDof == kWave, "fdyn_kernel: the same instances per workgroup, one lane per dof");
 static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
 
 // workgroups for `batch` instances at one wavefront each
@@ -223,6 +226,120 @@ int launch_inverse_dynamics(wbcqp_handle* h, const Slot& s, int batch, const voi
         hipLaunchKernelGGL(rnea_kernel<TI>, dim3(query_blocks(batch)), dim3(kRneaThreads), 0, stream, args);
         HIP_TRY(h, hipGetLastError());
         return WBCQP_OK;
+    });
+}
+
+// ---- forward dynamics: wbcqp_mass_matrix, wbcqp_forward_dynamics, wbcqp_spd_commands ----------------------------------------------------------------
+int check_mass_matrix(wbcqp_handle* h, int slot, int batch, const void* q, const void* M, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!q || !M) return fail(h, WBCQP_ERR_INVALID, "q and M are required");
+    if (batch > 0) *s = sl;
+    return WBCQP_OK;
+}
+
+int check_forward_dynamics(wbcqp_handle* h, int slot, int batch, const void* q, const void* tau, int ldt, const void* wrench, const double* damping,
+                           const void* a, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!q || !a) return fail(h, WBCQP_ERR_INVALID, "q and a are required");
+    if (tau && ldt < sl->terms.nv) return fail(h, WBCQP_ERR_INVALID, "ldt must be at least nv");
+    if (wrench && sl->wrench.n == 0) return fail(h, WBCQP_ERR_INVALID, "wrench given, but no frames are selected (wbcqp_set_wrench_frames)");
+    for (int j = 0; damping && j < sl->terms.nv; ++j)
+        if (!std::isfinite(damping[j]) || damping[j] < 0.0) return fail(h, WBCQP_ERR_INVALID, "damping must be finite and >= 0");
+    if (batch > 0) *s = sl;
+    return WBCQP_OK;
+}
+
+int check_spd_commands(wbcqp_handle* h, int slot, int batch, const wbcqp_spd* law, const void* q, const void* target, int ldtarget, const void* wrench,
+                       const void* commands, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (!law) return fail(h, WBCQP_ERR_INVALID, "spd law is NULL");
+    if (!std::isfinite(law->dt) || !(law->dt > 0.0)) return fail(h, WBCQP_ERR_INVALID, "dt must be finite and > 0");
+    if (!std::isfinite(law->kp) || !std::isfinite(law->kd)) return fail(h, WBCQP_ERR_INVALID, "kp / kd is not finite");
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!q || !target || !commands) return fail(h, WBCQP_ERR_INVALID, "q, target and commands are required");
+    if (ldtarget < sl->terms.nv - (sl->terms.floating_base ? 6 : 0)) return fail(h, WBCQP_ERR_INVALID, "ldtarget must be at least na");
+    if (wrench && sl->wrench.n == 0) return fail(h, WBCQP_ERR_INVALID, "wrench given, but no frames are selected (wbcqp_set_wrench_frames)");
+    if (batch > 0) *s = sl;
+    return WBCQP_OK;
+}
+
+// fdyn_kernel<TI, SPD> on arguments filled by `fill(FdynArgs<TI>&)`, behind whatever the stream already holds
+template <bool SPD, typename F> int launch_fdyn(wbcqp_handle* h, const Slot& s, int batch, hipStream_t stream, F&& fill)
+{
+    const TermsDev& T = s.terms;
+    const RneaDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, {T.g[0], T.g[1], T.g[2]}, T.ipool, T.dpool, T.i_jtype, T.i_last, T.i_idxq, T.i_idxv, T.i_anc,
+                    T.i_bodyof, T.i_kof, T.d_place, T.d_inertia, 0, nullptr, nullptr};
+    const int lds = fdyn_lds_bytes(T.nv);
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        FdynArgs<TI> args{};
+        args.D = D;
+        args.batch = batch;
+        fill(args);
+        if (lds > 64 * 1024)
+            HIP_TRY(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&fdyn_kernel<TI, SPD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        hipLaunchKernelGGL((fdyn_kernel<TI, SPD>), dim3(query_blocks(batch)), dim3(kFdynThreads), lds, stream, args);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+int launch_mass_matrix(wbcqp_handle* h, const Slot& s, int batch, const void* q, void* M, hipStream_t stream)
+{
+    return launch_fdyn<false>(h, s, batch, stream, [&](auto& a) {
+        using TI = std::remove_const_t<std::remove_pointer_t<decltype(a.q)>>;
+        a.q = static_cast<const TI*>(q);
+        a.M = static_cast<TI*>(M);
+    });
+}
+
+// the bias nle(q, v) - sum_k J_k' w_k by rnea_kernel into the output row, then fdyn_kernel on it
+int launch_forward_dynamics(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, const void* tau, int ldt, const void* wrench,
+                            const double* damping, void* a, int32_t* info, hipStream_t stream)
+{
+    WB_TRY(launch_inverse_dynamics(h, s, batch, q, v, nullptr, 0, wrench, a, stream));
+    return launch_fdyn<false>(h, s, batch, stream, [&](auto& g) {
+        using TI = std::remove_const_t<std::remove_pointer_t<decltype(g.q)>>;
+        g.q = static_cast<const TI*>(q);
+        g.v = static_cast<const TI*>(v);
+        g.rhs = static_cast<const TI*>(tau);
+        g.ldr = tau ? ldt : 0;
+        g.out = static_cast<TI*>(a);
+        g.info = info;
+        if (damping) std::copy(damping, damping + s.terms.nv, g.damping);
+    });
+}
+
+int launch_spd_commands(wbcqp_handle* h, const Slot& s, int batch, const wbcqp_spd& law, const void* q, const void* v, const void* target, int ldtarget,
+                        const void* wrench, void* commands, void* qddot, int32_t* info, hipStream_t stream)
+{
+    WB_TRY(launch_inverse_dynamics(h, s, batch, q, v, nullptr, 0, wrench, commands, stream));
+    return launch_fdyn<true>(h, s, batch, stream, [&](auto& g) {
+        using TI = std::remove_const_t<std::remove_pointer_t<decltype(g.q)>>;
+        g.q = static_cast<const TI*>(q);
+        g.v = static_cast<const TI*>(v);
+        g.rhs = static_cast<const TI*>(target);
+        g.ldr = ldtarget;
+        g.out = static_cast<TI*>(commands);
+        g.qddot = static_cast<TI*>(qddot);
+        g.info = info;
+        g.dt = law.dt;
+        g.kp = law.kp;
+        g.kd = law.kd;
     });
 }
 
