@@ -64,7 +64,9 @@ extern "C" {
  *        admittance laws that rewrite a tick's references, on the device); wbcqp_set_force_references (contact force references carried by a tick's
  *        reference row), wbcqp_zmp_distributor, wbcqp_stabilize_zmp, wbcqp_stabilize_zmp_host, WBCQP_STAB_ZMP and WBCQP_STAB_ERR_ZMP (the stabiliser's
  *        ZMP force distributor); wbcqp_spd, wbcqp_mass_matrix, wbcqp_forward_dynamics, wbcqp_spd_commands and their _host forms (M(q), the
- *        accelerations joint torques produce, and the reference's stable-PD torque commands, on the device).  151 therefore names more than one set of declarations: every one of them
+ *        accelerations joint torques produce, and the reference's stable-PD torque commands, on the device); wbcqp_reference_frame,
+ *        wbcqp_jacobian_outputs, wbcqp_set_jacobian_frames, wbcqp_jacobians and wbcqp_jacobians_host (frame Jacobians, the CoM Jacobian, the
+ *        centroidal momentum matrix and their drift terms, on the device).  151 therefore names more than one set of declarations: every one of them
  *        contains the one before it unchanged (nothing was removed or resized), so a caller checks for a symbol, not for the number
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
@@ -782,6 +784,50 @@ int wbcqp_forward_dynamics_host(wbcqp_handle* handle, int slot, int batch, const
                                 const double* damping, void* a, int32_t* info);
 int wbcqp_spd_commands_host(wbcqp_handle* handle, int slot, int batch, const wbcqp_spd* law, const void* q, const void* v, const void* target,
                             int ldtarget, const void* wrench, void* commands, void* qddot, int32_t* info);
+
+/* ---- Where a fleet's frames move for a given v: frame Jacobians, the CoM Jacobian, the centroidal momentum matrix ----
+ * What the reference's RobotModel::update(..., update_jacobians = true) fills one robot at a time (include/inria_wbc/utils/robot_model.hpp;
+ * src/utils/robot_model.cpp:92-98, 115-126: computeJointJacobians, jacobianCenterOfMass, RobotModel::jacobian(name, reference_frame)) and the
+ * matrix its controller and tsid's TaskMomentumEquality read as momentumJacobian (controller.cpp:245, task-momentum-equality.cpp:151), for a
+ * whole fleet.  One wavefront per instance (jacobian_kernel, csrc/wbcqp_jacobians.hpp), no atomics, every sum in a fixed order, an instance's
+ * result depends on its own rows alone: the same bits from run to run and at whatever index or batch size the rows arrive.  The slot needs a
+ * model (nb <= 64, nv <= 64: what wbcqp_inverse_dynamics admits).
+ *
+ * reference_frame: pinocchio's values and meanings.  WORLD: the spatial Jacobian about the TRUE world origin in the world's axes (the base
+ * translation is kept, as in wbcqp_observe); LOCAL: at the frame's origin in the frame's own axes; LOCAL_WORLD_ALIGNED: at the frame's origin in
+ * the world's axes.  J_world = Ad(oMf) J_local with wbcqp_observe's placement oMf.
+ *
+ * Each member of wbcqp_jacobian_outputs may be NULL; what is given is written, nothing else:
+ *   J     [batch][n_frames][6][nv]  the frames of wbcqp_set_jacobian_frames, in the order selected (repeats allowed).  Rows: linear (3), angular (3).
+ *                                   Columns in v's order; a floating base's six columns are in the base's own axes, as v is.  The column of a dof
+ *                                   that does not move the frame's body is an exact +0.0.
+ *   Jcom  [batch][3][nv]            the CoM Jacobian, world axes: vcom = Jcom v.
+ *   Ag    [batch][6][nv]            the centroidal momentum matrix: linear, then angular about the CoM, world axes -- the convention of
+ *                                   wbcqp_state.momentum (momentum = Ag v).  Jcom = Ag's linear rows over the total mass.
+ *   drift [batch][n_frames][6]      the frame's classical acceleration with zero joint accelerations and no gravity (what tsid's SE(3) task uses
+ *                                   as Jdot v), in LOCAL or LOCAL_WORLD_ALIGNED axes.  Needs v; not defined for WBCQP_RF_WORLD.
+ *   dAgv  [batch][6]                d(Ag)/dt v: the rate of the centroidal momentum with zero joint accelerations.  Needs v.
+ * q [batch][nq]; v [batch][nv], or NULL when neither drift nor dAgv is asked for (v is not read then).  The arrays of a trace
+ * (wbcqp_trace.q / .v, [n_rec][batch][...]) pass as they are with batch = n_rec * batch: one call answers every recorded tick.
+ * Refused with WBCQP_ERR_INVALID before anything is launched (nothing is written): a slot without a model, batch < 0, outputs NULL or every
+ * member NULL, an unknown reference_frame, J or drift while no frames are selected, drift or dAgv without v, drift with WBCQP_RF_WORLD, q NULL
+ * (batch > 0).  batch == 0: WBCQP_OK, nothing launched. */
+typedef enum { WBCQP_RF_WORLD = 0, WBCQP_RF_LOCAL = 1, WBCQP_RF_LOCAL_WORLD_ALIGNED = 2 } wbcqp_reference_frame;
+#define WBCQP_MAX_JACOBIAN_FRAMES 64
+typedef struct {
+    void *J, *Jcom, *Ag, *drift, *dAgv;
+} wbcqp_jacobian_outputs;
+/* Chooses the frames of J and drift by their indices in the model's frame table: a selection of its own, independent of
+ * wbcqp_set_observed_frames and wbcqp_set_wrench_frames.  n_frames == 0 drops it; wbcqp_set_structure / wbcqp_set_model on the slot drop it with
+ * the model.  WBCQP_ERR_INVALID (and the selection before stays) for a slot without a model, n_frames outside 0 .. WBCQP_MAX_JACOBIAN_FRAMES, a
+ * frame index outside the model. */
+int wbcqp_set_jacobian_frames(wbcqp_handle* handle, int slot, int n_frames, const int32_t* frames);
+/* DEVICE pointers of the handle's dtype, asynchronous on `stream`, ordered like wbcqp_observe.  reference_frame: a wbcqp_reference_frame. */
+int wbcqp_jacobians(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, int reference_frame, const wbcqp_jacobian_outputs* out,
+                    void* stream);
+/* Same with HOST pointers: stage through device buffers owned by the handle, block until done. */
+int wbcqp_jacobians_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, int reference_frame,
+                         const wbcqp_jacobian_outputs* out);
 
 /* ---- Did a robot hit something: model torques against measured torques over a stream of ticks ----
  * The reference's inria_wbc::safety::TorqueCollisionDetection (src/safety/torque_collision_detection.cpp) with the filters of

@@ -36,6 +36,7 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_set_wrench_frames", "wbcqp_inverse_dynamics", "wbcqp_inverse_dynamics_host",
            "wbcqp_mass_matrix", "wbcqp_mass_matrix_host", "wbcqp_forward_dynamics", "wbcqp_forward_dynamics_host",
            "wbcqp_spd_commands", "wbcqp_spd_commands_host",
+           "wbcqp_set_jacobian_frames", "wbcqp_jacobians", "wbcqp_jacobians_host",
            "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host",
            "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host",
            "wbcqp_set_force_references", "wbcqp_stabilize_zmp", "wbcqp_stabilize_zmp_host")
@@ -44,6 +45,8 @@ OBSERVABLES = ("com", "vcom", "placement", "velocity")  # what wbcqp_observe wri
 STAB_INPUTS = ("ref", "wrench", "com", "acom", "placement", "x_prev")  # the arrays of wbcqp_stab_inputs
 STAB_OUTPUTS = ("ref_out", "flags", "cop")  # what wbcqp_stabilize writes (wbcqp_stab_outputs)
 TORQUE_CHECKS = ("detected", "invalid", "discrepancy", "filtered", "first_tick", "n_detected")  # what wbcqp_detect_torque_collisions writes (wbcqp_torque_checks)
+JACOBIAN_OUTPUTS = ("J", "Jcom", "Ag", "drift", "dAgv")  # what wbcqp_jacobians writes (wbcqp_jacobian_outputs); per instance n_frames x 6 x nv, 3 x nv, 6 x nv, n_frames x 6, 6
+RF_WORLD, RF_LOCAL, RF_LOCAL_WORLD_ALIGNED = 0, 1, 2  # wbcqp_reference_frame: pinocchio's values
 COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
 ROW_FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "Acop")  # what wbcqp_problem_data writes (Acop: stacks with a cop task)
@@ -170,6 +173,10 @@ class CProgram(C.Structure):
 
 class CObservables(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in OBSERVABLES]
+
+
+class CJacobianOutputs(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in JACOBIAN_OUTPUTS]
 
 
 class CSpd(C.Structure):
@@ -324,6 +331,9 @@ def load_library(path: Optional[str] = None):
     lib.wbcqp_spd_commands.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]
     lib.wbcqp_spd_commands_host.argtypes = lib.wbcqp_spd_commands.argtypes[:-1]
+    lib.wbcqp_set_jacobian_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
+    lib.wbcqp_jacobians.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CJacobianOutputs), C.c_void_p]
+    lib.wbcqp_jacobians_host.argtypes = lib.wbcqp_jacobians.argtypes[:-1]
     lib.wbcqp_torque_monitor_state_bytes.argtypes = [C.POINTER(CTorqueMonitor)]
     lib.wbcqp_torque_monitor_state_bytes.restype = C.c_int64
     lib.wbcqp_detect_torque_collisions.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -552,7 +562,7 @@ class Handle:
     def _companions_of(self, slot: int, reset: bool = False) -> dict:
         """The slot's record; reset: a fresh one (the library drops the model, the selections of frames and the sphere table with the structure or the model)."""
         if reset or slot not in self._companions:
-            self._companions[slot] = {"model": None, "observed": 0, "spheres": 0, "wrench": 0}
+            self._companions[slot] = {"model": None, "observed": 0, "spheres": 0, "wrench": 0, "jacobian": 0}
         return self._companions[slot]
 
     # ---- device-pointer path (torch tensors are only carriers of device memory) ----
@@ -742,6 +752,39 @@ class Handle:
         c = CSpd(*[float(x) for x in law])
         self._check(self.lib.wbcqp_spd_commands_host(self._h, slot, B, C.byref(c), q.ctypes.data, dat(v), dat(target), int(target.shape[-1]), dat(wrench),
                                                      res["commands"].ctypes.data, res["qddot"].ctypes.data, res["info"].ctypes.data))
+        return res
+
+    def set_jacobian_frames(self, slot: int, frames: Sequence[int]):
+        """Which frames of the slot's model jacobians reports in J and drift: indices into the model's frame table (observe.frame_ids turns names
+        into them), repeats allowed, at most 64 (wbcqp_set_jacobian_frames).  A selection of its own, beside the observed and the wrench frames."""
+        self._select_frames(slot, frames, self.lib.wbcqp_set_jacobian_frames, "jacobian")
+
+    def jacobians(self, slot: int, batch: int, q, v=None, reference_frame: int = RF_LOCAL, J=None, Jcom=None, Ag=None, drift=None, dAgv=None,
+                  stream: int = 0):
+        """Frame Jacobians, the CoM Jacobian and the centroidal momentum matrix of `batch` states on device tensors (wbcqp_jacobians): q [batch, nq],
+        v [batch, nv] (None when neither drift nor dAgv is asked for); outputs, each optional: J [batch, n_frames, 6, nv], Jcom [batch, 3, nv],
+        Ag [batch, 6, nv], drift [batch, n_frames, 6], dAgv [batch, 6]."""
+        out = CJacobianOutputs(*[self._dptr(t) for t in (J, Jcom, Ag, drift, dAgv)])
+        self._check(self.lib.wbcqp_jacobians(self._h, slot, int(batch), self._dptr(q), self._dptr(v), int(reference_frame), C.byref(out),
+                                             C.c_void_p(stream)))
+
+    def jacobians_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, reference_frame: int = RF_LOCAL,
+                       which: Optional[Sequence[str]] = None) -> Dict[str, np.ndarray]:
+        """wbcqp_jacobians_host: a dict of the outputs named in `which` (of JACOBIAN_OUTPUTS).  which None: everything the arguments admit -- Jcom
+        and Ag; J when frames are selected; with v, dAgv and (frames selected, not RF_WORLD) drift.  J and drift are sized from what THIS Handle's
+        set_jacobian_frames last selected on the slot (see observe_host)."""
+        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        B, nv, nf = q.shape[0], self._companions_of(slot)["model"][0].nv, self._companions_of(slot)["jacobian"]
+        if v is not None:
+            v = np.ascontiguousarray(v, dtype=self.np_dtype)
+        if which is None:
+            which = ["Jcom", "Ag"] + (["J"] if nf else []) + (["dAgv"] if v is not None else []) + (
+                ["drift"] if v is not None and nf and reference_frame != RF_WORLD else [])
+        shape = {"J": (B, nf, 6, nv), "Jcom": (B, 3, nv), "Ag": (B, 6, nv), "drift": (B, nf, 6), "dAgv": (B, 6)}
+        res = {k: np.zeros(shape[k], self.np_dtype) for k in which}
+        out = CJacobianOutputs(*[res[k].ctypes.data if k in res else None for k in JACOBIAN_OUTPUTS])
+        self._check(self.lib.wbcqp_jacobians_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, int(reference_frame),
+                                                  C.byref(out)))
         return res
 
     def detect_torque_collisions(self, monitor, batch: int, n_ticks: int, tau_model, ldt: int, tau_sensor, state=None, detected=None, invalid=None,

@@ -131,6 +131,13 @@ namespace inria_wbc {
             {
                 IWBC_ERROR("this problem source has no model: compute_spd needs a model-driven source (CONTROLLER.model)");
             }
+            // Frame Jacobians, the CoM Jacobian and the centroidal momentum matrix at the states q -- wbcqp_jacobians_host.  J (null: not asked for):
+            // B x n*6*nv for the n named frames in the convention reference_frame (pinocchio's values: 0 WORLD, 1 LOCAL, 2 LOCAL_WORLD_ALIGNED),
+            // each frame's 6 x nv block row-major; Jcom: B x 3*nv; Ag: B x 6*nv.  Only a source that holds a model can tell
+            virtual void jacobians(const MatrixXd&, const std::vector<std::string>&, int, MatrixXd*, MatrixXd&, MatrixXd&)
+            {
+                IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
+            }
             // the foot's own mass added to a measured wrench (robot_model.cpp:171-186 of the reference), per instance, at the states q: force -= m g
             // with m the mass of the body that carries ft_frame, torque += (ankle - sole) x force with the world positions of that body's joint
             // frame and of sole_frame.  Only a source that holds a model can tell
@@ -412,6 +419,28 @@ namespace inria_wbc {
                 return commands;
             }
 
+            // The reference's RobotModel::jacobian(name, reference_frame), jacobianCenterOfMass and the momentumJacobian its controller reads
+            // (src/utils/robot_model.cpp:92-98, 115-126; controller.cpp:245) for every instance at q_tsid(): B x 6*nv, B x 3*nv and B x 6*nv
+            // (instance i's matrix row-major in row i; rows linear then angular, a floating base's six columns in the base's own axes; Ag's
+            // angular rows about the CoM), computed on the device (wbcqp_jacobians_host) when somebody asks and kept with the state like
+            // inertia_matrix().  A frame asked for the first time joins the selection and costs one more call.
+            enum ReferenceFrame { WORLD = 0, LOCAL = 1, LOCAL_WORLD_ALIGNED = 2 }; // pinocchio's values
+            MatrixXd jacobian(const std::string& frame, ReferenceFrame rf = WORLD) const
+            {
+                const int at = _ensure_jacobians(&frame, rf);
+                return _observed_block(jac_J_[rf], at, 6 * v_tsid_.cols);
+            }
+            const MatrixXd& jacobian_com() const
+            {
+                _ensure_jacobians(nullptr, LOCAL);
+                return jac_com_;
+            }
+            const MatrixXd& momentum_matrix() const
+            {
+                _ensure_jacobians(nullptr, LOCAL);
+                return jac_ag_;
+            }
+
             // The reference's self-collision check of the solver's own model (CONTROLLER.check_model_collisions, collision_path;
             // controller.hpp:148-150, collision_check.cpp), per instance, for the controller's CURRENT state: computed on the device
             // (wbcqp_check_collisions_host) and kept with the state like the observables above, so a tick or qp_step_back() refreshes it.
@@ -688,6 +717,46 @@ namespace inria_wbc {
             ComputedAt obs_at_; // the state and the source the four above were made for
             MatrixXd mass_;
             ComputedAt mass_at_; // the state (q alone) and the source mass_ was made for
+
+            // the Jacobians of the current state, fetched on demand on the pattern of _ensure_observed: J per convention for the frames asked for
+            // so far, Jcom and Ag with whichever call comes first at a state.  Returns the frame's place in the selection (-1: none asked)
+            int _ensure_jacobians(const std::string* frame, int rf) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
+                IWBC_ASSERT(rf == WORLD || rf == LOCAL || rf == LOCAL_WORLD_ALIGNED, "unknown reference frame ", rf);
+                auto self = const_cast<Controller*>(this);
+                int at = -1;
+                bool added = false;
+                if (frame) {
+                    auto it = std::find(jac_names_.begin(), jac_names_.end(), *frame);
+                    at = (int)std::distance(jac_names_.begin(), it);
+                    if (it == jac_names_.end()) {
+                        self->jac_names_.push_back(*frame);
+                        added = true;
+                    }
+                }
+                if (added)
+                    for (auto& c : self->jac_at_) c = ComputedAt{}; // (the selection grew: what is kept of every convention is the old one's)
+                const ComputedAt& kept = frame ? jac_at_[rf] : jac_com_at_;
+                if (!kept.current(source_.get(), q_tsid_, nullptr)) {
+                    self->jac_com_at_ = ComputedAt{};
+                    if (frame) self->jac_at_[rf] = ComputedAt{};
+                    try {
+                        self->source_->jacobians(q_tsid_, jac_names_, rf, frame ? &self->jac_J_[rf] : nullptr, self->jac_com_, self->jac_ag_);
+                    }
+                    catch (...) {
+                        if (added) self->jac_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
+                        throw;
+                    }
+                    self->jac_com_at_.set(source_.get(), q_tsid_, nullptr);
+                    if (frame) self->jac_at_[rf].set(source_.get(), q_tsid_, nullptr);
+                }
+                return at;
+            }
+            std::vector<std::string> jac_names_;
+            MatrixXd jac_J_[3], jac_com_, jac_ag_; // J: per convention
+            ComputedAt jac_at_[3], jac_com_at_;    // the state (q alone) and the source they were made for
 
             std::shared_ptr<ProblemSource> source_;
             const double* tick_references_ = nullptr; // [batch][nref] read by the next tick instead of the source's stored references (the stabiliser's ref_out)

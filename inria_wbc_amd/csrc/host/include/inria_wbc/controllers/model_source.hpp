@@ -394,6 +394,21 @@ namespace inria_wbc {
                                             targetpos.cols, nullptr, commands.data.data(), nullptr, nullptr) != WBCQP_OK)
                     IWBC_ERROR("wbcqp_spd_commands_host failed: ", wbcqp_last_error(handle_));
             }
+            // wbcqp_jacobians_host on the slot in use; the selection of frames goes to the device when it changes, not per call
+            void jacobians(const MatrixXd& q, const std::vector<std::string>& frames, int reference_frame, MatrixXd* J, MatrixXd& Jcom, MatrixXd& Ag) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                const int n = (int)frames.size(), nv = robot_->nv();
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq(), "one state row per instance");
+                IWBC_ASSERT(n <= WBCQP_MAX_JACOBIAN_FRAMES, "at most ", WBCQP_MAX_JACOBIAN_FRAMES, " frames can have a Jacobian");
+                select_frames(jacobian_frames_, frames, wbcqp_set_jacobian_frames, "wbcqp_set_jacobian_frames");
+                if (J) *J = MatrixXd(batch_, 6 * nv * n);
+                Jcom = MatrixXd(batch_, 3 * nv);
+                Ag = MatrixXd(batch_, 6 * nv);
+                const wbcqp_jacobian_outputs out = {(J && n) ? J->data.data() : nullptr, Jcom.data.data(), Ag.data.data(), nullptr, nullptr};
+                if (wbcqp_jacobians_host(handle_, slot_, batch_, q.data.data(), nullptr, reference_frame, &out) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_jacobians_host failed: ", wbcqp_last_error(handle_));
+            }
             void add_foot_mass(const MatrixXd& q, const std::string& ft_frame, const std::string& sole_frame, MatrixXd& force, MatrixXd& torque) const override
             {
                 if (!robot_->existFrame(ft_frame)) IWBC_ERROR("Frame name ", ft_frame, "is not in model"); // robot_model.cpp:173-176
@@ -518,6 +533,7 @@ namespace inria_wbc {
                 observed_.erase(slot);
                 spheres_.erase(slot);
                 wrench_frames_.erase(slot);
+                jacobian_frames_.erase(slot);
             }
 
             void store(const std::string& name, int off, const std::vector<double>& r)
@@ -551,7 +567,7 @@ namespace inria_wbc {
             std::vector<double> q0_, posture_user_;
             wbcqp_handle* handle_ = nullptr;
             std::map<int, Bound> bounds_;
-            FrameNames observed_, wrench_frames_; // wbcqp_set_observed_frames, wbcqp_set_wrench_frames
+            FrameNames observed_, wrench_frames_, jacobian_frames_; // wbcqp_set_observed_frames, wbcqp_set_wrench_frames, wbcqp_set_jacobian_frames
             // slot -> the collision file whose table it holds (wbcqp_set_collision_spheres) and every table entry's (member, place in the member)
             std::map<int, std::pair<std::string, std::vector<std::pair<std::string, int>>>> spheres_;
             Bound* cur_ = nullptr;

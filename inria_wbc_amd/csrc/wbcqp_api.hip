@@ -775,6 +775,36 @@ int wbcqp_spd_commands_host(wbcqp_handle* h, int slot, int batch, const wbcqp_sp
     });
 }
 
+int wbcqp_set_jacobian_frames(wbcqp_handle* h, int slot, int n_frames, const int32_t* frames)
+{
+    return set_frame_selection(h, slot, &Slot::jacobian, n_frames, frames, WBCQP_MAX_JACOBIAN_FRAMES, "a jacobian frame", "the jacobian frames");
+}
+
+int wbcqp_jacobians(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, int reference_frame, const wbcqp_jacobian_outputs* out, void* stream)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_jacobians(h, slot, batch, q, v, reference_frame, out, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_jacobians(h, *s, batch, q, v, reference_frame, *out, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_jacobians_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, int reference_frame, const wbcqp_jacobian_outputs* out)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_jacobians(h, slot, batch, q, v, reference_frame, out, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv, nf = (size_t)s->jacobian.n;
+    // (v goes up only where the kernel reads it)
+    Arr up[2] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, (out->drift || out->dAgv) ? const_cast<void*>(v) : nullptr, B * nv * es, 0}};
+    Arr dn[5] = {{-1, out->J, B * nf * 6 * nv * es, 0}, {-1, out->Jcom, B * 3 * nv * es, 0}, {-1, out->Ag, B * 6 * nv * es, 0}, {-1, out->drift, B * nf * 6 * es, 0},
+                 {-1, out->dAgv, B * 6 * es, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_jacobians(h, *s, batch, u[0], u[1], reference_frame, wbcqp_jacobian_outputs{d[0], d[1], d[2], d[3], d[4]}, nullptr);
+    });
+}
+
 int64_t wbcqp_torque_monitor_state_bytes(const wbcqp_torque_monitor* monitor)
 {
     return monitor_flaw(monitor) ? 0 : (int64_t)monitor_state_bytes(monitor->n_joints, monitor->filter, monitor->window);

@@ -58,10 +58,11 @@ struct Slot {
     TermsDev terms{};
     std::vector<void*> model_allocs;
     // the model's whole frame table (host copies: only task frames reach the device with the model) and the frames chosen from it, on the device, by
-    // wbcqp_set_observed_frames (wbcqp_observe) and wbcqp_set_wrench_frames (wbcqp_inverse_dynamics); dropped with the model
+    // wbcqp_set_observed_frames (wbcqp_observe), wbcqp_set_wrench_frames (wbcqp_inverse_dynamics) and wbcqp_set_jacobian_frames (wbcqp_jacobians);
+    // dropped with the model
     std::vector<int> frame_body_h;
     std::vector<double> frame_place_h;
-    FrameSel observed, wrench;
+    FrameSel observed, wrench, jacobian;
     // wbcqp_check_collisions: the sphere table of wbcqp_set_collision_spheres, one device allocation; dropped with the model
     CollideDev spheres{};
     void* spheres_alloc = nullptr;
@@ -335,6 +336,7 @@ void release_model(Slot& s)
     release(s.observed);
     release_spheres(s);
     release(s.wrench);
+    release(s.jacobian);
 }
 
 void release(Slot& s)

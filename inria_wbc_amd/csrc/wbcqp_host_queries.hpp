@@ -1,16 +1,22 @@
 // wbcqp_host_queries.hpp -- host side of the model queries on a fleet's states (wbcqp_api.hip): wbcqp_observe, wbcqp_check_collisions and
 // wbcqp_inverse_dynamics, each with the set-up call that puts its table on the slot, and wbcqp_mass_matrix, wbcqp_forward_dynamics and
-// wbcqp_spd_commands (fdyn_kernel, csrc/wbcqp_fdyn.hpp, behind rnea_kernel for the bias).  Per query: ONE check_* that the device-pointer and the
+// wbcqp_spd_commands (fdyn_kernel, csrc/wbcqp_fdyn.hpp, behind rnea_kernel for the bias) and wbcqp_jacobians (jacobian_kernel,
+// csrc/wbcqp_jacobians.hpp).  Per query: ONE check_* that the device-pointer and the
 // host-pointer entry point share (nothing is staged or launched before it has passed) and ONE launch_* of its kernel (csrc/wbcqp_observe.hpp,
 // wbcqp_collide.hpp, wbcqp_rnea.hpp), one wavefront per instance.  Host code only; included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_host_handle.hpp"
 #include "wbcqp_fdyn.hpp"
+#include "wbcqp_jacobians.hpp"
 
 namespace {
 
 static_assert(kObservePerBlock == kRneaPerBlock, "the three query kernels hold the same number of instances per workgroup");
 static_assert(kFdynPerBlock == kRneaPerBlock && kFdynMaxDof == kWave, "fdyn_kernel: the same instances per workgroup, one lane per dof");
+static_assert(kJacobianPerBlock == kRneaPerBlock && WBCQP_MAX_JACOBIAN_FRAMES == kMaxJacobianFrames && kMaxJacobianFrames == kWave,
+              "jacobian_kernel: the same instances per workgroup, one lane per selected frame");
+static_assert(WBCQP_RF_WORLD == kRfWorld && WBCQP_RF_LOCAL == kRfLocal && WBCQP_RF_LOCAL_WORLD_ALIGNED == kRfLocalWorldAligned,
+              "the header and the kernel agree on the reference frames");
 static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
 
 // workgroups for `batch` instances at one wavefront each
@@ -69,7 +75,7 @@ int upload_fresh(wbcqp_handle* h, const void* src, size_t bytes, const char* the
     return WBCQP_OK;
 }
 
-// wbcqp_set_observed_frames / wbcqp_set_wrench_frames: frame indices -> (placement, body) of each from the slot's host copy of the model's frame table;
+// wbcqp_set_observed_frames / wbcqp_set_wrench_frames / wbcqp_set_jacobian_frames: frame indices -> (placement, body) of each from the slot's host copy of the model's frame table;
 // n_frames == 0 drops the selection
 int set_frame_selection(wbcqp_handle* h, int slot, FrameSel Slot::*which, int n_frames, const int32_t* frames, int limit, const char* a_frame,
                         const char* the_frames)
@@ -340,6 +346,45 @@ int launch_spd_commands(wbcqp_handle* h, const Slot& s, int batch, const wbcqp_s
         g.dt = law.dt;
         g.kp = law.kp;
         g.kd = law.kd;
+    });
+}
+
+// ---- differential kinematics: wbcqp_jacobians --------------------------------------------------------------------------------------------------------
+int check_jacobians(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, int rf, const wbcqp_jacobian_outputs* out, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "jacobian outputs struct is NULL");
+    if (rf != WBCQP_RF_WORLD && rf != WBCQP_RF_LOCAL && rf != WBCQP_RF_LOCAL_WORLD_ALIGNED)
+        return fail(h, WBCQP_ERR_INVALID, "unknown reference_frame (WBCQP_RF_WORLD, WBCQP_RF_LOCAL or WBCQP_RF_LOCAL_WORLD_ALIGNED)");
+    if (!out->J && !out->Jcom && !out->Ag && !out->drift && !out->dAgv) return fail(h, WBCQP_ERR_INVALID, "every output is NULL: nothing is asked for");
+    if ((out->J || out->drift) && sl->jacobian.n == 0)
+        return fail(h, WBCQP_ERR_INVALID, "J / drift asked for, but no frames are selected (wbcqp_set_jacobian_frames)");
+    if ((out->drift || out->dAgv) && !v) return fail(h, WBCQP_ERR_INVALID, "drift / dAgv asked for, but v is NULL");
+    if (out->drift && rf == WBCQP_RF_WORLD)
+        return fail(h, WBCQP_ERR_INVALID, "drift asked for with WBCQP_RF_WORLD: a classical acceleration is LOCAL or LOCAL_WORLD_ALIGNED");
+    if (batch == 0) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    *s = sl;
+    return WBCQP_OK;
+}
+
+int launch_jacobians(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, int rf, const wbcqp_jacobian_outputs& out, hipStream_t stream)
+{
+    const TermsDev& T = s.terms;
+    const bool frames = out.J || out.drift;
+    const JacobianDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_last, T.i_idxq, T.i_idxv, T.i_anc, T.i_bodyof, T.i_kof,
+                        T.d_place, T.d_inertia, frames ? s.jacobian.n : 0, s.jacobian.body, s.jacobian.place};
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const JacobianArgs<TI> a{D, static_cast<const TI*>(q), (out.drift || out.dAgv) ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out.J),
+                                 static_cast<TI*>(out.Jcom), static_cast<TI*>(out.Ag), static_cast<TI*>(out.drift), static_cast<TI*>(out.dAgv), rf, batch};
+        hipLaunchKernelGGL(jacobian_kernel<TI>, dim3(query_blocks(batch)), dim3(kJacobianThreads), 0, stream, a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
     });
 }
 
