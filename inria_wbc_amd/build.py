@@ -233,7 +233,7 @@ def check_specialisations(lib_path: str) -> None:
         except ImportError:
             pass
     lib = ctypes.CDLL(lib_path)  # (a private handle on the file just built: the process may already hold the previous libwbcqp.so)
-    lib.wbcqp_layout_of.argtypes = [ctypes.POINTER(capi.CStructure), ctypes.POINTER(capi.CLayout)]
+    capi.declare(lib)
     for name, want in (("talos", 1), ("icub", 2), ("talos_single_support", 3)):
         sb, L = capi.StructureBuffers(structure.STRUCTURES[name]()), capi.CLayout()
         if lib.wbcqp_layout_of(ctypes.byref(sb.c), ctypes.byref(L)) != 0:

@@ -22,6 +22,7 @@ ERR_NAMES = {0: "OK", 1: "INVALID", 2: "HIP", 3: "UNSUPPORTED", 4: "NO_DEVICE", 
 F64, F32 = 0, 1
 K_STAMPS = 32  # phase stamps per QP of the -DWBCQP_STAMPS diagnostic build (kStamps, csrc/wbcqp_prims.hpp)
 FIELDS = ("M", "h", "A", "b1", "Ac", "bc", "blb", "bub", "tlb", "tub", "w", "Acop")
+OUT_FIELDS = ("x", "tau", "status", "iters", "objective", "n_active", "active_mask")  # wbcqp_outputs (active_mask: uint32 [batch, 8], in/out)
 
 # every symbol include/wbcqp.h declares
 EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy", "wbcqp_set_structure",
@@ -86,8 +87,7 @@ class CInputs(C.Structure):
 
 
 class COutputs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("tau", C.c_void_p), ("status", C.c_void_p), ("iters", C.c_void_p),
-                ("objective", C.c_void_p), ("n_active", C.c_void_p), ("active_mask", C.c_void_p)]
+    _fields_ = [(k, C.c_void_p) for k in OUT_FIELDS]
 
 
 class CDesc(C.Structure):
@@ -147,9 +147,6 @@ class CMix(C.Structure):
 
 class CMixedIO(C.Structure):
     _fields_ = [("state", CState), ("out", COutputs), ("q_next", C.c_void_p), ("v_next", C.c_void_p), ("q_solver", C.c_void_p), ("dt", C.c_double)]
-
-
-_lib = None
 
 
 class CTrace(C.Structure):
@@ -258,6 +255,128 @@ def torque_monitor_state_bytes(monitor) -> int:
     return int(load_library().wbcqp_torque_monitor_state_bytes(C.byref(TorqueMonitorBuffers(monitor).c)))
 
 
+def _sig(*argtypes, restype=C.c_int):
+    return restype, list(argtypes)
+
+
+_vp, _int, _p = C.c_void_p, C.c_int, C.POINTER
+# How every symbol of EXPORTS is declared: name -> (restype, argtypes), after the prototypes of include/wbcqp.h (tests/test_capi_binding.py holds the
+# two against each other).  A handle, a stream and an array of the handle's dtype are c_void_p.
+SIGNATURES = {
+    "wbcqp_version": _sig(),
+    "wbcqp_last_error": _sig(_vp, restype=C.c_char_p),
+    "wbcqp_create": _sig(_p(CDesc), _p(_vp)),
+    "wbcqp_destroy": _sig(_vp),
+    "wbcqp_set_structure": _sig(_vp, _int, _p(CStructure)),
+    "wbcqp_layout_of": _sig(_p(CStructure), _p(CLayout)),
+    "wbcqp_solve_batch": _sig(_vp, _int, _int, _p(CInputs), _p(COutputs), _vp),
+    "wbcqp_solve_ragged": _sig(_vp, _int, _p(CGroup), _vp),
+    "wbcqp_solve_dense": _sig(_vp, _int, _int, _int, _int, _int, _p(CDenseInputs), _p(COutputs), _vp),
+    "wbcqp_solve_dense_host": _sig(_vp, _int, _int, _int, _int, _int, _p(CDenseInputs), _p(_p(CDenseOutput))),
+    "wbcqp_allgather_tau": _sig(_vp, _vp, _vp, _vp, C.c_size_t, _vp),
+    "wbcqp_sync": _sig(_vp, _vp),
+    "wbcqp_launch_order": _sig(_vp, c_i32_p, C.c_int32, c_i32_p),
+    "wbcqp_integrate": _sig(_vp, _int, _int, _int, C.c_double, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp),
+    "wbcqp_set_model": _sig(_vp, _int, _p(CModel), _p(CTaskMap)),
+    "wbcqp_check_model": _sig(_p(CStructure), _p(CModel), _p(CTaskMap), c_i32_p),
+    "wbcqp_set_force_references": _sig(_vp, _int, c_i32_p, c_f64_p),
+    "wbcqp_problem_data": _sig(_vp, _int, _int, _p(CState), _p(CInputs), _vp),
+    "wbcqp_tick": _sig(_vp, _int, _int, _p(CTickIO), _vp),
+    "wbcqp_tick_graph_create": _sig(_vp, _int, _int, _p(CTickIO), _p(_vp)),
+    "wbcqp_tick_graph_launch": _sig(_vp, _vp, _vp),
+    "wbcqp_tick_graph_destroy": _sig(_vp, _vp),
+    "wbcqp_rollout": _sig(_vp, _int, _int, _int, _p(CRolloutIO), _vp),
+    "wbcqp_tick_mixed": _sig(_vp, _p(CMix), _int, c_i32_p, _p(CMixedIO), _vp),
+    "wbcqp_rollout_mixed": _sig(_vp, _p(CMix), _int, _int, c_i32_p, _p(CRolloutIO), _vp),
+    "wbcqp_task_costs": _sig(_vp, _int, _int, _p(CInputs), _vp, _vp, _vp, _vp),
+    "wbcqp_rollout_traced": _sig(_vp, _int, _int, _int, _p(CRolloutIO), _p(CTrace), _vp),
+    "wbcqp_rollout_mixed_traced": _sig(_vp, _p(CMix), _int, _int, c_i32_p, _p(CRolloutIO), _p(CTrace), _vp),
+    "wbcqp_check_program": _sig(_p(CProgram), _int, _int),
+    "wbcqp_reference_samples": _sig(_vp, _p(CProgram), _int, _int, _int, _vp, _vp),
+    "wbcqp_rollout_program": _sig(_vp, _int, _int, _int, _int, _p(CRolloutIO), _p(CProgram), _p(CTrace), _vp),
+    "wbcqp_rollout_mixed_program": _sig(_vp, _p(CMix), _int, _int, _int, _p(CRolloutIO), _p(CProgram), _p(CTrace), _vp),
+    "wbcqp_set_observed_frames": _sig(_vp, _int, _int, c_i32_p),
+    "wbcqp_observe": _sig(_vp, _int, _int, _vp, _vp, _p(CObservables), _vp),
+    "wbcqp_observe_acom": _sig(_vp, _int, _int, _vp, _vp, _p(CObservables), _vp, _vp),
+    "wbcqp_set_collision_spheres": _sig(_vp, _int, _p(CSphereModel)),
+    "wbcqp_check_collisions": _sig(_vp, _int, _int, _vp, _p(CCollisions), _vp),
+    "wbcqp_set_wrench_frames": _sig(_vp, _int, _int, c_i32_p),
+    "wbcqp_inverse_dynamics": _sig(_vp, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp),
+    "wbcqp_mass_matrix": _sig(_vp, _int, _int, _vp, _vp, _vp),
+    "wbcqp_forward_dynamics": _sig(_vp, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp),
+    "wbcqp_spd_commands": _sig(_vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp),
+    "wbcqp_set_jacobian_frames": _sig(_vp, _int, _int, c_i32_p),
+    "wbcqp_jacobians": _sig(_vp, _int, _int, _vp, _vp, _int, _p(CJacobianOutputs), _vp),
+    "wbcqp_torque_monitor_state_bytes": _sig(_p(CTorqueMonitor), restype=C.c_int64),
+    "wbcqp_detect_torque_collisions": _sig(_vp, _p(CTorqueMonitor), _int, _int, _vp, _int, _vp, _vp, _p(CTorqueChecks), _vp),
+    "wbcqp_stabilizer_state_bytes": _sig(_p(CStabilizer), restype=C.c_int64),
+    "wbcqp_stabilize": _sig(_vp, _p(CStabilizer), _int, _p(CStabInputs), _vp, _p(CStabOutputs), _vp),
+    "wbcqp_stabilize_zmp": _sig(_vp, _p(CStabilizer), _p(CZmpDistributor), _int, _p(CStabInputs), _vp, _p(CStabOutputs), _vp, _vp),
+}
+# the _host forms that are the device signature without the stream
+for _name in ("wbcqp_solve_batch", "wbcqp_integrate", "wbcqp_problem_data", "wbcqp_tick", "wbcqp_observe", "wbcqp_observe_acom",
+              "wbcqp_check_collisions", "wbcqp_inverse_dynamics", "wbcqp_mass_matrix", "wbcqp_forward_dynamics", "wbcqp_spd_commands",
+              "wbcqp_jacobians", "wbcqp_detect_torque_collisions", "wbcqp_stabilize", "wbcqp_stabilize_zmp"):
+    SIGNATURES[_name + "_host"] = (SIGNATURES[_name][0], SIGNATURES[_name][1][:-1])
+
+
+def declare(lib):
+    """Gives every export of a CDLL of the library (any build of it) its restype and argtypes from SIGNATURES; returns the CDLL."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+def stamp_buffer_setter(lib):
+    """wbcqp_debug_set_stamp_buffer(handle, device buffer of K_STAMPS int64 per QP) of a -DWBCQP_STAMPS build, declared: a diagnostic that is not in
+    the header, so not in EXPORTS.  None on a library without the symbol."""
+    fn = getattr(lib, "wbcqp_debug_set_stamp_buffer", None)
+    if fn is not None:
+        fn.restype, fn.argtypes = C.c_int, [_vp, _vp]
+    return fn
+
+
+def dev_ptr(t):
+    """Device tensor (anything with numel() and data_ptr()), EMPTY IS ABSENT: None or no elements -> NULL."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def dev_ptr_given(t):
+    """Device tensor, EMPTY IS GIVEN: only None -> NULL (the library says what is wrong with an empty tensor); an int is a device address."""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def host_ptr(a):
+    """Host (numpy) array: None -> NULL."""
+    return a.ctypes.data if a is not None else None
+
+
+def _check_state(state):
+    assert state is None or (state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"]), "state: a contiguous uint8 array [B, state_bytes]"
+
+
+def host_outputs(spec, names, null_empty: bool = False):
+    """The outputs of a _host call.  spec: name -> (shape, dtype) in the field order of the C struct that takes them; names: the ones asked for.
+    Returns (name -> zero-filled array for `names`, the pointers in spec order: NULL for a name not asked for and, with null_empty, for an array
+    without elements)."""
+    res = {k: np.zeros(*spec[k]) for k in names}
+    return res, [res[k].ctypes.data if k in res and (res[k].size or not null_empty) else None for k in spec]
+
+
+def c_inputs(ptrs) -> CInputs:
+    """wbcqp_inputs from name -> pointer; a field the mapping lacks is NULL."""
+    return CInputs(*[ptrs.get(k) for k in FIELDS])
+
+
+def _check(lib, rc: int, handle=None):
+    if rc != WBCQP_OK:
+        raise WbcqpError(rc, (lib.wbcqp_last_error(handle) or b"").decode())
+
+
+_lib = None
+
+
 def load_library(path: Optional[str] = None):
     """Loads libwbcqp.so -- after torch, when torch is installed: the library links libamdhip64.so.7, and a process in which it comes FIRST gets
     /opt/rocm's HIP runtime while a later `import torch` brings torch's bundled one.  Two runtimes on one GPU work, but the first one then answers
@@ -276,81 +395,8 @@ def load_library(path: Optional[str] = None):
         raise FileNotFoundError(
             "%s is missing: build it with `python -m inria_wbc_amd.build` (hipcc, gfx950). "
             "There is no fallback implementation." % path)
-    lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
-    lib.wbcqp_version.restype = C.c_int
-    lib.wbcqp_last_error.restype = C.c_char_p
-    lib.wbcqp_last_error.argtypes = [C.c_void_p]
-    lib.wbcqp_create.argtypes = [C.POINTER(CDesc), C.POINTER(C.c_void_p)]
-    lib.wbcqp_destroy.argtypes = [C.c_void_p]
-    lib.wbcqp_set_structure.argtypes = [C.c_void_p, C.c_int, C.POINTER(CStructure)]
-    lib.wbcqp_layout_of.argtypes = [C.POINTER(CStructure), C.POINTER(CLayout)]
-    lib.wbcqp_solve_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CInputs), C.POINTER(COutputs), C.c_void_p]
-    lib.wbcqp_solve_batch_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CInputs), C.POINTER(COutputs)]
-    lib.wbcqp_solve_ragged.argtypes = [C.c_void_p, C.c_int, C.POINTER(CGroup), C.c_void_p]
-    lib.wbcqp_allgather_tau.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.wbcqp_sync.argtypes = [C.c_void_p, C.c_void_p]
-    lib.wbcqp_integrate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.wbcqp_set_model.argtypes = [C.c_void_p, C.c_int, C.POINTER(CModel), C.POINTER(CTaskMap)]
-    lib.wbcqp_check_model.argtypes = [C.POINTER(CStructure), C.POINTER(CModel), C.POINTER(CTaskMap), C.POINTER(C.c_int32)]
-    lib.wbcqp_problem_data.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CState), C.POINTER(CInputs), C.c_void_p]
-    lib.wbcqp_problem_data_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CState), C.POINTER(CInputs)]
-    lib.wbcqp_tick.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CTickIO), C.c_void_p]
-    lib.wbcqp_tick_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CTickIO)]
-    lib.wbcqp_tick_graph_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CTickIO), C.POINTER(C.c_void_p)]
-    lib.wbcqp_tick_graph_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.wbcqp_tick_graph_destroy.argtypes = [C.c_void_p, C.c_void_p]
-    lib.wbcqp_tick_mixed.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, c_i32_p, C.POINTER(CMixedIO), C.c_void_p]
-    lib.wbcqp_rollout_mixed.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, c_i32_p, C.POINTER(CRolloutIO), C.c_void_p]
-    lib.wbcqp_task_costs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.wbcqp_rollout_traced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CTrace), C.c_void_p]
-    lib.wbcqp_rollout_mixed_traced.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, c_i32_p, C.POINTER(CRolloutIO), C.POINTER(CTrace),
-                                               C.c_void_p]
-    lib.wbcqp_check_program.argtypes = [C.POINTER(CProgram), C.c_int, C.c_int]
-    lib.wbcqp_reference_samples.argtypes = [C.c_void_p, C.POINTER(CProgram), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.wbcqp_rollout_program.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CProgram), C.POINTER(CTrace),
-                                          C.c_void_p]
-    lib.wbcqp_rollout_mixed_program.argtypes = [C.c_void_p, C.POINTER(CMix), C.c_int, C.c_int, C.c_int, C.POINTER(CRolloutIO), C.POINTER(CProgram),
-                                                C.POINTER(CTrace), C.c_void_p]
-    lib.wbcqp_set_observed_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
-    lib.wbcqp_observe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p]
-    lib.wbcqp_observe_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables)]
-    lib.wbcqp_observe_acom.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p, C.c_void_p]
-    lib.wbcqp_observe_acom_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(CObservables), C.c_void_p]
-    lib.wbcqp_set_collision_spheres.argtypes = [C.c_void_p, C.c_int, C.POINTER(CSphereModel)]
-    lib.wbcqp_check_collisions.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions), C.c_void_p]
-    lib.wbcqp_check_collisions_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(CCollisions)]
-    lib.wbcqp_set_wrench_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
-    lib.wbcqp_inverse_dynamics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.wbcqp_inverse_dynamics_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    lib.wbcqp_mass_matrix.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.wbcqp_mass_matrix_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.wbcqp_forward_dynamics.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]
-    lib.wbcqp_forward_dynamics_host.argtypes = lib.wbcqp_forward_dynamics.argtypes[:-1]
-    lib.wbcqp_spd_commands.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.wbcqp_spd_commands_host.argtypes = lib.wbcqp_spd_commands.argtypes[:-1]
-    lib.wbcqp_set_jacobian_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, c_i32_p]
-    lib.wbcqp_jacobians.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(CJacobianOutputs), C.c_void_p]
-    lib.wbcqp_jacobians_host.argtypes = lib.wbcqp_jacobians.argtypes[:-1]
-    lib.wbcqp_torque_monitor_state_bytes.argtypes = [C.POINTER(CTorqueMonitor)]
-    lib.wbcqp_torque_monitor_state_bytes.restype = C.c_int64
-    lib.wbcqp_detect_torque_collisions.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                   C.POINTER(CTorqueChecks), C.c_void_p]
-    lib.wbcqp_detect_torque_collisions_host.argtypes = [C.c_void_p, C.POINTER(CTorqueMonitor), C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
-                                                        C.c_void_p, C.POINTER(CTorqueChecks)]
-    lib.wbcqp_stabilizer_state_bytes.argtypes = [C.POINTER(CStabilizer)]
-    lib.wbcqp_stabilizer_state_bytes.restype = C.c_int64
-    lib.wbcqp_stabilize.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.c_int, C.POINTER(CStabInputs), C.c_void_p, C.POINTER(CStabOutputs), C.c_void_p]
-    lib.wbcqp_stabilize_host.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.c_int, C.POINTER(CStabInputs), C.c_void_p, C.POINTER(CStabOutputs)]
-    lib.wbcqp_set_force_references.argtypes = [C.c_void_p, C.c_int, c_i32_p, c_f64_p]
-    lib.wbcqp_stabilize_zmp.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.POINTER(CZmpDistributor), C.c_int, C.POINTER(CStabInputs), C.c_void_p,
-                                        C.POINTER(CStabOutputs), C.c_void_p, C.c_void_p]
-    lib.wbcqp_stabilize_zmp_host.argtypes = [C.c_void_p, C.POINTER(CStabilizer), C.POINTER(CZmpDistributor), C.c_int, C.POINTER(CStabInputs), C.c_void_p,
-                                             C.POINTER(CStabOutputs), C.c_void_p]
-    _lib = lib
-    return lib
+    _lib = declare(C.CDLL(path, mode=C.RTLD_GLOBAL))
+    return _lib
 
 
 class ProgramBuffers:
@@ -389,26 +435,35 @@ def check_program(prog, batch: int, n_slots: int = 0, offsets=None) -> None:
     """wbcqp_check_program: validates a reference program on the host -- no GPU needed.  Raises WbcqpError with the library's message otherwise."""
     lib = load_library()
     pb = ProgramBuffers(prog, np.zeros(batch, np.int32) if offsets is None else offsets)
-    rc = lib.wbcqp_check_program(C.byref(pb.c), int(batch), int(n_slots))
-    if rc != WBCQP_OK:
-        raise WbcqpError(rc, (lib.wbcqp_last_error(None) or b"").decode())
+    _check(lib, lib.wbcqp_check_program(C.byref(pb.c), int(batch), int(n_slots)))
 
 
-class ModelBuffers:
+class _KeptArrays:
+    """The arrays a host-side C struct points into, kept alive with it; an empty one is passed as one zero (never a NULL)."""
+
+    def __init__(self):
+        self._keep = []
+
+    def _kept(self, a, dtype, ctype):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        if a.size == 0:
+            a = np.zeros(1, dtype=dtype)
+        self._keep.append(a)
+        return a.ctypes.data_as(ctype)
+
+    def ip(self, a):
+        return self._kept(a, np.int32, c_i32_p)
+
+    def dp(self, a):
+        return self._kept(a, np.float64, c_f64_p)
+
+
+class ModelBuffers(_KeptArrays):
     """Host-side wbcqp_model + wbcqp_taskmap built from a `model.Model` and a `model.TaskMap`; keeps the arrays alive."""
 
     def __init__(self, model, tm):
-        self._keep = []
-
-        def keep(a, dtype):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if a.size == 0:
-                a = np.zeros(1, dtype=dtype)
-            self._keep.append(a)
-            return a
-
-        ip = lambda a: keep(a, np.int32).ctypes.data_as(c_i32_p)
-        dp = lambda a: keep(a, np.float64).ctypes.data_as(c_f64_p)
+        super().__init__()
+        ip, dp = self.ip, self.dp
         m = CModel()
         m.nbody, m.floating_base = model.nbody, int(model.floating_base)
         m.parent, m.jtype = ip(model.parent), ip(model.jtype)
@@ -436,25 +491,12 @@ class ModelBuffers:
         self.model, self.taskmap = m, k
 
 
-class StructureBuffers:
+class StructureBuffers(_KeptArrays):
     """Host-side wbcqp_structure built from a `Structure`; keeps the numpy arrays alive."""
 
     def __init__(self, st: Structure):
-        self._keep = []
-
-        def keep(a, dtype):
-            a = np.ascontiguousarray(a, dtype=dtype)
-            if a.size == 0:
-                a = np.zeros(1, dtype=dtype)
-            self._keep.append(a)
-            return a
-
-        def ip(a):
-            return keep(a, np.int32).ctypes.data_as(c_i32_p)
-
-        def dp(a):
-            return keep(a, np.float64).ctypes.data_as(c_f64_p)
-
+        super().__init__()
+        ip, dp = self.ip, self.dp
         B, lb, ub = st.friction()
         s = CStructure()
         s.nv, s.na, s.nc = st.nv, st.na, st.nc
@@ -488,9 +530,7 @@ def layout_of(st: Structure) -> Dict[str, int]:
     lib = load_library()
     sb = StructureBuffers(st)
     L = CLayout()
-    rc = lib.wbcqp_layout_of(C.byref(sb.c), C.byref(L))
-    if rc != WBCQP_OK:
-        raise WbcqpError(rc, (lib.wbcqp_last_error(None) or b"").decode())
+    _check(lib, lib.wbcqp_layout_of(C.byref(sb.c), C.byref(L)))
     return {k: getattr(L, k) for k, _ in CLayout._fields_}
 
 
@@ -500,9 +540,7 @@ def check_model(st: Structure, model, tm) -> int:
     lib = load_library()
     sb, mb = StructureBuffers(st), ModelBuffers(model, tm)
     lds = C.c_int32(0)
-    rc = lib.wbcqp_check_model(C.byref(sb.c), C.byref(mb.model), C.byref(mb.taskmap), C.byref(lds))
-    if rc != WBCQP_OK:
-        raise WbcqpError(rc, (lib.wbcqp_last_error(None) or b"").decode())
+    _check(lib, lib.wbcqp_check_model(C.byref(sb.c), C.byref(mb.model), C.byref(mb.taskmap), C.byref(lds)))
     return int(lds.value)
 
 
@@ -531,16 +569,15 @@ class Handle:
         self.device = device
         self._h = C.c_void_p()
         self._structs: Dict[int, Structure] = {}
+        self._lengths: Dict[int, Dict[str, int]] = {}  # slot -> Structure.field_lengths() of what set_structure uploaded
         # slot -> the structure's companions the library cannot be asked for: "model" (model, task map), the numbers of "observed" frames, "spheres", "wrench" frames
         self._companions: Dict[int, dict] = {}
         desc = CDesc(device, dtype, flags)
-        rc = self.lib.wbcqp_create(C.byref(desc), C.byref(self._h))
-        if rc != WBCQP_OK:
-            raise WbcqpError(rc, (self.lib.wbcqp_last_error(None) or b"").decode())
+        _check(self.lib, self.lib.wbcqp_create(C.byref(desc), C.byref(self._h)))
 
     def _check(self, rc: int):
         if rc != WBCQP_OK:
-            raise WbcqpError(rc, (self.lib.wbcqp_last_error(self._h) or b"").decode())
+            _check(self.lib, rc, self._h)
 
     def close(self):
         if self._h:
@@ -556,7 +593,7 @@ class Handle:
     def set_structure(self, slot: int, st: Structure):
         sb = StructureBuffers(st)
         self._check(self.lib.wbcqp_set_structure(self._h, slot, C.byref(sb.c)))
-        self._structs[slot] = st
+        self._structs[slot], self._lengths[slot] = st, st.field_lengths()
         self._companions_of(slot, reset=True)
 
     def _companions_of(self, slot: int, reset: bool = False) -> dict:
@@ -565,19 +602,28 @@ class Handle:
             self._companions[slot] = {"model": None, "observed": 0, "spheres": 0, "wrench": 0, "jacobian": 0}
         return self._companions[slot]
 
+    def _host(self, *arrays):
+        """Host arrays as the library reads them: contiguous, of the handle's dtype; None stays None."""
+        return [None if a is None else np.ascontiguousarray(a, dtype=self.np_dtype) for a in arrays]
+
+    def _nv(self, slot: int) -> int:
+        """nv of the slot's model: what the _host forms of the model queries size their outputs by."""
+        return self._companions_of(slot)["model"][0].nv
+
     # ---- device-pointer path (torch tensors are only carriers of device memory) ----
+    def _rows(self, slot: int, batch: int, rows, names=FIELDS) -> CInputs:
+        """wbcqp_inputs from device tensors: those of `names` that are given and that the slot's structure has; each checked against its length."""
+        L = self._lengths[slot]
+        ptrs = {}
+        for k in names:
+            t = rows.get(k)
+            if L[k] and t is not None:
+                assert t.is_cuda and t.is_contiguous() and t.numel() == batch * L[k], (k, tuple(t.shape), batch, L[k])
+                ptrs[k] = t.data_ptr()
+        return c_inputs(ptrs)
+
     def _pack(self, slot: int, batch: int, inputs, outputs):
-        st = self._structs[slot]
-        L = st.field_lengths()
-        cin = CInputs()
-        for k in FIELDS:
-            t = inputs.get(k)
-            if L[k] == 0 or t is None:
-                setattr(cin, k, None)
-                continue
-            assert t.is_cuda and t.is_contiguous() and t.numel() == batch * L[k], (k, tuple(t.shape), batch, L[k])
-            setattr(cin, k, t.data_ptr())
-        return cin, self._outs(outputs)
+        return self._rows(slot, batch, inputs), self._outs(outputs)
 
     def solve_batch(self, slot: int, batch: int, inputs: Dict[str, "object"], outputs: Dict[str, "object"], stream: int = 0):
         cin, cout = self._pack(slot, batch, inputs, outputs)
@@ -594,7 +640,7 @@ class Handle:
     def integrate(self, batch: int, nv: int, floating_base: bool, dt: float, q, dq, x, ldx: int, status, q_next, v_next,
                   q_solver=None, stream: int = 0):
         """State integration after the path (controller.cpp:250-272) on device tensors (anything with .data_ptr())."""
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        ptr = dev_ptr_given
         self._check(self.lib.wbcqp_integrate(self._h, batch, nv, 1 if floating_base else 0, float(dt), ptr(q), ptr(dq), ptr(x), ldx,
                                              ptr(status), ptr(q_next), ptr(v_next), ptr(q_solver), C.c_void_p(stream)))
 
@@ -625,35 +671,30 @@ class Handle:
     def observe(self, slot: int, batch: int, q, v=None, com=None, vcom=None, placement=None, velocity=None, stream: int = 0, acom=None):
         """CoM and frame poses of `batch` states on device tensors (wbcqp_observe): q [batch, nq], v [batch, nv] (None when neither vcom, acom nor
         velocity is asked for); outputs, each optional: com / vcom / acom [batch, 3], placement [batch, n_frames, 12], velocity [batch, n_frames, 6]."""
-        out = CObservables(self._ptr(com), self._ptr(vcom), self._ptr(placement), self._ptr(velocity))
+        out = CObservables(dev_ptr(com), dev_ptr(vcom), dev_ptr(placement), dev_ptr(velocity))
         if acom is not None:  # (wbcqp_observe_acom: the same launch with one more output)
-            self._check(self.lib.wbcqp_observe_acom(self._h, slot, int(batch), self._ptr(q), self._ptr(v), C.byref(out), self._ptr(acom), C.c_void_p(stream)))
+            self._check(self.lib.wbcqp_observe_acom(self._h, slot, int(batch), dev_ptr(q), dev_ptr(v), C.byref(out), dev_ptr(acom), C.c_void_p(stream)))
             return
-        self._check(self.lib.wbcqp_observe(self._h, slot, int(batch), self._ptr(q), self._ptr(v), C.byref(out), C.c_void_p(stream)))
+        self._check(self.lib.wbcqp_observe(self._h, slot, int(batch), dev_ptr(q), dev_ptr(v), C.byref(out), C.c_void_p(stream)))
 
     def observe_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, acom: bool = False) -> Dict[str, np.ndarray]:
         """wbcqp_observe_host: dict(com [B, 3], placement [B, n_frames, 12]) and, when v is given, vcom [B, 3] and velocity [B, n_frames, 6]
         (placement / velocity only when frames are selected); acom=True (needs v) adds acom [B, 3].  The library cannot be asked how many frames a slot observes, so the outputs are
         sized from what THIS Handle's set_observed_frames last selected on the slot: a selection made any other way (the raw library, another
         wrapper of the same handle) is not seen here -- such callers size their own buffers and use observe()."""
-        q = np.ascontiguousarray(q, dtype=self.np_dtype)
-        B = q.shape[0]
+        q, v = self._host(q, v)
+        B, f = q.shape[0], self.np_dtype
         nf = self._companions_of(slot)["observed"]
-        res = {"com": np.zeros((B, 3), self.np_dtype)}
-        if nf:
-            res["placement"] = np.zeros((B, nf, 12), self.np_dtype)
+        names = ["com", "placement"] if nf else ["com"]
         if v is not None:
-            v = np.ascontiguousarray(v, dtype=self.np_dtype)
-            res["vcom"] = np.zeros((B, 3), self.np_dtype)
-            if nf:
-                res["velocity"] = np.zeros((B, nf, 6), self.np_dtype)
-        out = CObservables(*[res[k].ctypes.data if k in res else None for k in OBSERVABLES])
+            names += ["vcom", "velocity"] if nf else ["vcom"]
+        res, ptrs = host_outputs({"com": ((B, 3), f), "vcom": ((B, 3), f), "placement": ((B, nf, 12), f), "velocity": ((B, nf, 6), f)}, names)
+        out = CObservables(*ptrs)
         if acom:
-            res["acom"] = np.zeros((B, 3), self.np_dtype)
-            self._check(self.lib.wbcqp_observe_acom_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out),
-                                                         res["acom"].ctypes.data))
+            res["acom"] = np.zeros((B, 3), f)
+            self._check(self.lib.wbcqp_observe_acom_host(self._h, slot, B, q.ctypes.data, host_ptr(v), C.byref(out), res["acom"].ctypes.data))
             return res
-        self._check(self.lib.wbcqp_observe_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, C.byref(out)))
+        self._check(self.lib.wbcqp_observe_host(self._h, slot, B, q.ctypes.data, host_ptr(v), C.byref(out)))
         return res
 
     def set_wrench_frames(self, slot: int, frames: Sequence[int]):
@@ -667,38 +708,32 @@ class Handle:
         wrench [batch, n_frames, 6] or None: linear, angular in the own axes of the frames of set_wrench_frames."""
         if a is not None and lda == 0:
             lda = int(a.shape[-1])
-        ptr = lambda t: t.data_ptr() if t is not None else None  # (an empty tensor stays a given one: the library says what is wrong with it)
+        ptr = dev_ptr_given
         self._check(self.lib.wbcqp_inverse_dynamics(self._h, slot, int(batch), ptr(q), ptr(v), ptr(a), int(lda), ptr(wrench), ptr(tau),
                                                     C.c_void_p(stream)))
 
     def inverse_dynamics_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, a: Optional[np.ndarray] = None,
                               wrench: Optional[np.ndarray] = None) -> np.ndarray:
         """wbcqp_inverse_dynamics_host: tau [B, nv].  a [B, lda] with lda >= nv: its first nv columns are the accelerations (a tick's x as it is)."""
-        q = np.ascontiguousarray(q, dtype=self.np_dtype)
+        q, v, a, wrench = self._host(q, v, a, wrench)
         B = q.shape[0]
-        nv = self._companions_of(slot)["model"][0].nv
-        v, a, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, a, wrench))
-        tau = np.zeros((B, nv), self.np_dtype)
-        dat = lambda t: t.ctypes.data if t is not None else None
+        tau = np.zeros((B, self._nv(slot)), self.np_dtype)
+        dat = host_ptr
         self._check(self.lib.wbcqp_inverse_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(a), int(a.shape[-1]) if a is not None else 0,
                                                          dat(wrench), tau.ctypes.data))
         return tau
 
     def mass_matrix(self, slot: int, batch: int, q, M, stream: int = 0):
         """M(q) of `batch` states on device tensors (wbcqp_mass_matrix): q [batch, nq], M [batch, nv, nv], both triangles."""
-        self._check(self.lib.wbcqp_mass_matrix(self._h, slot, int(batch), self._dptr(q), self._dptr(M), C.c_void_p(stream)))
+        self._check(self.lib.wbcqp_mass_matrix(self._h, slot, int(batch), dev_ptr_given(q), dev_ptr_given(M), C.c_void_p(stream)))
 
     def mass_matrix_host(self, slot: int, q: np.ndarray) -> np.ndarray:
         """wbcqp_mass_matrix_host: M [B, nv, nv]."""
         q = np.ascontiguousarray(q, dtype=self.np_dtype)
-        B, nv = q.shape[0], self._companions_of(slot)["model"][0].nv
+        B, nv = q.shape[0], self._nv(slot)
         M = np.zeros((B, nv, nv), self.np_dtype)
         self._check(self.lib.wbcqp_mass_matrix_host(self._h, slot, B, q.ctypes.data, M.ctypes.data))
         return M
-
-    @staticmethod
-    def _dptr(t):
-        return t.data_ptr() if t is not None else None  # (an empty tensor stays a given one: the library says what is wrong with it)
 
     @staticmethod
     def _damping(damping):
@@ -715,17 +750,17 @@ class Handle:
         if tau is not None and ldt == 0:
             ldt = int(tau.shape[-1])
         keep, dptr = self._damping(damping)  # (keep: holds the converted array alive until the call has copied it)
-        self._check(self.lib.wbcqp_forward_dynamics(self._h, slot, int(batch), self._dptr(q), self._dptr(v), self._dptr(tau), int(ldt), self._dptr(wrench),
-                                                    dptr, self._dptr(a), self._dptr(info), C.c_void_p(stream)))
+        ptr = dev_ptr_given
+        self._check(self.lib.wbcqp_forward_dynamics(self._h, slot, int(batch), ptr(q), ptr(v), ptr(tau), int(ldt), ptr(wrench), dptr, ptr(a), ptr(info),
+                                                    C.c_void_p(stream)))
 
     def forward_dynamics_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, tau: Optional[np.ndarray] = None,
                               wrench: Optional[np.ndarray] = None, damping=None):
         """wbcqp_forward_dynamics_host: (a [B, nv], info [B]).  tau [B, ldt] with ldt >= nv: its first nv columns are the torques."""
-        q = np.ascontiguousarray(q, dtype=self.np_dtype)
-        B, nv = q.shape[0], self._companions_of(slot)["model"][0].nv
-        v, tau, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, tau, wrench))
+        q, v, tau, wrench = self._host(q, v, tau, wrench)
+        B, nv = q.shape[0], self._nv(slot)
         a, info = np.zeros((B, nv), self.np_dtype), np.zeros(B, np.int32)
-        dat = lambda t: t.ctypes.data if t is not None else None
+        dat = host_ptr
         keep, dptr = self._damping(damping)  # (keep: holds the converted array alive until the call has copied it)
         self._check(self.lib.wbcqp_forward_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(tau), int(tau.shape[-1]) if tau is not None else 0,
                                                          dat(wrench), dptr, a.ctypes.data, info.ctypes.data))
@@ -739,19 +774,20 @@ class Handle:
         if ldtarget == 0:
             ldtarget = int(target.shape[-1])
         c = CSpd(*[float(x) for x in law])
-        self._check(self.lib.wbcqp_spd_commands(self._h, slot, int(batch), C.byref(c), self._dptr(q), self._dptr(v), self._dptr(target), int(ldtarget),
-                                                self._dptr(wrench), self._dptr(commands), self._dptr(qddot), self._dptr(info), C.c_void_p(stream)))
+        ptr = dev_ptr_given
+        self._check(self.lib.wbcqp_spd_commands(self._h, slot, int(batch), C.byref(c), ptr(q), ptr(v), ptr(target), int(ldtarget), ptr(wrench),
+                                                ptr(commands), ptr(qddot), ptr(info), C.c_void_p(stream)))
 
     def spd_commands_host(self, slot: int, law, q: np.ndarray, v: Optional[np.ndarray], target: np.ndarray, wrench: Optional[np.ndarray] = None):
         """wbcqp_spd_commands_host: dict(commands [B, nv], qddot [B, nv], info [B]).  target [B, ldtarget] with ldtarget >= na."""
-        q = np.ascontiguousarray(q, dtype=self.np_dtype)
-        B, nv = q.shape[0], self._companions_of(slot)["model"][0].nv
-        v, target, wrench = (np.ascontiguousarray(t, dtype=self.np_dtype) if t is not None else None for t in (v, target, wrench))
-        res = {"commands": np.zeros((B, nv), self.np_dtype), "qddot": np.zeros((B, nv), self.np_dtype), "info": np.zeros(B, np.int32)}
-        dat = lambda t: t.ctypes.data if t is not None else None
+        q, v, target, wrench = self._host(q, v, target, wrench)
+        B, nv = q.shape[0], self._nv(slot)
+        spec = {"commands": ((B, nv), self.np_dtype), "qddot": ((B, nv), self.np_dtype), "info": ((B,), np.int32)}  # (the call's last three arguments)
+        res, ptrs = host_outputs(spec, spec)
+        dat = host_ptr
         c = CSpd(*[float(x) for x in law])
         self._check(self.lib.wbcqp_spd_commands_host(self._h, slot, B, C.byref(c), q.ctypes.data, dat(v), dat(target), int(target.shape[-1]), dat(wrench),
-                                                     res["commands"].ctypes.data, res["qddot"].ctypes.data, res["info"].ctypes.data))
+                                                     *ptrs))
         return res
 
     def set_jacobian_frames(self, slot: int, frames: Sequence[int]):
@@ -764,8 +800,8 @@ class Handle:
         """Frame Jacobians, the CoM Jacobian and the centroidal momentum matrix of `batch` states on device tensors (wbcqp_jacobians): q [batch, nq],
         v [batch, nv] (None when neither drift nor dAgv is asked for); outputs, each optional: J [batch, n_frames, 6, nv], Jcom [batch, 3, nv],
         Ag [batch, 6, nv], drift [batch, n_frames, 6], dAgv [batch, 6]."""
-        out = CJacobianOutputs(*[self._dptr(t) for t in (J, Jcom, Ag, drift, dAgv)])
-        self._check(self.lib.wbcqp_jacobians(self._h, slot, int(batch), self._dptr(q), self._dptr(v), int(reference_frame), C.byref(out),
+        out = CJacobianOutputs(*[dev_ptr_given(t) for t in (J, Jcom, Ag, drift, dAgv)])
+        self._check(self.lib.wbcqp_jacobians(self._h, slot, int(batch), dev_ptr_given(q), dev_ptr_given(v), int(reference_frame), C.byref(out),
                                              C.c_void_p(stream)))
 
     def jacobians_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, reference_frame: int = RF_LOCAL,
@@ -773,18 +809,15 @@ class Handle:
         """wbcqp_jacobians_host: a dict of the outputs named in `which` (of JACOBIAN_OUTPUTS).  which None: everything the arguments admit -- Jcom
         and Ag; J when frames are selected; with v, dAgv and (frames selected, not RF_WORLD) drift.  J and drift are sized from what THIS Handle's
         set_jacobian_frames last selected on the slot (see observe_host)."""
-        q = np.ascontiguousarray(q, dtype=self.np_dtype)
-        B, nv, nf = q.shape[0], self._companions_of(slot)["model"][0].nv, self._companions_of(slot)["jacobian"]
-        if v is not None:
-            v = np.ascontiguousarray(v, dtype=self.np_dtype)
+        q, v = self._host(q, v)
+        B, nv, nf, f = q.shape[0], self._nv(slot), self._companions_of(slot)["jacobian"], self.np_dtype
         if which is None:
             which = ["Jcom", "Ag"] + (["J"] if nf else []) + (["dAgv"] if v is not None else []) + (
                 ["drift"] if v is not None and nf and reference_frame != RF_WORLD else [])
-        shape = {"J": (B, nf, 6, nv), "Jcom": (B, 3, nv), "Ag": (B, 6, nv), "drift": (B, nf, 6), "dAgv": (B, 6)}
-        res = {k: np.zeros(shape[k], self.np_dtype) for k in which}
-        out = CJacobianOutputs(*[res[k].ctypes.data if k in res else None for k in JACOBIAN_OUTPUTS])
-        self._check(self.lib.wbcqp_jacobians_host(self._h, slot, B, q.ctypes.data, v.ctypes.data if v is not None else None, int(reference_frame),
-                                                  C.byref(out)))
+        res, ptrs = host_outputs({"J": ((B, nf, 6, nv), f), "Jcom": ((B, 3, nv), f), "Ag": ((B, 6, nv), f), "drift": ((B, nf, 6), f), "dAgv": ((B, 6), f)},
+                                 which)
+        out = CJacobianOutputs(*ptrs)
+        self._check(self.lib.wbcqp_jacobians_host(self._h, slot, B, q.ctypes.data, host_ptr(v), int(reference_frame), C.byref(out)))
         return res
 
     def detect_torque_collisions(self, monitor, batch: int, n_ticks: int, tau_model, ldt: int, tau_sensor, state=None, detected=None, invalid=None,
@@ -795,7 +828,7 @@ class Handle:
         in and out, or None; outputs, each optional: detected [n_ticks, batch] int32, invalid [n_ticks, batch] int64 (bit j: joint j),
         discrepancy / filtered [n_ticks, batch, n_joints] (the handle's dtype), first_tick / n_detected [batch] int32."""
         mb = TorqueMonitorBuffers(monitor)
-        ptr = lambda t: (t if isinstance(t, int) else t.data_ptr()) if t is not None else None
+        ptr = dev_ptr_given
         out = CTorqueChecks(ptr(detected), ptr(invalid), ptr(discrepancy), ptr(filtered), ptr(first_tick), ptr(n_detected))
         self._check(self.lib.wbcqp_detect_torque_collisions(self._h, C.byref(mb.c), int(batch), int(n_ticks), ptr(tau_model), int(ldt), ptr(tau_sensor),
                                                             ptr(state), C.byref(out), C.c_void_p(stream)))
@@ -804,21 +837,25 @@ class Handle:
                                       outputs: Sequence[str] = TORQUE_CHECKS) -> Dict[str, np.ndarray]:
         """wbcqp_detect_torque_collisions_host: tau_model [T, B, ldt], tau_sensor [T, B, n_joints]; state: a contiguous uint8 array
         [B, state_bytes], updated in place, or None.  Returns the outputs named in `outputs` as numpy arrays (invalid as uint64)."""
-        tau_model = np.ascontiguousarray(tau_model, dtype=self.np_dtype)
-        tau_sensor = np.ascontiguousarray(tau_sensor, dtype=self.np_dtype)
+        tau_model, tau_sensor = self._host(tau_model, tau_sensor)
         T, B, n = tau_sensor.shape
         assert tau_model.shape[:2] == (T, B), (tau_model.shape, tau_sensor.shape)
-        if state is not None:
-            assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"], "state: a contiguous uint8 array [B, state_bytes]"
-        shapes = {"detected": ((T, B), np.int32), "invalid": ((T, B), np.uint64), "discrepancy": ((T, B, n), self.np_dtype),
-                  "filtered": ((T, B, n), self.np_dtype), "first_tick": ((B,), np.int32), "n_detected": ((B,), np.int32)}
-        res = {k: np.zeros(*shapes[k]) for k in outputs}
+        _check_state(state)
+        res, ptrs = host_outputs({"detected": ((T, B), np.int32), "invalid": ((T, B), np.uint64), "discrepancy": ((T, B, n), self.np_dtype),
+                                  "filtered": ((T, B, n), self.np_dtype), "first_tick": ((B,), np.int32), "n_detected": ((B,), np.int32)}, outputs)
         mb = TorqueMonitorBuffers(monitor)
-        out = CTorqueChecks(*[res[k].ctypes.data if k in res else None for k in TORQUE_CHECKS])
+        out = CTorqueChecks(*ptrs)
         self._check(self.lib.wbcqp_detect_torque_collisions_host(self._h, C.byref(mb.c), B, T, tau_model.ctypes.data, int(tau_model.shape[2]),
-                                                                 tau_sensor.ctypes.data, state.ctypes.data if state is not None else None,
-                                                                 C.byref(out)))
+                                                                 tau_sensor.ctypes.data, host_ptr(state), C.byref(out)))
         return res
+
+    @staticmethod
+    def _stab_io(stab, ref, wrench, com, acom, placement, ldp, x_prev, ldx, ref_out, flags, cop):
+        """(wbcqp_stabilizer, wbcqp_stab_inputs, wbcqp_stab_outputs) of stabilize and stabilize_zmp, from device tensors or device addresses."""
+        ptr = dev_ptr_given
+        width = lambda t, ld: int(ld) if ld or t is None or isinstance(t, int) else int(t.numel() // max(int(t.shape[0]), 1))  # noqa: E731
+        cin = CStabInputs(ptr(ref), ptr(wrench), ptr(com), ptr(acom), ptr(placement), width(placement, ldp), ptr(x_prev), width(x_prev, ldx))
+        return c_stabilizer(stab), cin, CStabOutputs(ptr(ref_out), ptr(flags), ptr(cop))
 
     def stabilize(self, stab, batch: int, ref, wrench, com, acom, placement, ldp: int = 0, x_prev=None, ldx: int = 0, state=None, ref_out=None,
                   flags=None, cop=None, stream: int = 0):
@@ -826,65 +863,46 @@ class Handle:
         com / acom [batch, 3]; placement: row i starts i * ldp elements after its data pointer (ldp = 0: its row length), as observe() writes it;
         x_prev: the previous tick's x, rows ldx apart (0: its row length), or None; state: uint8 / float64 tensor of batch * state_bytes bytes, in
         and out, or None; outputs, each optional: ref_out [batch, nref] (may be ref), flags [batch] int32, cop [batch, 3, 2]."""
-        ptr = lambda t: (t if isinstance(t, int) else t.data_ptr()) if t is not None else None  # noqa: E731
-        width = lambda t, ld: int(ld) if ld or t is None or isinstance(t, int) else int(t.numel() // max(int(t.shape[0]), 1))  # noqa: E731
-        cs = c_stabilizer(stab)
-        cin = CStabInputs(ptr(ref), ptr(wrench), ptr(com), ptr(acom), ptr(placement), width(placement, ldp), ptr(x_prev), width(x_prev, ldx))
-        out = CStabOutputs(ptr(ref_out), ptr(flags), ptr(cop))
-        self._check(self.lib.wbcqp_stabilize(self._h, C.byref(cs), int(batch), C.byref(cin), ptr(state), C.byref(out), C.c_void_p(stream)))
+        cs, cin, out = self._stab_io(stab, ref, wrench, com, acom, placement, ldp, x_prev, ldx, ref_out, flags, cop)
+        self._check(self.lib.wbcqp_stabilize(self._h, C.byref(cs), int(batch), C.byref(cin), dev_ptr_given(state), C.byref(out), C.c_void_p(stream)))
 
     def stabilize_zmp(self, stab, zmp, batch: int, ref, wrench, com, acom, placement, ldp: int = 0, x_prev=None, ldx: int = 0, state=None,
                       ref_out=None, flags=None, cop=None, alpha=None, stream: int = 0):
         """stabilize with the ZMP force distributor (wbcqp_stabilize_zmp).  zmp: a stabilizer.ZmpDistributor, or None (then this IS stabilize);
         alpha [batch, 2]: one more optional output."""
-        ptr = lambda t: (t if isinstance(t, int) else t.data_ptr()) if t is not None else None  # noqa: E731
-        width = lambda t, ld: int(ld) if ld or t is None or isinstance(t, int) else int(t.numel() // max(int(t.shape[0]), 1))  # noqa: E731
-        cs = c_stabilizer(stab)
-        cz = c_zmp_distributor(zmp) if zmp is not None else None
-        cin = CStabInputs(ptr(ref), ptr(wrench), ptr(com), ptr(acom), ptr(placement), width(placement, ldp), ptr(x_prev), width(x_prev, ldx))
-        out = CStabOutputs(ptr(ref_out), ptr(flags), ptr(cop))
-        self._check(self.lib.wbcqp_stabilize_zmp(self._h, C.byref(cs), C.byref(cz) if cz is not None else None, int(batch), C.byref(cin), ptr(state),
-                                                 C.byref(out), ptr(alpha), C.c_void_p(stream)))
+        cs, cin, out = self._stab_io(stab, ref, wrench, com, acom, placement, ldp, x_prev, ldx, ref_out, flags, cop)
+        cz = C.byref(c_zmp_distributor(zmp)) if zmp is not None else None
+        self._check(self.lib.wbcqp_stabilize_zmp(self._h, C.byref(cs), cz, int(batch), C.byref(cin), dev_ptr_given(state), C.byref(out),
+                                                 dev_ptr_given(alpha), C.c_void_p(stream)))
+
+    def _stabilize_host(self, export, distributor: tuple, stab, inputs, state, names, outputs):
+        """The body of stabilize_host and stabilize_zmp_host.  export: the symbol itself; distributor: the arguments it takes between the stabiliser
+        and the batch (none, or the wbcqp_zmp_distributor); names: the outputs it has."""
+        a = dict(zip(STAB_INPUTS, self._host(*[inputs.get(k) for k in STAB_INPUTS])))
+        B = a["ref"].shape[0]
+        a = {k: (t.reshape(B, -1) if t is not None else None) for k, t in a.items()}
+        _check_state(state)
+        dat = host_ptr
+        cin = CStabInputs(dat(a["ref"]), dat(a["wrench"]), dat(a["com"]), dat(a["acom"]), dat(a["placement"]), int(a["placement"].shape[1]),
+                          dat(a["x_prev"]), int(a["x_prev"].shape[1]) if a["x_prev"] is not None else 0)
+        shape = {"ref_out": ((B, int(stab.nref)), self.np_dtype), "flags": ((B,), np.int32), "cop": ((B, 3, 2), self.np_dtype),
+                 "alpha": ((B, 2), self.np_dtype)}
+        res, ptrs = host_outputs({k: shape[k] for k in names}, outputs)
+        cs, out = c_stabilizer(stab), CStabOutputs(*ptrs[:3])
+        self._check(export(self._h, C.byref(cs), *distributor, B, C.byref(cin), host_ptr(state), C.byref(out), *ptrs[3:]))
+        return res
 
     def stabilize_zmp_host(self, stab, zmp, inputs: Dict[str, np.ndarray], state: Optional[np.ndarray] = None,
                            outputs: Sequence[str] = STAB_OUTPUTS + ("alpha",)) -> Dict[str, np.ndarray]:
         """wbcqp_stabilize_zmp_host: stabilize_host with the distributor (zmp None: stabilize_host's bits); `alpha` [B, 2] is one more output."""
-        a = {k: (np.ascontiguousarray(inputs[k], dtype=self.np_dtype) if inputs.get(k) is not None else None) for k in STAB_INPUTS}
-        B = a["ref"].shape[0]
-        a = {k: (t.reshape(B, -1) if t is not None else None) for k, t in a.items()}
-        if state is not None:
-            assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"], "state: a contiguous uint8 array [B, state_bytes]"
-        shapes = {"ref_out": ((B, int(stab.nref)), self.np_dtype), "flags": ((B,), np.int32), "cop": ((B, 3, 2), self.np_dtype),
-                  "alpha": ((B, 2), self.np_dtype)}
-        res = {k: np.zeros(*shapes[k]) for k in outputs}
-        dat = lambda t: t.ctypes.data if t is not None else None  # noqa: E731
-        cs = c_stabilizer(stab)
-        cz = c_zmp_distributor(zmp) if zmp is not None else None
-        cin = CStabInputs(dat(a["ref"]), dat(a["wrench"]), dat(a["com"]), dat(a["acom"]), dat(a["placement"]), int(a["placement"].shape[1]),
-                          dat(a["x_prev"]), int(a["x_prev"].shape[1]) if a["x_prev"] is not None else 0)
-        out = CStabOutputs(*[res[k].ctypes.data if k in res else None for k in STAB_OUTPUTS])
-        self._check(self.lib.wbcqp_stabilize_zmp_host(self._h, C.byref(cs), C.byref(cz) if cz is not None else None, B, C.byref(cin), dat(state),
-                                                      C.byref(out), res["alpha"].ctypes.data if "alpha" in res else None))
-        return res
+        cz = C.byref(c_zmp_distributor(zmp)) if zmp is not None else None
+        return self._stabilize_host(self.lib.wbcqp_stabilize_zmp_host, (cz,), stab, inputs, state, STAB_OUTPUTS + ("alpha",), outputs)
 
     def stabilize_host(self, stab, inputs: Dict[str, np.ndarray], state: Optional[np.ndarray] = None,
                        outputs: Sequence[str] = STAB_OUTPUTS) -> Dict[str, np.ndarray]:
         """wbcqp_stabilize_host: inputs as stabilizer.step takes them (ref [B, nref], wrench [B, 12], com, acom [B, 3], placement [B, ldp], x_prev
         [B, ldx] or absent); state: a contiguous uint8 array [B, state_bytes], updated in place, or None.  Returns the outputs named in `outputs`."""
-        a = {k: (np.ascontiguousarray(inputs[k], dtype=self.np_dtype) if inputs.get(k) is not None else None) for k in STAB_INPUTS}
-        B = a["ref"].shape[0]
-        a = {k: (t.reshape(B, -1) if t is not None else None) for k, t in a.items()}
-        if state is not None:
-            assert state.dtype == np.uint8 and state.flags["C_CONTIGUOUS"], "state: a contiguous uint8 array [B, state_bytes]"
-        shapes = {"ref_out": ((B, int(stab.nref)), self.np_dtype), "flags": ((B,), np.int32), "cop": ((B, 3, 2), self.np_dtype)}
-        res = {k: np.zeros(*shapes[k]) for k in outputs}
-        dat = lambda t: t.ctypes.data if t is not None else None  # noqa: E731
-        cs = c_stabilizer(stab)
-        cin = CStabInputs(dat(a["ref"]), dat(a["wrench"]), dat(a["com"]), dat(a["acom"]), dat(a["placement"]), int(a["placement"].shape[1]),
-                          dat(a["x_prev"]), int(a["x_prev"].shape[1]) if a["x_prev"] is not None else 0)
-        out = CStabOutputs(*[res[k].ctypes.data if k in res else None for k in STAB_OUTPUTS])
-        self._check(self.lib.wbcqp_stabilize_host(self._h, C.byref(cs), B, C.byref(cin), dat(state), C.byref(out)))
-        return res
+        return self._stabilize_host(self.lib.wbcqp_stabilize_host, (), stab, inputs, state, STAB_OUTPUTS, outputs)
 
     def set_collision_spheres(self, slot: int, table):
         """The slot's sphere model (wbcqp_set_collision_spheres): a collision.SphereTable (collision.sphere_table builds one from the reference's
@@ -903,8 +921,8 @@ class Handle:
     def check_collisions(self, slot: int, batch: int, q, colliding=None, first_pair=None, n_pairs=None, clearance=None, centres=None, stream: int = 0):
         """Self-collision of `batch` states on device tensors (wbcqp_check_collisions): q [batch, nq]; outputs, each optional: colliding [batch],
         first_pair [batch, 2], n_pairs [batch] (int32), clearance [batch], centres [batch, n_spheres, 3] (the handle's dtype)."""
-        out = CCollisions(self._ptr(colliding), self._ptr(first_pair), self._ptr(n_pairs), self._ptr(clearance), self._ptr(centres))
-        self._check(self.lib.wbcqp_check_collisions(self._h, slot, int(batch), self._ptr(q), C.byref(out), C.c_void_p(stream)))
+        out = CCollisions(dev_ptr(colliding), dev_ptr(first_pair), dev_ptr(n_pairs), dev_ptr(clearance), dev_ptr(centres))
+        self._check(self.lib.wbcqp_check_collisions(self._h, slot, int(batch), dev_ptr(q), C.byref(out), C.c_void_p(stream)))
 
     def check_collisions_host(self, slot: int, q: np.ndarray) -> Dict[str, np.ndarray]:
         """wbcqp_check_collisions_host: the five outputs as numpy arrays.  Like observe_host, `centres` is sized from what THIS Handle's
@@ -912,40 +930,32 @@ class Handle:
         q = np.ascontiguousarray(q, dtype=self.np_dtype)
         B = q.shape[0]
         ns = self._companions_of(slot)["spheres"]
-        res = {"colliding": np.zeros(B, np.int32), "first_pair": np.zeros((B, 2), np.int32), "n_pairs": np.zeros(B, np.int32),
-               "clearance": np.zeros(B, self.np_dtype), "centres": np.zeros((B, ns, 3), self.np_dtype)}
-        out = CCollisions(*[res[k].ctypes.data if res[k].size else None for k in COLLISIONS])
+        res, ptrs = host_outputs({"colliding": ((B,), np.int32), "first_pair": ((B, 2), np.int32), "n_pairs": ((B,), np.int32),
+                                  "clearance": ((B,), self.np_dtype), "centres": ((B, ns, 3), self.np_dtype)}, COLLISIONS, null_empty=True)
+        out = CCollisions(*ptrs)
         self._check(self.lib.wbcqp_check_collisions_host(self._h, slot, B, q.ctypes.data, C.byref(out)))
         return res
 
     def problem_data(self, slot: int, batch: int, state: Dict[str, "object"], rows: Dict[str, "object"], stream: int = 0):
         """q, v, ref -> M, h, A, b1, Ac, bc, blb, bub on device tensors (wbcqp_problem_data)."""
-        st = self._structs[slot]
-        L = st.field_lengths()
-        cs = self._state(state)
-        cin = CInputs()
-        for k in FIELDS:
-            t = rows.get(k)
-            if k not in ROW_FIELDS or L[k] == 0 or t is None:
-                setattr(cin, k, None)
-                continue
-            assert t.is_cuda and t.is_contiguous() and t.numel() == batch * L[k], (k, tuple(t.shape), batch, L[k])
-            setattr(cin, k, t.data_ptr())
+        cs, cin = self._state(state), self._rows(slot, batch, rows, ROW_FIELDS)
         self._check(self.lib.wbcqp_problem_data(self._h, slot, batch, C.byref(cs), C.byref(cin), C.c_void_p(stream)))
 
+    def _host_rows(self, slot: int, batch: int):
+        """(name -> zero-filled [batch, L[name]] array, name -> its pointer) for the rows a _host call writes (ROW_FIELDS); a row the slot's
+        structure does not have is an array without columns and a NULL."""
+        L = self._lengths[slot]
+        rows, ptrs = host_outputs({k: ((batch, L[k]), self.np_dtype) for k in ROW_FIELDS}, ROW_FIELDS, null_empty=True)
+        return rows, dict(zip(ROW_FIELDS, ptrs))
+
     def problem_data_host(self, slot: int, q: np.ndarray, v: np.ndarray, ref: np.ndarray) -> Dict[str, np.ndarray]:
-        st = self._structs[slot]
-        L = st.field_lengths()
-        q, v, ref = (np.ascontiguousarray(a, dtype=self.np_dtype) for a in (q, v, ref))
+        q, v, ref = self._host(q, v, ref)
         batch = q.shape[0]
-        out = {k: np.zeros((batch, max(L[k], 1)), self.np_dtype) for k in ROW_FIELDS}
+        res, ptrs = self._host_rows(slot, batch)
         mom = np.zeros((batch, 6), self.np_dtype)
         cs = CState(q.ctypes.data, v.ctypes.data, ref.ctypes.data, mom.ctypes.data)
-        cin = CInputs()
-        for k in FIELDS:
-            setattr(cin, k, out[k].ctypes.data if k in ROW_FIELDS and L[k] else None)
+        cin = c_inputs(ptrs)
         self._check(self.lib.wbcqp_problem_data_host(self._h, slot, batch, C.byref(cs), C.byref(cin)))
-        res = {k: a[:, :L[k]] for k, a in out.items()}
         res["momentum"] = mom  # centroidal momentum Ag v: linear, then angular about the CoM (controller.cpp:245 keeps the last three)
         return res
 
@@ -954,7 +964,7 @@ class Handle:
         io = CTickIO()
         io.state = self._state(state, need_ref=True)
         io.rows, io.out = cin, cout
-        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver), float(dt)
+        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), dev_ptr(q_solver), float(dt)
         return io
 
     def tick(self, slot: int, batch: int, state, rows, out, q_next, v_next, dt: float, q_solver=None, stream: int = 0):
@@ -970,34 +980,35 @@ class Handle:
         limits["w"]  # (a call without weights is refused here, not in the library)
         self.rollout_traced(slot, batch, n_ticks, state, limits, out, q_next, v_next, dt, None, 1, q_solver, iters_sum, ticks_ok, stream)
 
-    @staticmethod
-    def _ptr(t):
-        return t.data_ptr() if t is not None and t.numel() else None
-
     def _mix(self, slots: Sequence[int], w: Sequence, tlb=None, tub=None):
         """wbcqp_mix: slots (one per contact set of one robot model), w[k] = device tensor [B, n_tasks of slots[k]] by instance (or None)."""
         slots_arr = np.ascontiguousarray(slots, dtype=np.int32)
-        w_arr = (C.c_void_p * max(len(slots_arr), 1))(*[self._ptr(t) for t in w])
-        mix = CMix(len(slots_arr), slots_arr.ctypes.data_as(c_i32_p), C.cast(w_arr, C.POINTER(C.c_void_p)), self._ptr(tlb), self._ptr(tub))
+        w_arr = (C.c_void_p * max(len(slots_arr), 1))(*[dev_ptr(t) for t in w])
+        mix = CMix(len(slots_arr), slots_arr.ctypes.data_as(c_i32_p), C.cast(w_arr, C.POINTER(C.c_void_p)), dev_ptr(tlb), dev_ptr(tub))
         return mix, (slots_arr, w_arr)  # (the second item keeps the arrays alive for the call)
 
-    def _outs(self, out) -> COutputs:
-        cout = COutputs()
-        for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask"):  # active_mask: int32 [batch, 8], in/out
-            setattr(cout, k, self._ptr(out.get(k)))
-        return cout
+    @staticmethod
+    def _outs(out, names=OUT_FIELDS) -> COutputs:
+        """wbcqp_outputs from device tensors; names: the leading fields to take.  One that is missing or not taken is NULL."""
+        return COutputs(*[dev_ptr(out.get(k)) for k in names])
 
     def _state(self, state, need_ref: bool = False) -> CState:
         """wbcqp_state from device tensors q, v (ref, momentum [batch, 6]: an output); need_ref: a state without ref is refused here."""
-        return CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr() if need_ref else self._ptr(state.get("ref")),
-                      self._ptr(state.get("momentum")))
+        return CState(state["q"].data_ptr(), state["v"].data_ptr(), state["ref"].data_ptr() if need_ref else dev_ptr(state.get("ref")),
+                      dev_ptr(state.get("momentum")))
 
-    def _rollout_io(self, state, out, q_next, v_next, dt: float, q_solver, iters_sum, ticks_ok, need_ref: bool = False) -> CRolloutIO:
+    def _rollout_io(self, state, out, q_next, v_next, dt: float, q_solver, iters_sum, ticks_ok, need_ref: bool = False, limits=None) -> CRolloutIO:
+        """limits: (slot, dict of tlb, tub, w) for a roll-out of one slot; a mixed one carries them in its wbcqp_mix."""
         io = CRolloutIO()
+        if limits is not None:
+            slot, lim = limits
+            if self._structs[slot].act_bounds:
+                io.tlb, io.tub = dev_ptr(lim.get("tlb")), dev_ptr(lim.get("tub"))
+            io.w = dev_ptr(lim.get("w"))
         io.state = self._state(state, need_ref)
         io.out = self._outs(out)
-        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver), float(dt)
-        io.iters_sum, io.ticks_ok = self._ptr(iters_sum), self._ptr(ticks_ok)
+        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), dev_ptr(q_solver), float(dt)
+        io.iters_sum, io.ticks_ok = dev_ptr(iters_sum), dev_ptr(ticks_ok)
         return io
 
     def tick_mixed(self, slots: Sequence[int], which, state, w: Sequence, out, q_next, v_next, dt: float, tlb=None, tub=None, q_solver=None,
@@ -1009,7 +1020,7 @@ class Handle:
         mix, keep = self._mix(slots, w, tlb, tub)
         io = CMixedIO()
         io.state, io.out = self._state(state), self._outs(out)
-        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), self._ptr(q_solver), float(dt)
+        io.q_next, io.v_next, io.q_solver, io.dt = q_next.data_ptr(), v_next.data_ptr(), dev_ptr(q_solver), float(dt)
         self._check(self.lib.wbcqp_tick_mixed(self._h, C.byref(mix), int(which.size), which.ctypes.data_as(c_i32_p), C.byref(io),
                                               C.c_void_p(stream)))
         del keep
@@ -1023,10 +1034,8 @@ class Handle:
     def task_costs(self, slot: int, batch: int, rows: Dict[str, "object"], x, tau, cost, stream: int = 0):
         """Per-task costs ||A_t x - b_t|| of a solved record (wbcqp_task_costs), device tensors: rows (A, b1, Acop read) as given to
         solve_batch, x [B, n], tau [B, na] (may be None without a torque task), cost [B, n_tasks] written."""
-        cin = CInputs()
-        for k in ("A", "b1", "Acop"):
-            setattr(cin, k, self._ptr(rows.get(k)))
-        self._check(self.lib.wbcqp_task_costs(self._h, slot, batch, C.byref(cin), self._ptr(x), self._ptr(tau), self._ptr(cost),
+        cin = c_inputs({k: dev_ptr(rows.get(k)) for k in ("A", "b1", "Acop")})
+        self._check(self.lib.wbcqp_task_costs(self._h, slot, batch, C.byref(cin), dev_ptr(x), dev_ptr(tau), dev_ptr(cost),
                                               C.c_void_p(stream)))
 
     @staticmethod
@@ -1037,7 +1046,7 @@ class Handle:
         ct = CTrace()
         ct.stride = int(stride)
         for k in TRACE_FIELDS:
-            setattr(ct, k, Handle._ptr(trace.get(k)))
+            setattr(ct, k, dev_ptr(trace.get(k)))
         return C.byref(ct)
 
     def rollout_traced(self, slot: int, batch: int, n_ticks: int, state, limits, out, q_next, v_next, dt: float, trace=None, stride: int = 1,
@@ -1045,11 +1054,7 @@ class Handle:
         """rollout() that also keeps every stride-th tick's results (wbcqp_rollout_traced).  trace: dict of device tensors, q [n_rec, B, nq],
         v [n_rec, B, nv], x [n_rec, B, n], tau [n_rec, B, na], status / iters [n_rec, B] int32, objective [n_rec, B], cost [n_rec, B, n_tasks]
         (n_rec = n_ticks // stride); a field left out is not recorded; trace=None is rollout()."""
-        st = self._structs[slot]
-        io = self._rollout_io(state, out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok, need_ref=True)
-        io.tlb = self._ptr(limits.get("tlb")) if st.act_bounds else None
-        io.tub = self._ptr(limits.get("tub")) if st.act_bounds else None
-        io.w = self._ptr(limits.get("w"))
+        io = self._rollout_io(state, out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok, need_ref=True, limits=(slot, limits))
         self._check(self.lib.wbcqp_rollout_traced(self._h, slot, batch, n_ticks, C.byref(io), self._trace(trace, stride), C.c_void_p(stream)))
 
     def rollout_mixed_traced(self, slots: Sequence[int], schedule, state, w: Sequence, out, q_next, v_next, dt: float, trace=None, stride: int = 1,
@@ -1070,20 +1075,16 @@ class Handle:
         pb = ProgramBuffers(prog, offsets, base)
         B = pb.offsets.size
         assert out.is_contiguous() and out.numel() == n_ticks * B * prog.nref, (tuple(out.shape), n_ticks, B, prog.nref)
-        self._check(self.lib.wbcqp_reference_samples(self._h, C.byref(pb.c), B, int(tick0), int(n_ticks), self._ptr(out), C.c_void_p(stream)))
+        self._check(self.lib.wbcqp_reference_samples(self._h, C.byref(pb.c), B, int(tick0), int(n_ticks), dev_ptr(out), C.c_void_p(stream)))
         return out
 
     def rollout_program(self, slot: int, batch: int, tick0: int, n_ticks: int, prog, base, offsets, state, limits, out, q_next, v_next, dt: float,
                         trace=None, stride: int = 1, q_solver=None, iters_sum=None, ticks_ok=None, stream: int = 0):
         """rollout_traced() with the references generated on the device from a reference program (wbcqp_rollout_program): state needs q and v
         only; call tick t plays behaviour tick tick0 + t - offsets[i] of instance i."""
-        st = self._structs[slot]
         pb = ProgramBuffers(prog, offsets, base)
         assert pb.offsets.size == batch, (pb.offsets.size, batch)
-        io = self._rollout_io(dict(state, ref=None), out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok)
-        io.tlb = self._ptr(limits.get("tlb")) if st.act_bounds else None
-        io.tub = self._ptr(limits.get("tub")) if st.act_bounds else None
-        io.w = self._ptr(limits.get("w"))
+        io = self._rollout_io(dict(state, ref=None), out, q_next, v_next, dt, q_solver, iters_sum, ticks_ok, limits=(slot, limits))
         self._check(self.lib.wbcqp_rollout_program(self._h, slot, batch, int(tick0), n_ticks, C.byref(io), C.byref(pb.c), self._trace(trace, stride),
                                                    C.c_void_p(stream)))
 
@@ -1099,39 +1100,36 @@ class Handle:
                                                          self._trace(trace, stride), C.c_void_p(stream)))
         del keep
 
+    def _host_outs(self, st: Structure, batch: int):
+        """(name -> array, wbcqp_outputs of their pointers) for a _host solve: zeros, status -99; the caller cuts tau to [:, :na] after the call."""
+        f = self.np_dtype
+        out, ptrs = host_outputs({"x": ((batch, st.n), f), "tau": ((batch, max(st.na, 1)), f), "status": ((batch,), np.int32),
+                                  "iters": ((batch,), np.int32), "objective": ((batch,), f), "n_active": ((batch,), np.int32),
+                                  "active_mask": ((batch, 8), np.uint32)}, OUT_FIELDS)  # (active_mask in/out: zeros = no warm-start hint)
+        out["status"][:] = -99
+        return out, COutputs(*ptrs)
+
     def tick_host(self, slot: int, q: np.ndarray, v: np.ndarray, ref: np.ndarray, tlb, tub, w, dt: float, want_rows: bool = False):
         """One whole tick with host arrays (wbcqp_tick_host): returns dict(x, tau, status, iters, objective, n_active, active_mask, q_next, v_next,
         q_solver, momentum[, rows])."""
         st = self._structs[slot]
-        L = st.field_lengths()
-        f = lambda a: np.ascontiguousarray(a, dtype=self.np_dtype)
-        q, v, ref, w = f(q), f(v), f(ref), f(w)
+        q, v, ref, w = self._host(q, v, ref, w)
         B = q.shape[0]
-        tlb, tub = (f(tlb), f(tub)) if L["tlb"] else (None, None)
-        out = dict(x=np.zeros((B, st.n), self.np_dtype), tau=np.zeros((B, max(st.na, 1)), self.np_dtype), status=np.full(B, -99, np.int32),
-                   iters=np.zeros(B, np.int32), q_next=np.zeros_like(q), v_next=np.zeros_like(v), q_solver=np.zeros_like(v))
-        rows = {k: np.zeros((B, max(L[k], 1)), self.np_dtype) for k in ROW_FIELDS} if want_rows else {}
+        rows, ptrs = self._host_rows(slot, B) if want_rows else ({}, {})
+        if self._lengths[slot]["tlb"]:
+            tlb, tub = self._host(tlb, tub)
+            ptrs.update(tlb=tlb.ctypes.data, tub=tub.ctypes.data)
+        ptrs["w"] = w.ctypes.data
         io = CTickIO()
-        out["momentum"] = np.zeros((B, 6), self.np_dtype)
+        out, io.out = self._host_outs(st, B)
+        out.update(q_next=np.zeros_like(q), v_next=np.zeros_like(v), q_solver=np.zeros_like(v), momentum=np.zeros((B, 6), self.np_dtype))
         io.state = CState(q.ctypes.data, v.ctypes.data, ref.ctypes.data, out["momentum"].ctypes.data)
-        cin = CInputs()
-        for k in FIELDS:
-            setattr(cin, k, None)
-        for k, a in rows.items():
-            if L[k]:
-                setattr(cin, k, a.ctypes.data)
-        if L["tlb"]:
-            cin.tlb, cin.tub = tlb.ctypes.data, tub.ctypes.data
-        cin.w = w.ctypes.data
-        io.rows = cin
-        out.update(objective=np.zeros(B, self.np_dtype), n_active=np.zeros(B, np.int32), active_mask=np.zeros((B, 8), np.uint32))
-        io.out = COutputs(out["x"].ctypes.data, out["tau"].ctypes.data, out["status"].ctypes.data, out["iters"].ctypes.data,
-                          out["objective"].ctypes.data, out["n_active"].ctypes.data, out["active_mask"].ctypes.data)
+        io.rows = c_inputs(ptrs)
         io.q_next, io.v_next, io.q_solver, io.dt = out["q_next"].ctypes.data, out["v_next"].ctypes.data, out["q_solver"].ctypes.data, float(dt)
         self._check(self.lib.wbcqp_tick_host(self._h, slot, B, C.byref(io)))
         out["tau"] = out["tau"][:, :st.na]
         if want_rows:
-            out["rows"] = {k: a[:, :L[k]] for k, a in rows.items()}
+            out["rows"] = rows
         return out
 
     def tick_graph(self, slot: int, batch: int, state, rows, out, q_next, v_next, dt: float, q_solver=None) -> int:
@@ -1151,7 +1149,7 @@ class Handle:
         """(order, packed): the launch order the next solve of the last launch's shape will use; order is None before any"""
         buf = np.zeros(1 << 16, dtype=np.int32)
         packed = C.c_int32(0)
-        n = self.lib.wbcqp_launch_order(self._h, buf.ctypes.data_as(c_i32_p), C.c_int32(buf.size), C.byref(packed))
+        n = self.lib.wbcqp_launch_order(self._h, buf.ctypes.data_as(c_i32_p), buf.size, C.byref(packed))
         if n < 0:
             self._check(n)
         return (buf[:n].copy() if n else None), bool(packed.value)
@@ -1163,25 +1161,13 @@ class Handle:
     def solve_batch_host(self, slot: int, inputs: Dict[str, np.ndarray], hint=None) -> Dict[str, np.ndarray]:
         """wbcqp_solve_batch_host.  hint: [batch, 8] words (any 32-bit integer type) that fill outputs.active_mask before the call -- under
         FLAG_WARM_START the library reads them as the pick hint (include/wbcqp.h); None: zeros, no hint."""
-        st = self._structs[slot]
-        L = st.field_lengths()
+        st, L = self._structs[slot], self._lengths[slot]
         batch = int(np.asarray(inputs["h"]).reshape(-1, st.nv).shape[0])
-        keep = {}
-        cin = CInputs()
-        for k in FIELDS:
-            if L[k] == 0:
-                setattr(cin, k, None)
-                continue
-            a = np.ascontiguousarray(inputs[k], dtype=self.np_dtype).reshape(batch, L[k])
-            keep[k] = a
-            setattr(cin, k, a.ctypes.data)
-        out = dict(x=np.zeros((batch, st.n), self.np_dtype), tau=np.zeros((batch, max(st.na, 1)), self.np_dtype),
-                   status=np.full(batch, -99, np.int32), iters=np.zeros(batch, np.int32),
-                   objective=np.zeros(batch, self.np_dtype), n_active=np.zeros(batch, np.int32),
-                   active_mask=np.zeros((batch, 8), np.uint32))  # (in/out: zeros = no warm-start hint; out = the solution's active rows)
+        keep = {k: np.ascontiguousarray(inputs[k], dtype=self.np_dtype).reshape(batch, L[k]) for k in FIELDS if L[k]}
+        cin = c_inputs({k: a.ctypes.data for k, a in keep.items()})
+        out, cout = self._host_outs(st, batch)
         if hint is not None:
             out["active_mask"][:] = np.ascontiguousarray(hint).view(np.uint32).reshape(batch, 8)
-        cout = COutputs(*[out[k].ctypes.data for k in ("x", "tau", "status", "iters", "objective", "n_active", "active_mask")])
         self._check(self.lib.wbcqp_solve_batch_host(self._h, slot, batch, C.byref(cin), C.byref(cout)))
         out["tau"] = out["tau"][:, :st.na]
         return out
@@ -1199,11 +1185,8 @@ class Handle:
         neq, nin = CE.shape[1], CI.shape[1]
         ce0 = f(ce0).reshape(B, neq) if neq else np.zeros((B, 0))
         ci0 = f(ci0).reshape(B, nin) if nin else np.zeros((B, 0))
-        ptr = lambda a: a.ctypes.data if a.size else None
-        din = CDenseInputs(ptr(H), ptr(g), ptr(CE), ptr(ce0), ptr(CI), ptr(ci0))
+        din = CDenseInputs(*[host_ptr(a if a.size else None) for a in (H, g, CE, ce0, CI, ci0)])
         res = C.POINTER(CDenseOutput)()
-        self.lib.wbcqp_solve_dense_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CDenseInputs),
-                                                    C.POINTER(C.POINTER(CDenseOutput))]
         self._check(self.lib.wbcqp_solve_dense_host(self._h, B, n, neq, nin, int(max_iter), C.byref(din), C.byref(res)))
         o = res.contents
         return dict(x=np.ctypeslib.as_array(o.x, shape=(B, n)).copy(), status=np.ctypeslib.as_array(o.status, shape=(B,)).copy(),
@@ -1215,13 +1198,8 @@ class Handle:
         """Device-pointer form of the narrow seam (wbcqp_solve_dense): inputs H, g, CE, ce0, CI, ci0 and outputs x, status, iters
         (objective, n_active optional) are device tensors of the handle's dtype, [batch, ...]."""
         batch = inputs["g"].shape[0]
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        din = CDenseInputs(*[ptr(inputs.get(k)) for k in ("H", "g", "CE", "ce0", "CI", "ci0")])
-        cout = COutputs()
-        for k in ("x", "tau", "status", "iters", "objective", "n_active"):
-            setattr(cout, k, ptr(outputs.get(k)))
-        self.lib.wbcqp_solve_dense.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(CDenseInputs),
-                                               C.POINTER(COutputs), C.c_void_p]
+        din = CDenseInputs(*[dev_ptr(inputs.get(k)) for k in ("H", "g", "CE", "ce0", "CI", "ci0")])
+        cout = self._outs(outputs, OUT_FIELDS[:-1])  # (an active_mask among the outputs is not passed on)
         self._check(self.lib.wbcqp_solve_dense(self._h, int(batch), int(n), int(neq), int(nin), int(max_iter), C.byref(din), C.byref(cout),
                                                C.c_void_p(stream)))
 

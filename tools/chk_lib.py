@@ -2,7 +2,6 @@
 """Solves one seeded Talos batch with the named build of the library (libwbcqp.so or the diagnostic libwbcqp_stamps.so),
 three launches, and saves every launch's outputs.  Run once per library in separate processes: two builds of the same
 symbols must not share a process.      python tools/chk_lib.py <library file name> <out.npz>"""
-import ctypes as C
 import os
 import sys
 
@@ -31,8 +30,8 @@ def main():
         h.set_structure(0, st)
         if "stamps" in which:
             dbg = torch.zeros(B, capi.K_STAMPS, dtype=torch.int64, device=dev)
-            lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
-            assert lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+            set_stamp_buffer = capi.stamp_buffer_setter(lib)
+            assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
         h.solve_batch(0, B, d_in, d_out, stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         for k, v in d_out.items():

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Same QP replicated B times: per-QP cycles (stamped build) and wall time against the number of busy CUs.
 Separates what a QP costs alone from what the chip adds when every CU runs one (instruction fetch, HBM, clocks)."""
-import ctypes as C
 import os
 import sys
 import time
@@ -20,7 +19,7 @@ def main():
     st = structure.talos_structure()
     one = synth.generate(st, 4, synth.SEED_BASE["talos"])
     dev = torch.device("cuda", 0)
-    lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
+    set_stamp_buffer = capi.stamp_buffer_setter(lib)
     for which in (0, 2):
         for B in (1, 8, 32, 64, 128, 256, 512):
             inp = {k: np.repeat(v[which:which + 1], B, axis=0) for k, v in one.items()}
@@ -30,7 +29,7 @@ def main():
             dbg = torch.zeros(B, capi.K_STAMPS, dtype=torch.int64, device=dev)
             h = capi.Handle(0, capi.F64, flags=capi.FLAG_INDEX_ORDER)
             h.set_structure(0, st)
-            assert lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+            assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
             for _ in range(3):
                 h.solve_batch(0, B, d_in, d_out, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()

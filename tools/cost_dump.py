@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Per-QP cycles of the bench batch (stamped build, index order) next to the iteration counts: how well does
 setup + iterations x constant predict a QP's cost?  Writes gpurun_out/cost_dump.npz."""
-import ctypes as C
 import os
 import sys
 
@@ -16,7 +15,7 @@ def main():
     from inria_wbc_amd import capi, structure, synth
     capi.LIB_PATH = os.path.join(ROOT, "inria_wbc_amd", "lib", "libwbcqp_stamps.so")
     lib = capi.load_library(capi.LIB_PATH)
-    lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
+    set_stamp_buffer = capi.stamp_buffer_setter(lib)
     st = structure.talos_structure()
     B = 1024
     inp = synth.generate(st, B, synth.SEED_BASE["talos"])
@@ -27,7 +26,7 @@ def main():
     dbg = torch.zeros(B, capi.K_STAMPS, dtype=torch.int64, device=dev)
     h = capi.Handle(0, capi.F64, flags=capi.FLAG_INDEX_ORDER | capi.FLAG_HW_DISPATCH)
     h.set_structure(0, st)
-    assert lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+    assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
     runs = []
     for _ in range(3):
         h.solve_batch(0, B, d_in, d_out, stream=torch.cuda.current_stream().cuda_stream)

@@ -3,7 +3,6 @@
 (the second pass finds them in L2 / MALL), (b) 8192 distinct records (287 MB) after 2 GiB of unrelated traffic has gone through the
 caches, 512 workgroups at a time.  Prints the mean 'load' stamp of both (cycles from the QP's first instruction to the barrier that
 ends phase 0).   python tools/load_phase_probe.py"""
-import ctypes as C
 import os
 import sys
 
@@ -25,7 +24,7 @@ def main():
     dev = torch.device("cuda", 0)
     L = st.field_lengths()
     sp = torch.cuda.current_stream().cuda_stream
-    lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
+    set_stamp_buffer = capi.stamp_buffer_setter(lib)
 
     def records(B):
         s = mdl.sample_states(m, tm, min(B, 512), 9_000_000, q_noise=0.01, v_noise=0.05, ref_noise=0.01)
@@ -49,7 +48,7 @@ def main():
         dbg = torch.zeros(B, capi.K_STAMPS, dtype=torch.int64, device=dev)
         h = capi.Handle(0, capi.F64)
         h.set_structure(0, st)
-        assert lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+        assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
         for _ in range(passes):
             if flush:
                 a = torch.empty(256 * 1024 * 1024, dtype=torch.float64, device=dev)  # 2 GiB written, then read

@@ -8,7 +8,6 @@ every phase can be read off.  Cycles per pick (columns: wave 0..3).
     gpurun -- python tools/loop_waves.py [--tick 40] [--qps 943,412]
 """
 import argparse
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -33,7 +32,7 @@ def one(lib, qp_list, tick):
     from inria_wbc_amd import capi, structure, synth
     capi.LIB_PATH = lib
     L = capi.load_library()
-    L.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
+    set_stamp_buffer = capi.stamp_buffer_setter(L)
     st = structure.talos_structure()
     B = 1024
     dev = torch.device("cuda", 0)
@@ -51,7 +50,7 @@ def one(lib, qp_list, tick):
                   status=torch.zeros(1, dtype=torch.int32, device=dev), iters=torch.zeros(1, dtype=torch.int32, device=dev))
         one_in = {k: v[qp:qp + 1].contiguous() for k, v in d_in.items()}
         dbg = torch.zeros(1, capi.K_STAMPS, dtype=torch.int64, device=dev)
-        assert L.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+        assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
         for _ in range(3):
             h.solve_batch(0, 1, one_in, o1, stream=sp)
         torch.cuda.synchronize()

@@ -6,7 +6,6 @@ Reads SHARES, not run time: the stamped build forbids overlaps the real kernel h
     python inria_wbc_amd/build.py --stamps && python tools/phase_profile.py [--robot talos] [--batch 256] [--noise 0.5]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -69,8 +68,8 @@ def main():
     dbg = torch.zeros(B, capi.K_STAMPS, dtype=torch.int64, device=dev)
     h = capi.Handle(0, capi.F64, flags=args.flags | capi.FLAG_INDEX_ORDER | capi.FLAG_HW_DISPATCH)
     h.set_structure(0, st)
-    lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
-    rc = lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr()))
+    set_stamp_buffer = capi.stamp_buffer_setter(lib)
+    rc = set_stamp_buffer(h._h, dbg.data_ptr())
     assert rc == 0, rc
     for _ in range(2):
         h.solve_batch(0, B, d_in, d_out, stream=torch.cuda.current_stream().cuda_stream)

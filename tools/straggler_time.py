@@ -76,12 +76,11 @@ def main():
            "fit_us": {"setup_plus_launch": round(float(fit[0]), 2), "per_iteration": round(float(fit[1]), 3)},
            "note": "batch-1 launches back to back on one stream: launch overhead included (about 5 us)"}
     if args.stamps:
-        import ctypes as C
         from tools.phase_profile import NAMES
         lib = capi.load_library()
-        lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
+        set_stamp_buffer = capi.stamp_buffer_setter(lib)
         dbg = torch.zeros(1, capi.K_STAMPS, dtype=torch.int64, device=dev)
-        assert lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+        assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
         for r in (rows[0], rows[4]):
             one = {k: v[r[0]:r[0] + 1].contiguous() for k, v in d_in.items()}
             for _ in range(3):

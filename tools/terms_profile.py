@@ -2,7 +2,6 @@
 """Per-phase cycle shares of the rows kernel (wbcqp::terms_kernel) from the -DWBCQP_STAMPS diagnostic build.
 Usage (GPU box): python tools/terms_profile.py [--batch 1024]"""
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -51,8 +50,8 @@ def main():
         h.close()
         return
     dbg = torch.zeros(B, 24, dtype=torch.int64, device=dev)
-    lib.wbcqp_debug_set_stamp_buffer.argtypes = [C.c_void_p, C.c_void_p]
-    assert lib.wbcqp_debug_set_stamp_buffer(h._h, C.c_void_p(dbg.data_ptr())) == 0
+    set_stamp_buffer = capi.stamp_buffer_setter(lib)
+    assert set_stamp_buffer(h._h, dbg.data_ptr()) == 0
     for _ in range(3):
         h.problem_data(0, B, state, rows, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
