@@ -2,7 +2,8 @@
 
 Shared by tests/test_task_laws_host.py (the C oracle against this statement, on the CPU) and tests/test_gpu_task_laws.py (the device
 against it).  Frame placements, velocities, classical accelerations, Jacobians, CoM and momentum terms come from oracle/rbd.py
-(rbd_terms): they are held to parity elsewhere.  What is stated here, in mpmath at 50 digits, is what the kernel and the oracle each
+(rbd_terms): they are held to parity elsewhere -- entry by entry against an mpmath statement of their own in tests/rbd_exact.py
+(tests/test_rbd_exact_host.py for the oracle, tests/test_gpu_rbd_exact.py for the device).  What is stated here, in mpmath at 50 digits, is what the kernel and the oracle each
 write in their own floating point:
   * errorInSE3's rotation part: the exact logarithm of oMf' R_ref (no angle thresholds, no branches);
   * tsid's computeAccLimits, returning per joint the eleven decisions it took and the margin of every inequality among them;
