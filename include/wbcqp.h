@@ -361,7 +361,10 @@ int wbcqp_allgather_tau(wbcqp_handle* handle, void* comm, const void* send, void
  * joints when floating_base != 0, revolute joints only otherwise (nq = nv).  x is the solver output [batch][ldx], dv its
  * first nv entries.  status may be NULL; an instance whose status is not WBCQP_HQP_OPTIMAL keeps its state (the
  * reference throws there, controller.cpp:284-307).  q_solver ([batch][nv]) may be NULL.  DEVICE pointers of the handle's
- * dtype, asynchronous on `stream`. */
+ * dtype, asynchronous on `stream`.
+ * q_next, v_next and q_solver must not overlap q, dq or x: the integration is not done in place (the base's twist is read
+ * after v_next has been stored).  q_next == q or v_next == dq is refused with WBCQP_ERR_INVALID; any other overlap is the
+ * caller's to avoid.  tests/se3_exact.py states every output exactly; tests/test_gpu_se3_exact.py holds the kernel to it. */
 int wbcqp_integrate(wbcqp_handle* handle, int batch, int nv, int floating_base, double dt,
                     const void* q, const void* dq, const void* x, int ldx, const int32_t* status,
                     void* q_next, void* v_next, void* q_solver, void* stream);
@@ -477,7 +480,7 @@ typedef struct {
     wbcqp_inputs rows;
     wbcqp_outputs out;
     void* q_next;    /* [batch][nq] */
-    void* v_next;    /* [batch][nv] */
+    void* v_next;    /* [batch][nv]; q_next / v_next must not be state.q / state.v: refused with WBCQP_ERR_INVALID, as wbcqp_integrate refuses it */
     void* q_solver;  /* [batch][nv] or NULL */
     double dt;
 } wbcqp_tick_io;
@@ -517,7 +520,7 @@ typedef struct {
     const void* w;       /* [batch][n_tasks] */
     wbcqp_outputs out;   /* x, tau, status, iters (objective, n_active) of the LAST tick */
     void* q_next;        /* [batch][nq] the state after n_ticks ticks */
-    void* v_next;        /* [batch][nv] */
+    void* v_next;        /* [batch][nv]; with n_ticks == 1 the call is one wbcqp_tick: q_next / v_next equal to state.q / state.v are refused there */
     void* q_solver;      /* [batch][nv] or NULL */
     double dt;
     int32_t* iters_sum;  /* [batch] active-set iterations over all ticks, may be NULL */
@@ -562,7 +565,7 @@ typedef struct {              /* wbcqp_tick_io without the record: the library k
     wbcqp_state state;        /* q [batch][nq], v [batch][nv], ref [batch][nref], momentum [batch][6] or NULL */
     wbcqp_outputs out;        /* x [batch][ldx], tau [batch][na], status, iters (objective, n_active, active_mask) by instance */
     void* q_next;             /* [batch][nq] */
-    void* v_next;             /* [batch][nv] */
+    void* v_next;             /* [batch][nv]; q_next / v_next must not be state.q / state.v (the integration is not done in place; NOT checked on this path) */
     void* q_solver;           /* [batch][nv] or NULL */
     double dt;
 } wbcqp_mixed_io;

@@ -506,6 +506,7 @@ int wbcqp_integrate_host(wbcqp_handle* h, int batch, int nv, int floating_base, 
 {
     if (!h) return WBCQP_ERR_INVALID;
     if (batch < 0 || nv <= 0 || ldx < nv) return fail(h, WBCQP_ERR_INVALID, "bad batch / nv / ldx");
+    if (floating_base && nv < 6) return fail(h, WBCQP_ERR_INVALID, "a floating base needs nv >= 6");  // (before anything is staged)
     if (batch == 0) return WBCQP_OK;
     if (!q || !dq || !x || !q_next || !v_next) return fail(h, WBCQP_ERR_INVALID, "q / dq / x / q_next / v_next is NULL");
     HIP_TRY(h, hipSetDevice(h->device));

@@ -328,6 +328,8 @@ int integrate_impl(wbcqp_handle* h, int batch, int nv, int floating_base, double
     if (floating_base && nv < 6) return fail(h, WBCQP_ERR_INVALID, "a floating base needs nv >= 6");
     if (batch == 0) return WBCQP_OK;
     if (!q || !dq || !x || !q_next || !v_next) return fail(h, WBCQP_ERR_INVALID, "q / dq / x / q_next / v_next is NULL");
+    // the kernel's outputs are __restrict__, and lane 0 reads dq[0..5] after lanes 0..5 have stored v_next[0..5]: in place, the base would be integrated twice
+    if (q_next == q || v_next == dq) return fail(h, WBCQP_ERR_INVALID, "q_next / v_next must not be q / dq: the integration is not done in place");
     HIP_TRY(h, hipSetDevice(h->device));
     return with_dtype(h, [&](auto tag) -> int {
         using TI = WB_TI(tag);

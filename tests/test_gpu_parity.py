@@ -284,6 +284,14 @@ def test_integrate_parity(floating_base):
     assert np.abs(qn[ok] - ref["q_next"][ok]).max() < 1e-13   # device and host libm differ in the last bits of sin/cos/atan2
     assert np.abs(qs[ok] - ref["q_solver"][ok]).max() < 1e-12
     assert np.array_equal(qn[~ok], q[~ok]) and np.array_equal(vn[~ok], dq[~ok])
+    # ... and q_solver is that kept state repacked: position and joints copied, the INPUT quaternion's rotation vector (the oracle takes no
+    # status and says nothing here; tests/test_gpu_se3_exact.py holds the same entries to the exact statement)
+    kept = q[~ok]
+    if floating_base:
+        assert np.array_equal(qs[~ok][:, :3], kept[:, :3]) and np.array_equal(qs[~ok][:, 6:], kept[:, 7:])
+        assert np.abs(qs[~ok][:, 3:6] - Rot.from_quat(kept[:, 3:7]).as_rotvec()).max() < 1e-12
+    else:
+        assert np.array_equal(qs[~ok], kept)
     h.close()
 
 
