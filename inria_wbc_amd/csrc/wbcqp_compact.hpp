@@ -28,6 +28,9 @@
 // instruction accounting (tools/phase_insts.sh): the QP ends at stamp WBCQP_X_STOP, so the SQ counters of two such builds differ by one phase
 #undef STAMP
 #define STAMP(i) { if ((i) == WBCQP_X_STOP) return; }
+#if WBCQP_X_STOP == 22 || WBCQP_X_STOP == 5 || WBCQP_X_STOP == 6 || WBCQP_X_STOP == 19
+#error "stamps 22, 5, 6 and 19 sit inside equality_phase_in_place (wbcqp_equality.hpp): a build cannot end the QP there"
+#endif
 #endif
 
 namespace wbcqp {
@@ -277,6 +280,69 @@ __device__ __forceinline__ void rotate_row_ps(const double* prm, int L, double& 
             }
     }
 }
+// the reflector of a full step, H = I - tau v v' with v = d[iq:] - alpha e_0, from d[iq] and |d2|^2.  `below`: positions exist behind iq; without
+// them (or with d2 = 0) nothing is reflected and alpha is alpha0
+struct Reflector { double alpha, v0, tau; };
+__device__ __forceinline__ Reflector reflector(double diq, double dn2, bool below, double alpha0)
+{
+    Reflector h{alpha0, 0.0, 0.0};
+    if (below && dn2 > 0.0) {
+        const double inx = rsqrt(dn2);
+        const double nx = dn2 * inx;
+        h.alpha = (diq >= 0.0) ? -nx : nx;
+        h.v0 = diq - h.alpha;
+        h.tau = fast_rcp(fma(nx, fabs(diq), dn2));
+    }
+    return h;
+}
+// d's entry of column j = neq + pos: into V from iq0 on (zero below), into dI below iq0 (zero from there on)
+__device__ __forceinline__ void store_d(double* Vn, double* dI, int j, int pos, int iq0, double dj) { Vn[j] = (j >= iq0) ? dj : 0.0; dI[pos] = (j < iq0) ? dj : 0.0; }
+// "one of this wave's rows holds a z_k^2 > eps", for z_exceeds_eps
+__device__ __forceinline__ void flag_zbig(const Ctx& c, int* LSi, bool zbig)
+{
+    const unsigned long long any = __ballot(zbig);
+    if (c.lane == 0) LSi[BZF + c.wave] = (any != 0ull) ? 1 : 0;
+}
+// z'z > eps, from the flags of the `nw` waves that formed z; the sum itself only when no wave's flag is up (degenerate picks only).  Every thread calls it
+__device__ __forceinline__ bool z_exceeds_eps(Ctx& c, const int* LSi, int nw, double eps)
+{
+    int zf = LSi[BZF] | LSi[BZF + 1];
+    if (nw > 2) zf |= LSi[BZF + 2];
+    bool zok = zf != 0;
+    if (!zok) {
+        const double zk = (c.tid < c.n) ? c.z[c.tid] : 0.0;
+        zok = fabs(block_sum(c, zk * zk)) > eps;
+    }
+    return zok;
+}
+// generation `par` of the pick election's slots; one thread calls it, a barrier before the slot's next atomics
+__device__ __forceinline__ void arm_election(double* EL, int par, bool use_warm)
+{
+    unsigned* ELu = reinterpret_cast<unsigned*>(EL);
+    EL[EMIN + par] = kNone;
+    ELu[EKEY + par] = 0xffffffffu;
+    if (use_warm) {
+        EL[EWMIN + par] = kNone;
+        ELu[EWKEY + par] = 0xffffffffu;
+    }
+}
+// Step 2b's partial step length t1 (dual feasibility), elected inside ONE wave (no barrier: a wave's LDS operations execute in order) among the lanes
+// that stand (r > 0), first position on ties: lane 0 arms the slots, a standing lane bids its ratio u / r, and the lanes that hold the minimum claim
+// it with their position.  Bid and claim are two calls so that the caller's own work runs under the first atomic's round trip.
+__device__ __forceinline__ void t1_arm(double* EL) { EL[ET1] = __builtin_huge_val(); reinterpret_cast<unsigned*>(EL)[ET1POS] = 0x7fffffffu; }
+__device__ __forceinline__ double t1_bid(double* EL, bool stands, double u, double r)
+{
+    double ratio = __builtin_huge_val();
+    if (stands) {
+        ratio = ratio_pos(u, r);
+        lds_min_f64(EL + ET1, ratio);
+    }
+    return ratio;
+}
+__device__ __forceinline__ void t1_claim(double* EL, bool stands, double ratio, int pos)
+{
+    if (stands && ratio == EL[ET1]) lds_min_u32(reinterpret_cast<unsigned*>(EL) + ET1POS, (unsigned)pos);
+}
 } // namespace lp
 
 // what a thread keeps about the one row of s it owns (nin2 <= 256: row tid)
@@ -285,6 +351,79 @@ struct OwnRow {
     double ci0;
     const double* coef; // friction rows only: the 12 coefficients of the row (of its positive twin) in the LDS table, else null
 };
+
+// The actuation rows' global loads between their issue and their use: rows nu .. nv - 1 of M (pM: the record's packed M), the contact Jacobians'
+// columns (pAc) and the force generators' coefficients of the lane's columns (a constant table of the structure: L2).  Four lanes per row (ActRegs).
+template <typename TI>
+struct ActLoads {
+    TI mv[cp::NVQ];
+    TI av[2][6];
+    double tv[cp::KQ][6];
+    bool issued = false;
+
+    __device__ __forceinline__ void issue(const Ctx& c, const DevStruct& S, const TI* pM, const TI* pAc)
+    {
+        const int tid = c.tid, nv = c.nv, na = c.na, nc = c.nc;
+        if (na > 0) {
+            const int rr = min(tid >> 2, na - 1), q4 = tid & 3;
+            const int row = c.nu + rr;
+#pragma unroll
+            for (int u = 0; u < cp::NVQ; ++u) {
+                const int j = min(q4 + 4 * u, nv - 1);
+                const int hi = max(row, j), lo = min(row, j);
+                mv[u] = pM[hi * (hi + 1) / 2 + lo];
+            }
+            if (nc > 0) {
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 6; ++r) av[ct][r] = pAc[(min(ct, nc - 1) * 6 + r) * nv + row];
+#pragma unroll
+                for (int u = 0; u < cp::KQ; ++u) {
+                    const int mcol = min(q4 + 4 * u, c.k - 1);
+#pragma unroll
+                    for (int r = 0; r < 6; ++r) tv[u][r] = S.force_gen[(u / 3) * 72 * ((nc > 1) ? 1 : 0) + r * 12 + (mcol - 12 * (u / 3) * ((nc > 1) ? 1 : 0))];
+                }
+            }
+        }
+        issued = true;
+    }
+    // [M_a | -J_a'] of the lane's columns, J_a' = T'A_c formed here (na > 0)
+    __device__ __forceinline__ void consume(const Ctx& c, ActRegs& ar) const
+    {
+        const int q4 = c.tid & 3;
+#pragma unroll
+        for (int u = 0; u < cp::NVQ; ++u) ar.am[u] = (q4 + 4 * u < c.nv) ? (double)mv[u] : 0.0;
+#pragma unroll
+        for (int u = 0; u < cp::KQ; ++u) {
+            double sacc = 0.0;
+            if (c.nc > 0) {
+#pragma unroll
+                for (int r = 0; r < 6; ++r) sacc = fma(tv[u][r], (double)av[u / 3][r], sacc);
+            }
+            ar.aj[u] = (q4 + 4 * u < c.k) ? sacc : 0.0;
+        }
+    }
+};
+
+// The actuation rows into registers.  The generic kernel (SPEC 0) loads where it uses, into an object of its own: the values live nowhere else (through
+// the caller's object the allocator went past 256 VGPRs: AGPR copies, one workgroup per CU).  A specialised one takes what was issued behind the equality QR.
+template <int SPEC, typename TI>
+__device__ __forceinline__ void load_act_rows(const Ctx& c, const DevStruct& S, const TI* pM, const TI* pAc, ActLoads<TI>& early, ActRegs& ar)
+{
+    ar = ActRegs{};
+    if (c.na > 0) {
+        if constexpr (SPEC == 0) {
+            ActLoads<TI> here;
+            here.issue(c, S, pM, pAc);
+            here.consume(c, ar);
+        }
+        else {
+            if (!early.issued) early.issue(c, S, pM, pAc);
+            early.consume(c, ar);
+        }
+    }
+}
 
 template <int SPEC> __device__ __forceinline__ Dims dims_of(const DevStruct& S)
 {
@@ -319,6 +458,31 @@ __global__ __launch_bounds__(128) void ffcache_kernel(const DevStruct S, const T
     ol[0] = yF[0][0]; ol[1] = yF[0][1]; ol[2] = yF[1][0]; ol[3] = yF[1][1]; ol[4] = tF[0]; ol[5] = tF[1];
     __builtin_amdgcn_s_waitcnt(0); // (every store of the entry before the weight that validates it; readers are later launches in stream order anyway)
     if (lane == 0) o[0] = wt;
+}
+
+// Phase 5: x and tau = h_a + M_a dv - J_a' f (getActuatorForces) of the final iterate, the active mask (the next tick's hint under
+// WBCQP_FLAG_WARM_START), status, iterations and objective.  qp: the QP's index in the batch, qr: its record's.  Its first barrier ends the loop.
+template <typename TI>
+__device__ __forceinline__ void decode_and_write(Ctx& c, const GroupArgs<TI>& ga, const ActRegs& ar, double* tact, const signed char* act, size_t qp, size_t qr,
+                                                 int status, int iters, double f_value)
+{
+    const int tid = c.tid, n = c.n, na = c.na, nin2 = c.nin2;
+    bsync();
+    TI* xo = ga.x + qp * n;
+    for (int i = tid; i < n; i += kThreads) xo[i] = (TI)c.x[i];
+    if (na > 0) {
+        TI* to = ga.tau + qp * na;
+        const TI hav = ga.h[qr * c.nv + c.nu + min(tid, na - 1)];
+        // tau' of the final iterate, from scratch (inside the loop it is carried by increments)
+        {
+            const double acc = act_dot(c, ar, c.x, c.z, 0.0);
+            if ((tid & 3) == 0 && (tid >> 2) < na) tact[tid >> 2] = acc;
+            bsync();
+        }
+        if (tid < na) to[tid] = (TI)((double)hav + tact[tid]);
+    }
+    if (ga.amask) write_active_mask(ga, qp, c, (status == HQP_OPTIMAL) && nin2 > 0 && tid < nin2 && act[tid] != 0);
+    write_results(ga, qp, c, status, iters, f_value);
 }
 
 // SPEC > 0: the instantiation for the shipped stack kSpecDims[SPEC - 1] -- every size and LDS offset below is a literal
@@ -568,125 +732,25 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             excl[tid] = 1;
         }
         if (tid >= n && tid < VS) c.xold[tid] = 0.0; // the second x buffer gets the same finite padding as the first (g, its tenant so far, ends at n)
-        if (tid == 0) { // the loop's election slots (lp::E*), both generations armed
-            double* EL0 = lds + D.o_vec + vm.EL;
-            unsigned* EL0u = reinterpret_cast<unsigned*>(EL0);
-            EL0[lp::EMIN] = lp::kNone; EL0[lp::EMIN + 1] = lp::kNone; EL0[lp::EWMIN] = lp::kNone; EL0[lp::EWMIN + 1] = lp::kNone;
-            EL0u[lp::EKEY] = 0xffffffffu; EL0u[lp::EKEY + 1] = 0xffffffffu; EL0u[lp::EWKEY] = 0xffffffffu; EL0u[lp::EWKEY + 1] = 0xffffffffu;
+        if (tid == 0) { // the loop's election slots (lp::E*), both generations armed (the hinted rows' too: whether a hint is used is decided at the loop's head)
+            lp::arm_election(lds + D.o_vec + vm.EL, 0, true);
+            lp::arm_election(lds + D.o_vec + vm.EL, 1, true);
         }
     }
 
     // The actuation rows' global loads (rows nu .. nv - 1 of M, the contact Jacobians' columns: from the record, L2 or HBM by now) are ISSUED as soon as the
     // equality QR has released its registers and CONSUMED behind the phases that follow it (y, x, u): their latency -- most of the 3.1 k cycles the phase
     // "actuation rows -> registers" took -- runs under those phases' barriers.
-    TI act_mv[cp::NVQ];
-    TI act_av[2][6];
-    double act_tv[cp::KQ][6]; // the force generators' coefficients of the lane's columns (a constant table of the structure: L2)
-    bool act_issued = false;
-    auto issue_act_loads_into = [&](TI (&act_mv)[cp::NVQ], TI (&act_av)[2][6], double (&act_tv)[cp::KQ][6]) __attribute__((always_inline)) {
-        if (na > 0) {
-            const int rr = min(tid >> 2, na - 1), q4 = tid & 3;
-            const int row = nu + rr;
-#pragma unroll
-            for (int u = 0; u < cp::NVQ; ++u) {
-                const int j = min(q4 + 4 * u, nv - 1);
-                const int hi = max(row, j), lo = min(row, j);
-                act_mv[u] = pM[hi * (hi + 1) / 2 + lo];
-            }
-            if (nc > 0) {
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) act_av[ct][r] = pAc[(min(ct, nc - 1) * 6 + r) * nv + row];
-#pragma unroll
-                for (int u = 0; u < cp::KQ; ++u) {
-                    const int mcol = min(q4 + 4 * u, k - 1);
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) act_tv[u][r] = S.force_gen[(u / 3) * 72 * ((nc > 1) ? 1 : 0) + r * 12 + (mcol - 12 * (u / 3) * ((nc > 1) ? 1 : 0))];
-                }
-            }
-        }
-    };
-    auto issue_act_loads = [&]() __attribute__((always_inline)) {
-        issue_act_loads_into(act_mv, act_av, act_tv);
-        act_issued = true;
-    };
-
-    // ---------------- phase 3: equality constraints, blocked (equality_phase_blocked with N already in place) ----------------
+    // (the specialised kernels only: in the generic one, whose dimensions are run-time values, the loaded values' longer life pushed the allocator
+    // past 256 VGPRs -- AGPR copies, one workgroup per CU; tools/kernel_regs.py, profiles/r06/not_kept.txt item 9)
+    ActLoads<TI> act_early;
+    // ---------------- phase 3: equality constraints, blocked, N already in place ----------------
     if (neq > 0) {
-        const int m = neq;
-        double* rhs = ce0v;
-        // ---- rhs_e = -(N(:,e)'x0 + ce0_e): 8 lanes per equality, ten terms each in flight
-        {
-            const int e = tid >> 3, kc = tid & 7;
-            const int es = min(e, m - 1);
-            double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-            for (int i = 0; i < 10; i += 2) {
-                const int k0 = min(kc + 8 * i, n - 1), k1 = min(kc + 8 * i + 8, n - 1);
-                const double x0 = (kc + 8 * i < n) ? c.x[k0] : 0.0, x1 = (kc + 8 * i + 8 < n) ? c.x[k1] : 0.0;
-                a0 = fma(Nm[k0 * ldb + es], x0, a0);
-                a1 = fma(Nm[k1 * ldb + es], x1, a1);
-            }
-            const double acc = grp8_sum(a0 + a1);
-            if (e < m && kc == 0) rhs[e] = -(acc + rhs[e]);
-        }
-        STAMP(22)
-        // ---- B = J0' N over N itself: every product is in registers before the first element is replaced
-        {
-            const int ncg = (m + 3) >> 2;
-            const int cpi = tid / ncg, cg = tid - cpi * ncg;
-            const int c0 = 2 * cpi, c1i = min(c0 + 1, n - 1);
-            const bool actv = c0 < n;
-            int kmin = actv ? blk_begin(c0, nv) : n, kmax = actv ? c1i + 1 : 0;
-            kmin = wave_min_int(kmin);
-            kmax = wave_max_int(kmax);
-            double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
-            const int c0s = actv ? c0 : 0, c1s = actv ? c1i : 0;
-            tile2x4(c.J, c0s, c1s, ldj, Nm + 4 * cg, ldb, kmin, kmax, acc);
-            bsync();
-            if (actv) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    if (4 * cg + q < m) {
-                        Nm[c0 * ldb + 4 * cg + q] = acc[0][q];
-                        if (c0 + 1 < n) Nm[(c0 + 1) * ldb + 4 * cg + q] = acc[1][q];
-                    }
-            }
-        }
-        bsync();
-        STAMP(5)
         constexpr int NTQ = (SPEC > 0 && kSpecDims[SPEC > 0 ? SPEC - 1 : 0].n <= 64) ? 8 : 10; // row pairs per lane of the QR (iCub, Talos on one foot: n 62)
-        bool ok = qr_unified<NTQ>(c, Nm, c.s, c.s + 160);
-        if (!ok) status = HQP_ERROR; // redundant equalities
-        else {
-            // (the specialised kernels only: in the generic one, whose dimensions are run-time values, the loaded values' longer life pushed the allocator
-            // past 256 VGPRs -- AGPR copies, one workgroup per CU; tools/kernel_regs.py, profiles/r06/not_kept.txt item 9)
-            if constexpr (SPEC != 0) {
-                if (D.act_bounds) issue_act_loads();
-            }
-            bsync();
-            STAMP(6)
-            if (c.wave == 0) {
-                if (m <= 12) solve_y<12>(c, rhs);
-                else if (m <= 20) solve_y<20>(c, rhs);
-                else solve_y<24>(c, rhs);
-            }
-            bsync();
-            STAMP(19)
-            double yy = 0.0;
-            if (tid < m) yy = rhs[tid] * rhs[tid];
-            if (tid >= 128 && tid - 128 < n) {
-                const int kk = tid - 128;
-                const double* Jr = c.J + kk * ldj;
-                double acc = 0.0;
-                for (int e = 0; e < m; ++e) acc = fma(Jr[e], rhs[e], acc);
-                c.x[kk] += acc;
-            }
-            yy = block_sum(c, yy); // (its barrier is also the one the loop's set-up waits for: every read of J, R and y is behind it)
-            f_value += 0.5 * yy;
-            c.iq = m;
-        }
+        const auto behind_qr = [&act_early, &c, &S, &D, pM, pAc]() __attribute__((always_inline)) {
+            if (SPEC != 0 && D.act_bounds) act_early.issue(c, S, pM, pAc);
+        };
+        if (!equality_phase_in_place<NTQ>(c, Nm, ce0v, f_value, behind_qr)) status = HQP_ERROR; // redundant equalities
         STAMP(8)
     }
 
@@ -695,42 +759,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
     // decode's tau = h_a + M_a dv - J_a' f reads them: they are loaded BEHIND the loop then, and the loop does not carry their 38 registers -- which is what the
     // three-per-CU twin of such a stack (168 VGPRs) kept in scratch (round 5: 148 B/lane, a third of the scratch instructions inside the loop).
     ActRegs ar;
-    auto load_act_rows = [&]() __attribute__((always_inline)) {
-    if (na > 0) {
-        const int q4 = tid & 3;
-        auto consume = [&](TI (&mv)[cp::NVQ], TI (&av)[2][6], double (&tv)[cp::KQ][6]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int u = 0; u < cp::NVQ; ++u) ar.am[u] = (q4 + 4 * u < nv) ? (double)mv[u] : 0.0;
-#pragma unroll
-            for (int u = 0; u < cp::KQ; ++u) {
-                double sacc = 0.0;
-                if (nc > 0) {
-#pragma unroll
-                    for (int r = 0; r < 6; ++r) sacc = fma(tv[u][r], (double)av[u / 3][r], sacc);
-                }
-                ar.aj[u] = (q4 + 4 * u < k) ? sacc : 0.0;
-            }
-        };
-        if constexpr (SPEC == 0) { // (the generic kernel: loads and use in one place, the values live nowhere else -- see the early issue behind the QR)
-            TI mv[cp::NVQ];
-            TI av[2][6];
-            double tv[cp::KQ][6];
-            issue_act_loads_into(mv, av, tv);
-            consume(mv, av, tv);
-        }
-        else {
-            if (!act_issued) issue_act_loads();
-            consume(act_mv, act_av, act_tv);
-        }
-    }
-    else {
-#pragma unroll
-        for (int u = 0; u < cp::NVQ; ++u) ar.am[u] = 0.0;
-#pragma unroll
-        for (int u = 0; u < cp::KQ; ++u) ar.aj[u] = 0.0;
-    }
-    };
-    if (D.act_bounds) load_act_rows();
+    if (D.act_bounds) load_act_rows<SPEC>(c, S, pM, pAc, act_early, ar);
 
     STAMP(7)
 
@@ -815,8 +844,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             own.coef = nullptr;
             if (tid < nin2) {
                 const int mt = meta0;
-                const int kind = mt & 3, rr = (mt >> 3) & 255, ct = (mt >> 11) & 15;
-                const bool neg = (mt >> 2) & 1;
+                const auto [kind, neg, rr, ct, col] = row_meta_unpack(mt);
                 if (kind == INEQ_BOUNDS) {
                     own.meta = mt;
                     own.ci0 = neg ? c.bub[rr] : -c.blb[rr];
@@ -906,8 +934,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             }
             const int mt = own.meta;
             if (mt >= 0) {
-                const int kind = mt & 3, ct = (mt >> 11) & 15, col = (mt >> 15) & 255;
-                const bool neg = (mt >> 2) & 1;
+                const auto [kind, neg, rr, ct, col] = row_meta_unpack(mt);
                 double v;
                 if (kind == INEQ_BOUNDS) {
                     const double xv = fma(t, zp[col], xp[col]);
@@ -943,8 +970,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             }
             const int mt = own.meta;
             if (mt >= 0) {
-                const int kind = mt & 3, ct = (mt >> 11) & 15, col = (mt >> 15) & 255;
-                const bool neg = (mt >> 2) & 1;
+                const auto [kind, neg, rr, ct, col] = row_meta_unpack(mt);
                 double dz;
                 if (kind == INEQ_BOUNDS) {
                     const double zc = zp[col];
@@ -1060,8 +1086,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             STAMP(9)
             // the row n of constraint ip: kind, first column of its support, sign
             const int ip = (int)(key >> 23), mt = (int)(key & 0x7fffffu);
-            const int kind = mt & 3, rr = (mt >> 3) & 255, ct = (mt >> 11) & 15, col = (mt >> 15) & 255;
-            const bool negrow = (mt >> 2) & 1;
+            const auto [kind, negrow, rr, ct, col] = row_meta_unpack(mt);
             const double sg = negrow ? -1.0 : 1.0;
             const int iq0 = c.iq;
             if (tid == kThreads - 1) {
@@ -1069,12 +1094,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 c.A[iq0] = ip;
                 // the slot of the NEXT election is re-armed here: its last readers passed the barrier of the election just held, its next atomics lie
                 // behind this pick's barriers
-                EL[lp::EMIN + par] = lp::kNone;
-                ELu[lp::EKEY + par] = 0xffffffffu;
-                if (use_warm) {
-                    EL[lp::EWMIN + par] = lp::kNone;
-                    ELu[lp::EWKEY + par] = 0xffffffffu;
-                }
+                lp::arm_election(EL, par, use_warm);
             }
             STAMP(10)
 
@@ -1086,10 +1106,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 if (c.wave == 0) {
                     const int j = neq + min(c.lane, MM - 1);
                     const double dj = sg * fma(-Wp[col], Vp[j], c.J[col * ldj + j]);
-                    if (c.lane < MM) {
-                        Vn[j] = (j >= iq0) ? dj : 0.0;
-                        dI[c.lane] = (j < iq0) ? dj : 0.0;
-                    }
+                    if (c.lane < MM) lp::store_d(Vn, dI, j, c.lane, iq0, dj);
                 }
             }
             else if (kind == INEQ_FORCE) {
@@ -1109,10 +1126,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 a = quad_sum(a);
                 fw = quad_sum(fw);
                 const double dj = sg * fma(-fw, vj, a); // (the table holds the positive row)
-                if (q4 == 0 && jq < MM) {
-                    Vn[j] = (j >= iq0) ? dj : 0.0;
-                    dI[jq] = (j < iq0) ? dj : 0.0;
-                }
+                if (q4 == 0 && jq < MM) lp::store_d(Vn, dI, j, jq, iq0, dj);
             }
             else {
                 // the row is in the registers of quad rr: published with n'w, then a quad per column, a quarter of the rows per lane
@@ -1148,10 +1162,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 double acc = dot8(c.np, 1, c.J + j, ldj, ka, kb);
                 acc = quad_sum(acc);
                 const double dj = fma(-npw, vj, acc);
-                if (q4 == 0 && jq < MM) {
-                    Vn[j] = (j >= iq0) ? dj : 0.0;
-                    dI[jq] = (j < iq0) ? dj : 0.0;
-                }
+                if (q4 == 0 && jq < MM) lp::store_d(Vn, dI, j, jq, iq0, dj);
             }
             STAMP(24)
             bsync(); // A
@@ -1206,15 +1217,11 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                         zbig = zv * zv > eps;
                     }
                     STAMP(18)
-                    const unsigned long long any = __ballot(zbig);
-                    if (c.lane == 0) LSi[lp::BZF + c.wave] = (any != 0ull) ? 1 : 0;
+                    lp::flag_zbig(c, LSi, zbig);
                 }
                 else {
                     const int i = c.lane;
-                    if (i == 0) { // the step length's election slots (their last readers are two barriers back)
-                        EL[lp::ET1] = inf;
-                        ELu[lp::ET1POS] = 0x7fffffffu;
-                    }
+                    if (i == 0) lp::t1_arm(EL); // (the slots' last readers are two barriers back)
                     const double* Rr = Ri + lp::rio(min(i, MM - 1), MM);
                     const double* dq = dI + i;
                     double r0 = 0.0, r1 = 0.0, r2 = 0.0, r3 = 0.0;
@@ -1232,30 +1239,18 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                     const double vq = Vn[neq + min(i, MM - 1)];
                     const double diq = Vn[iq0 < n ? iq0 : n - 1];
                     if (i < mi) c.r[neq + i] = rl;
-                    // step 2b's partial step length t1 (dual feasibility): elected among the lanes with r > 0, first position on ties
-                    double ratio = inf;
-                    if (rl > 0.0) {
-                        ratio = ratio_pos(c.u[neq + i], rl);
-                        lds_min_f64(EL + lp::ET1, ratio);
-                    }
+                    const bool stands = rl > 0.0;
+                    const double ratio = lp::t1_bid(EL, stands, stands ? c.u[neq + i] : 0.0, rl);
                     const double dn2 = wave_sum((i < MM) ? vq * vq : 0.0); // |d2|^2 = z'n (V is zero below iq)
-                    if (rl > 0.0 && ratio == EL[lp::ET1]) lds_min_u32(ELu + lp::ET1POS, (unsigned)(neq + i));
-                    // the reflector of a full step, H = I - tau v v' with v = d[iq:] - alpha e_0, and the step length t2
-                    double alpha = (iq0 < n) ? diq : 0.0, v0 = 0.0, tau = 0.0;
-                    if (iq0 + 1 < n && dn2 > 0.0) {
-                        const double inx = rsqrt(dn2);
-                        const double nx = dn2 * inx;
-                        alpha = (diq >= 0.0) ? -nx : nx;
-                        v0 = diq - alpha;
-                        tau = fast_rcp(fma(nx, fabs(diq), dn2));
-                    }
+                    lp::t1_claim(EL, stands, ratio, neq + i);
+                    const lp::Reflector h = lp::reflector(diq, dn2, iq0 + 1 < n, (iq0 < n) ? diq : 0.0); // ... and the step length t2
                     if (c.lane == 0) { // (|d2|^2, alpha) and (v0, tau) are read as pairs: written as pairs
                         double2v o;
                         o.x = dn2;
-                        o.y = alpha;
+                        o.y = h.alpha;
                         *reinterpret_cast<double2v*>(__builtin_assume_aligned(LS + lp::BDN2, 16)) = o;
-                        o.x = v0;
-                        o.y = tau;
+                        o.x = h.v0;
+                        o.y = h.tau;
                         *reinterpret_cast<double2v*>(__builtin_assume_aligned(LS + lp::BV0, 16)) = o;
                         LS[lp::BT2C] = ratio_pos(-sip, dn2);
                     }
@@ -1266,12 +1261,10 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
             STAMP(12)
             double znp, dn2, t1, alpha, v0, tau, t2;
             int lpos;
-            bool zok;
             {
                 const double2 da = *reinterpret_cast<const double2*>(LS + lp::BDN2); // |d2|^2, alpha
                 const double2 vt = *reinterpret_cast<const double2*>(LS + lp::BV0);  // v0, tau
                 const double t2c = LS[lp::BT2C];
-                const int zf = LSi[lp::BZF] | LSi[lp::BZF + 1] | LSi[lp::BZF + 2];
                 t1 = EL[lp::ET1];
                 lpos = (int)ELu[lp::ET1POS];
                 dn2 = da.x;
@@ -1279,12 +1272,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 v0 = vt.x;
                 tau = vt.y;
                 znp = dn2; // z'n = (J2 d2)'n = d2'(J2'n) = |d2|^2: the second reduction eiquadprog spends on it is the first one again
-                zok = zf != 0;
-                if (!zok) { // no row's z_k^2 alone exceeds eps: the sum decides (degenerate picks only)
-                    const double zk = (tid < n) ? c.z[tid] : 0.0;
-                    zok = fabs(block_sum(c, zk * zk)) > eps;
-                }
-                t2 = zok ? t2c : inf;
+                t2 = lp::z_exceeds_eps(c, LSi, 3, eps) ? t2c : inf;
             }
             double uiq = 0.0; // u[iq] of the candidate: every thread carries it, LDS sees it when the constraint is added
             int drops = 0;
@@ -1493,8 +1481,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                             c.part[kr] = tj; // column iq' of J, for the w of phase C
                             zbig = zn * zn > eps;
                         }
-                        const unsigned long long any = __ballot(zbig);
-                        if (c.lane == 0) LSi[lp::BZF + c.wave] = (any != 0ull) ? 1 : 0;
+                        lp::flag_zbig(c, LSi, zbig);
                     }
                     else if (c.wave == 3) {
                         // rows of Ri.  Row i <= p has all its elements from column p on; row i > p begins at column i (left of it
@@ -1523,10 +1510,7 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                         const bool row = i < mi;
                         const bool has = row && i != p;
                         const int i2 = i - ((i > p) ? 1 : 0);
-                        if (i == 0) {
-                            EL[lp::ET1] = inf;
-                            ELu[lp::ET1POS] = 0x7fffffffu;
-                        }
+                        if (i == 0) lp::t1_arm(EL);
                         const double tj = row ? cl * qP : 0.0;
                         const double rn = row ? fma(-delta, tj, c.r[neq + min(i, mi - 1)]) : 0.0;
                         const double uu = c.u[neq + min(i, mi - 1)];
@@ -1538,12 +1522,8 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                         }
                         if (i == mi) c.A[iq - 1] = ip; // the candidate moves with its position
                         DSTAMP(40)
-                        double ratio = inf;
-                        if (has && rn > 0.0) {
-                            ratio = ratio_pos(uu, rn);
-                            lds_min_f64(EL + lp::ET1, ratio);
-                        }
-                        if (has && rn > 0.0 && ratio == EL[lp::ET1]) lds_min_u32(ELu + lp::ET1POS, (unsigned)(neq + i2));
+                        const bool stands = has && rn > 0.0;
+                        lp::t1_claim(EL, stands, lp::t1_bid(EL, stands, uu, rn), neq + i2);
                         DSTAMP(41)
                     }
                 }
@@ -1551,29 +1531,17 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
                 bsync();
                 STAMP(15)
                 {
-                    const int zf = LSi[lp::BZF] | LSi[lp::BZF + 1];
                     t1 = EL[lp::ET1];
                     lpos = (int)ELu[lp::ET1POS];
                     znp = fma(delta, delta, znp);
                     dn2 = fma(delta, delta, dn2);
                     c.iq = iq - 1;
-                    zok = zf != 0;
-                    if (!zok) {
-                        const double zk = (tid < n) ? c.z[tid] : 0.0;
-                        zok = fabs(block_sum(c, zk * zk)) > eps;
-                    }
-                    t2 = zok ? ratio_pos(-sip, znp) : inf;
+                    t2 = lp::z_exceeds_eps(c, LSi, 2, eps) ? ratio_pos(-sip, znp) : inf;
                     // the reflector of the shorter active set: d[iq'] = delta heads the null-space part now
-                    alpha = delta;
-                    v0 = 0.0;
-                    tau = 0.0;
-                    if (iq < n && dn2 > 0.0) { // (iq' + 1 < n)
-                        const double inx = rsqrt(dn2);
-                        const double nx = dn2 * inx;
-                        alpha = (delta >= 0.0) ? -nx : nx;
-                        v0 = delta - alpha;
-                        tau = fast_rcp(fma(nx, fabs(delta), dn2));
-                    }
+                    const lp::Reflector h = lp::reflector(delta, dn2, iq < n /* iq' + 1 < n */, delta);
+                    alpha = h.alpha;
+                    v0 = h.v0;
+                    tau = h.tau;
                     DSTAMP(42)
                 }
             }
@@ -1588,25 +1556,8 @@ __device__ __forceinline__ void solve_one_compact(const GroupArgs<TI>& ga, const
 
     STAMP(16)
     // ---------------- phase 5: decode + write-out ----------------
-    // tau = h_a + M_a dv - J_a' f   (getActuatorForces)
-    if (!D.act_bounds) load_act_rows(); // (no actuation inequality rows: the decode is their only reader; the loads fly under the barrier and the x stores)
-    bsync();
-    TI* xo = ga.x + qp * n;
-    for (int i = tid; i < n; i += kThreads) xo[i] = (TI)c.x[i];
-    if (na > 0) {
-        TI* to = ga.tau + qp * na;
-        const TI hav = ga.h[qr * nv + nu + min(tid, na - 1)];
-        // tau' of the final iterate, from scratch (inside the loop it is carried by increments)
-        {
-            const double acc = act_dot(c, ar, c.x, c.z, 0.0);
-            if ((tid & 3) == 0 && (tid >> 2) < na) tact[tid >> 2] = acc;
-            bsync();
-        }
-        if (tid < na) to[tid] = (TI)((double)hav + tact[tid]);
-    }
-    if (ga.amask) // (the next tick's hint under WBCQP_FLAG_WARM_START)
-        write_active_mask(ga, qp, c, (status == HQP_OPTIMAL) && nin2 > 0 && tid < nin2 && act[tid] != 0);
-    write_results(ga, qp, c, status, D.max_iter - left, f_value);
+    if (!D.act_bounds) load_act_rows<SPEC>(c, S, pM, pAc, act_early, ar); // (no actuation inequality rows: the decode is their only reader; the loads fly under its barrier and the x stores)
+    decode_and_write(c, ga, ar, tact, act, qp, qr, status, D.max_iter - left, f_value);
 }
 
 #endif // __HIPCC__

@@ -234,6 +234,48 @@ __device__ __forceinline__ void solve_y(Ctx& c, double* rhs)
 // Returns false on (numerically) redundant equalities -- upstream's REDUNDANT_EQUALITIES.
 // Requires n <= 80, 1 <= m <= 22.
 // ------------------------------------------------------------------------------------------------
+// rhs_e = -(N(:,e)'x0 + ce0_e): 8 lanes per equality, ten terms each in flight
+template <typename Ce0>
+__device__ __forceinline__ void equality_rhs(Ctx& c, const double* Nm, double* rhs, Ce0 ce0_of)
+{
+    const int n = c.n, m = c.neq, ldb = c.ldb, e = c.tid >> 3, kc = c.tid & 7;
+    const int es = min(e, m - 1);
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int i = 0; i < 10; i += 2) {
+        const int k0 = min(kc + 8 * i, n - 1), k1 = min(kc + 8 * i + 8, n - 1);
+        const double x0 = (kc + 8 * i < n) ? c.x[k0] : 0.0, x1 = (kc + 8 * i + 8 < n) ? c.x[k1] : 0.0;
+        a0 = fma(Nm[k0 * ldb + es], x0, a0);
+        a1 = fma(Nm[k1 * ldb + es], x1, a1);
+    }
+    const double acc = grp8_sum(a0 + a1);
+    if (e < m && kc == 0) rhs[e] = -(acc + ce0_of(e));
+}
+// y = R'^-1 rhs on one wave | barrier | x = x0 + J[:, :m] y, f += y'y / 2 (a block reduction: two barriers), iq = m
+__device__ __forceinline__ void equality_y_and_x(Ctx& c, double* rhs, double& f_value)
+{
+    const int n = c.n, m = c.neq, ldj = c.ldj, tid = c.tid;
+    if (c.wave == 0) {
+        if (m <= 12) solve_y<12>(c, rhs);
+        else if (m <= 20) solve_y<20>(c, rhs);
+        else solve_y<24>(c, rhs);
+    }
+    bsync();
+    STAMP(19)
+    double yy = 0.0;
+    if (tid < m) yy = rhs[tid] * rhs[tid];
+    if (tid >= 128 && tid - 128 < n) {
+        const int kk = tid - 128;
+        const double* Jr = c.J + kk * ldj;
+        double acc = 0.0;
+        for (int e = 0; e < m; ++e) acc = fma(Jr[e], rhs[e], acc);
+        c.x[kk] += acc;
+    }
+    yy = block_sum(c, yy);
+    f_value += 0.5 * yy;
+    c.iq = m;
+}
+
 // build_n(Nm) writes N = CE' (n x m, leading dimension c.ldb) -- every thread calls it, a barrier follows; ce0_of(e) is ce0 of equality e
 template <typename BuildN, typename Ce0>
 __device__ __forceinline__ bool equality_phase_blocked_t(Ctx& c, double& f_value, BuildN build_n, Ce0 ce0_of)
@@ -248,23 +290,7 @@ __device__ __forceinline__ bool equality_phase_blocked_t(Ctx& c, double& f_value
     build_n(Nm);
     bsync();
     STAMP(21)
-    // ---- rhs_e = -(N(:,e)'x0 + ce0_e): 8 lanes per equality, ten terms each in flight
-    {
-        const int e = tid >> 3, kc = tid & 7;
-        const int es = min(e, m - 1);
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int i = 0; i < 10; i += 2) {
-            const int k0 = min(kc + 8 * i, n - 1), k1 = min(kc + 8 * i + 8, n - 1);
-            const double x0 = (kc + 8 * i < n) ? c.x[k0] : 0.0, x1 = (kc + 8 * i + 8 < n) ? c.x[k1] : 0.0;
-            a0 = fma(Nm[k0 * ldb + es], x0, a0);
-            a1 = fma(Nm[k1 * ldb + es], x1, a1);
-        }
-        const double acc = grp8_sum(a0 + a1);
-        if (e < m && kc == 0) {
-            rhs[e] = -(acc + ce0_of(e));
-        }
-    }
+    equality_rhs(c, Nm, rhs, ce0_of);
     STAMP(22)
     // ---- B = J0' N: item (pair of columns of J0, 4 equalities).  The k range is the same for the whole wave (J0 is upper
     //      triangular and block diagonal: whatever lies outside a lane's own range is an exact zero), so every J0 read is
@@ -295,29 +321,7 @@ __device__ __forceinline__ bool equality_phase_blocked_t(Ctx& c, double& f_value
     if (!qr_unified(c, Bm, c.s, c.s + 160)) return false; // redundant equalities
     bsync();
     STAMP(6)
-    // ---- y = R'^-1 rhs on one wave
-    if (c.wave == 0) {
-        if (m <= 12) solve_y<12>(c, rhs);
-        else if (m <= 20) solve_y<20>(c, rhs);
-        else solve_y<24>(c, rhs);
-    }
-    bsync();
-    STAMP(19)
-    // ---- x = x0 + J[:, :m] y ; f += y'y / 2
-    {
-        double yy = 0.0;
-        if (tid < m) yy = rhs[tid] * rhs[tid];
-        if (tid >= 128 && tid - 128 < n) {
-            const int kk = tid - 128;
-            const double* Jr = c.J + kk * ldj;
-            double acc = 0.0;
-            for (int e = 0; e < m; ++e) acc = fma(Jr[e], rhs[e], acc);
-            c.x[kk] += acc;
-        }
-        yy = block_sum(c, yy);
-        f_value += 0.5 * yy;
-    }
-    c.iq = m;
+    equality_y_and_x(c, rhs, f_value);
     bsync();
     return true;
 }
@@ -361,6 +365,48 @@ __device__ __forceinline__ bool equality_phase_blocked(Ctx& c, double& f_value)
     }
         },
         [&](int e) __attribute__((always_inline)) { return (e < c.nu) ? c.h[e] : -c.bc[e - c.nu]; });
+}
+
+// The compact layout's form: N = CE' already stands in the R region (Nm: phase 0 lands it there from the record's registers) and B = J0'N replaces it IN
+// PLACE -- every product is in registers before the first element is overwritten, one barrier more.  rhs holds ce0 on entry and y on return.
+// behind_qr() runs when the QR has released its registers, ahead of the barrier that publishes R: the compact body issues its actuation rows' global
+// loads there.  NTQ: row pairs per lane of the QR.  The last reduction's barrier is the phase's last: every read of J, R and y is behind it.
+template <int NTQ, typename BehindQr>
+__device__ __forceinline__ bool equality_phase_in_place(Ctx& c, double* Nm, double* rhs, double& f_value, BehindQr behind_qr)
+{
+    const int n = c.n, m = c.neq, nv = c.nv, ldj = c.ldj, ldb = c.ldb, tid = c.tid;
+    equality_rhs(c, Nm, rhs, [rhs](int e) __attribute__((always_inline)) { return rhs[e]; });
+    STAMP(22)
+    // ---- B = J0' N over N itself
+    {
+        const int ncg = (m + 3) >> 2;
+        const int cpi = tid / ncg, cg = tid - cpi * ncg;
+        const int c0 = 2 * cpi, c1i = min(c0 + 1, n - 1);
+        const bool actv = c0 < n;
+        int kmin = actv ? blk_begin(c0, nv) : n, kmax = actv ? c1i + 1 : 0;
+        kmin = wave_min_int(kmin);
+        kmax = wave_max_int(kmax);
+        double acc[2][4] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+        const int c0s = actv ? c0 : 0, c1s = actv ? c1i : 0;
+        tile2x4(c.J, c0s, c1s, ldj, Nm + 4 * cg, ldb, kmin, kmax, acc);
+        bsync();
+        if (actv) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (4 * cg + q < m) {
+                    Nm[c0 * ldb + 4 * cg + q] = acc[0][q];
+                    if (c0 + 1 < n) Nm[(c0 + 1) * ldb + 4 * cg + q] = acc[1][q];
+                }
+        }
+    }
+    bsync();
+    STAMP(5)
+    if (!qr_unified<NTQ>(c, Nm, c.s, c.s + 160)) return false; // redundant equalities
+    behind_qr();
+    bsync();
+    STAMP(6)
+    equality_y_and_x(c, rhs, f_value);
+    return true;
 }
 
 #endif // __HIPCC__

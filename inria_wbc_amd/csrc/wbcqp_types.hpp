@@ -29,6 +29,8 @@ enum VecSlot {
 constexpr int kIntA = 0, kIntAold = 128, kIntGskip = 256, kIntIai = 384, kIntIaexcl = 896, kIntMeta = 1408, kIntCount = 1920;
 // packed row descriptor: bits 0-1 kind, bit 2 negated copy (-A row), bits 3-10 local row, bits 11-14 contact, bits 15-22 column
 __host__ __device__ inline int row_meta_pack(int kind, int neg, int rr, int ct, int col) { return kind | (neg << 2) | (rr << 3) | (ct << 11) | (col << 15); }
+struct RowMeta { int kind; bool neg; int rr, ct, col; };
+__host__ __device__ inline RowMeta row_meta_unpack(int mt) { return {mt & 3, ((mt >> 2) & 1) != 0, (mt >> 3) & 255, (mt >> 11) & 15, (mt >> 15) & 255}; }
 
 enum { INEQ_BOUNDS = 0, INEQ_ACTUATION = 1, INEQ_FORCE = 2 };
 enum { HQP_UNKNOWN = -1, HQP_OPTIMAL = 0, HQP_INFEASIBLE = 1, HQP_UNBOUNDED = 2, HQP_MAX_ITER = 3, HQP_ERROR = 4 };
