@@ -66,7 +66,9 @@ extern "C" {
  *        ZMP force distributor); wbcqp_spd, wbcqp_mass_matrix, wbcqp_forward_dynamics, wbcqp_spd_commands and their _host forms (M(q), the
  *        accelerations joint torques produce, and the reference's stable-PD torque commands, on the device); wbcqp_reference_frame,
  *        wbcqp_jacobian_outputs, wbcqp_set_jacobian_frames, wbcqp_jacobians and wbcqp_jacobians_host (frame Jacobians, the CoM Jacobian, the
- *        centroidal momentum matrix and their drift terms, on the device).  151 therefore names more than one set of declarations: every one of them
+ *        centroidal momentum matrix and their drift terms, on the device); wbcqp_hessian_outputs, wbcqp_kinematic_hessians and
+ *        wbcqp_kinematic_hessians_host (the frames' kinematic Hessians dJ/dq and the Jacobians' time variation, on the device).  151 therefore
+ *        names more than one set of declarations: every one of them
  *        contains the one before it unchanged (nothing was removed or resized), so a caller checks for a symbol, not for the number
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
@@ -831,6 +833,45 @@ int wbcqp_jacobians(wbcqp_handle* handle, int slot, int batch, const void* q, co
 /* Same with HOST pointers: stage through device buffers owned by the handle, block until done. */
 int wbcqp_jacobians_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, int reference_frame,
                          const wbcqp_jacobian_outputs* out);
+
+/* ---- How a fleet's frame Jacobians change: kinematic Hessians dJ/dq and the Jacobians' time variation ----
+ * What the reference's RobotModel::update(..., update_jacobians = true) fills with computeJointKinematicHessians and hands out as
+ * RobotModel::hessian(name, reference_frame) (include/inria_wbc/utils/robot_model.hpp:61; src/utils/robot_model.cpp:92-98, 128-135), and
+ * pinocchio's getFrameJacobianTimeVariation, for a whole fleet.  One wavefront per instance (hessian_kernel, csrc/wbcqp_hessians.hpp), no
+ * atomics, every sum in a fixed order, an instance's result depends on its own rows alone: the same bits from run to run and at whatever index
+ * or batch size the rows arrive.  The slot needs a model and a selection of frames (wbcqp_set_jacobian_frames: the frames of wbcqp_jacobians' J,
+ * no selection of its own).
+ *
+ * For a selected frame f in the convention reference_frame, J is exactly what wbcqp_jacobians returns (rows linear then angular, a floating
+ * base's six columns in the base's own axes).  Each member of wbcqp_hessian_outputs may be NULL; what is given is written whole, nothing else:
+ *   H   [batch][n_frames][6][nv][nv]  H[b][f][r][j][k] = d J[b][f][r][j] / d q_k, k fastest: pinocchio's Tensor3x (6, nv, nv).  d/dq_k is the
+ *                                     derivative along dof k in the tangent space, d/de at e = 0 of J(q (+) e e_k) with the SE(3) integration
+ *                                     of wbcqp_integrate; that fixes the free-flyer's own 6 x 6 block.
+ *   dJ  [batch][n_frames][6][nv]      dJ[b][f][r][j] = sum_k H[b][f][r][j][k] v_k: dJ/dt along v, pinocchio's getFrameJacobianTimeVariation.
+ *                                     Needs v.  Formed from the bodies' velocities, not from H: asking for dJ alone costs no H.
+ * With "k <= j" for "dof k's body is dof j's body or one of its ancestors" (two dofs of the free-flyer are each <= the other), J_j = (l_j, w_j)
+ * column j of J and x_m the motion cross product (l1, w1) x_m (l2, w2) = (w1 x l2 + l1 x w2, w1 x w2), H[.][.][.][j][k] is, where both j and k
+ * move the frame's body,
+ *   WBCQP_RF_WORLD                k <= j: J_k x_m J_j                 otherwise: +0.0
+ *   WBCQP_RF_LOCAL                k <= j: +0.0                        otherwise: J_j x_m J_k
+ *   WBCQP_RF_LOCAL_WORLD_ALIGNED  k <= j: (w_k x l_j, w_k x w_j)      otherwise: (w_j x l_k, +0.0)
+ * and +0.0 everywhere else.  Every such +0.0, and the entries k = j that are a vector's product with itself, are +0.0 bit for bit.
+ * dJ v is the frame's spatial acceleration at zero joint accelerations: in LOCAL_WORLD_ALIGNED it equals wbcqp_jacobians' drift, in LOCAL
+ * drift = dJ v + (w_f x l_f, 0) with (l_f, w_f) = J v.
+ * q [batch][nq]; v [batch][nv], or NULL when dJ is not asked for (v is not read then, and H has the bits of the call with v).  The arrays of a
+ * trace (wbcqp_trace.q / .v, [n_rec][batch][...]) pass as they are with batch = n_rec * batch.  H is large (6 nv^2 numbers per frame and robot:
+ * 120 KB for the Talos-like model, nv = 50): offsets are 64-bit, a call may write more than 4 GB.
+ * Refused with WBCQP_ERR_INVALID before anything is launched (nothing is written): a slot without a model, batch < 0, outputs NULL or both
+ * members NULL, an unknown reference_frame, no frames selected, dJ without v, q NULL (batch > 0).  batch == 0: WBCQP_OK, nothing launched. */
+typedef struct {
+    void *H, *dJ;
+} wbcqp_hessian_outputs;
+/* DEVICE pointers of the handle's dtype, asynchronous on `stream`, ordered like wbcqp_observe.  reference_frame: a wbcqp_reference_frame. */
+int wbcqp_kinematic_hessians(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, int reference_frame,
+                             const wbcqp_hessian_outputs* out, void* stream);
+/* Same with HOST pointers: stage through device buffers owned by the handle, block until done. */
+int wbcqp_kinematic_hessians_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, int reference_frame,
+                                  const wbcqp_hessian_outputs* out);
 
 /* ---- Did a robot hit something: model torques against measured torques over a stream of ticks ----
  * The reference's inria_wbc::safety::TorqueCollisionDetection (src/safety/torque_collision_detection.cpp) with the filters of

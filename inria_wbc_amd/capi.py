@@ -38,6 +38,7 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_mass_matrix", "wbcqp_mass_matrix_host", "wbcqp_forward_dynamics", "wbcqp_forward_dynamics_host",
            "wbcqp_spd_commands", "wbcqp_spd_commands_host",
            "wbcqp_set_jacobian_frames", "wbcqp_jacobians", "wbcqp_jacobians_host",
+           "wbcqp_kinematic_hessians", "wbcqp_kinematic_hessians_host",
            "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host",
            "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host",
            "wbcqp_set_force_references", "wbcqp_stabilize_zmp", "wbcqp_stabilize_zmp_host")
@@ -47,6 +48,11 @@ STAB_INPUTS = ("ref", "wrench", "com", "acom", "placement", "x_prev")  # the arr
 STAB_OUTPUTS = ("ref_out", "flags", "cop")  # what wbcqp_stabilize writes (wbcqp_stab_outputs)
 TORQUE_CHECKS = ("detected", "invalid", "discrepancy", "filtered", "first_tick", "n_detected")  # what wbcqp_detect_torque_collisions writes (wbcqp_torque_checks)
 JACOBIAN_OUTPUTS = ("J", "Jcom", "Ag", "drift", "dAgv")  # what wbcqp_jacobians writes (wbcqp_jacobian_outputs); per instance n_frames x 6 x nv, 3 x nv, 6 x nv, n_frames x 6, 6
+# what wbcqp_kinematic_hessians writes (wbcqp_hessian_outputs; per instance n_frames x 6 x nv x nv, n_frames x 6 x nv).  The names and the struct
+# are defined beside the numpy statement of the call and imported here: the one binding struct that lives outside this module.
+# tests/test_capi_binding.py fixes the number of structures THIS module defines (31) and checks their layouts, and existing tests stay as they
+# are; CHessianOutputs' layout is checked against the header in tests/test_hessians_host.py with the same function.
+from .hessians import OUTPUTS as HESSIAN_OUTPUTS, CHessianOutputs  # noqa: E402
 RF_WORLD, RF_LOCAL, RF_LOCAL_WORLD_ALIGNED = 0, 1, 2  # wbcqp_reference_frame: pinocchio's values
 COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
@@ -307,6 +313,7 @@ SIGNATURES = {
     "wbcqp_spd_commands": _sig(_vp, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp),
     "wbcqp_set_jacobian_frames": _sig(_vp, _int, _int, c_i32_p),
     "wbcqp_jacobians": _sig(_vp, _int, _int, _vp, _vp, _int, _p(CJacobianOutputs), _vp),
+    "wbcqp_kinematic_hessians": _sig(_vp, _int, _int, _vp, _vp, _int, _p(CHessianOutputs), _vp),
     "wbcqp_torque_monitor_state_bytes": _sig(_p(CTorqueMonitor), restype=C.c_int64),
     "wbcqp_detect_torque_collisions": _sig(_vp, _p(CTorqueMonitor), _int, _int, _vp, _int, _vp, _vp, _p(CTorqueChecks), _vp),
     "wbcqp_stabilizer_state_bytes": _sig(_p(CStabilizer), restype=C.c_int64),
@@ -316,7 +323,7 @@ SIGNATURES = {
 # the _host forms that are the device signature without the stream
 for _name in ("wbcqp_solve_batch", "wbcqp_integrate", "wbcqp_problem_data", "wbcqp_tick", "wbcqp_observe", "wbcqp_observe_acom",
               "wbcqp_check_collisions", "wbcqp_inverse_dynamics", "wbcqp_mass_matrix", "wbcqp_forward_dynamics", "wbcqp_spd_commands",
-              "wbcqp_jacobians", "wbcqp_detect_torque_collisions", "wbcqp_stabilize", "wbcqp_stabilize_zmp"):
+              "wbcqp_jacobians", "wbcqp_kinematic_hessians", "wbcqp_detect_torque_collisions", "wbcqp_stabilize", "wbcqp_stabilize_zmp"):
     SIGNATURES[_name + "_host"] = (SIGNATURES[_name][0], SIGNATURES[_name][1][:-1])
 
 
@@ -818,6 +825,27 @@ class Handle:
                                  which)
         out = CJacobianOutputs(*ptrs)
         self._check(self.lib.wbcqp_jacobians_host(self._h, slot, B, q.ctypes.data, host_ptr(v), int(reference_frame), C.byref(out)))
+        return res
+
+    def kinematic_hessians(self, slot: int, batch: int, q, v=None, reference_frame: int = RF_LOCAL, H=None, dJ=None, stream: int = 0):
+        """The kinematic Hessians and the Jacobians' time variation of `batch` states on device tensors (wbcqp_kinematic_hessians), for the frames of
+        set_jacobian_frames: q [batch, nq], v [batch, nv] (None when dJ is not asked for); outputs, each optional: H [batch, n_frames, 6, nv, nv]
+        (H[b, f, r, j, k] = d J[b, f, r, j] / d q_k), dJ [batch, n_frames, 6, nv]."""
+        out = CHessianOutputs(*[dev_ptr_given(t) for t in (H, dJ)])
+        self._check(self.lib.wbcqp_kinematic_hessians(self._h, slot, int(batch), dev_ptr_given(q), dev_ptr_given(v), int(reference_frame),
+                                                      C.byref(out), C.c_void_p(stream)))
+
+    def kinematic_hessians_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, reference_frame: int = RF_LOCAL,
+                                which: Optional[Sequence[str]] = None) -> Dict[str, np.ndarray]:
+        """wbcqp_kinematic_hessians_host: a dict of the outputs named in `which` (of HESSIAN_OUTPUTS).  which None: H and, with v, dJ.  Sized from
+        what THIS Handle's set_jacobian_frames last selected on the slot (see observe_host)."""
+        q, v = self._host(q, v)
+        B, nv, nf, f = q.shape[0], self._nv(slot), self._companions_of(slot)["jacobian"], self.np_dtype
+        if which is None:
+            which = ["H"] + (["dJ"] if v is not None else [])
+        res, ptrs = host_outputs({"H": ((B, nf, 6, nv, nv), f), "dJ": ((B, nf, 6, nv), f)}, which)
+        out = CHessianOutputs(*ptrs)
+        self._check(self.lib.wbcqp_kinematic_hessians_host(self._h, slot, B, q.ctypes.data, host_ptr(v), int(reference_frame), C.byref(out)))
         return res
 
     def detect_torque_collisions(self, monitor, batch: int, n_ticks: int, tau_model, ldt: int, tau_sensor, state=None, detected=None, invalid=None,

@@ -138,6 +138,13 @@ namespace inria_wbc {
             {
                 IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
             }
+            // The kinematic Hessians dJ/dq and the Jacobians' time variation at the states q (and v, for dJ) -- wbcqp_kinematic_hessians_host.  H (null:
+            // not asked for): B x n*6*nv*nv for the n named frames in the convention reference_frame, each frame's [6][nv][nv] block as it is; dJ
+            // (null: not asked for; needs v): B x n*6*nv.  Only a source that holds a model can tell
+            virtual void hessians(const MatrixXd&, const MatrixXd*, const std::vector<std::string>&, int, MatrixXd*, MatrixXd*)
+            {
+                IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
+            }
             // the foot's own mass added to a measured wrench (robot_model.cpp:171-186 of the reference), per instance, at the states q: force -= m g
             // with m the mass of the body that carries ft_frame, torque += (ankle - sole) x force with the world positions of that body's joint
             // frame and of sole_frame.  Only a source that holds a model can tell
@@ -441,6 +448,22 @@ namespace inria_wbc {
                 return jac_ag_;
             }
 
+            // The reference's RobotModel::hessian(name, reference_frame) (src/utils/robot_model.cpp:128-135: pinocchio's getJointKinematicHessian)
+            // and the Jacobian's time variation (getFrameJacobianTimeVariation) for every instance at q_tsid() and the velocity beside it (dq(false) of an instance that is not latched): B x 6*nv*nv with
+            // instance i's tensor in row i as [6][nv][nv] (H[r][j][k] = d J[r][j] / d q_k, k fastest), and B x 6*nv with sum_k H[r][j][k] v_k
+            // row-major in row i.  Computed on the device (wbcqp_kinematic_hessians_host) when somebody asks and kept with the state like
+            // jacobian(); the frames are jacobian()'s selection, and a frame asked for the first time joins it.
+            MatrixXd hessian(const std::string& frame, ReferenceFrame rf = WORLD) const
+            {
+                const int at = _ensure_hessians(frame, rf, false);
+                return _observed_block(hes_H_[rf], at, 6 * v_tsid_.cols * v_tsid_.cols);
+            }
+            MatrixXd jacobian_time_variation(const std::string& frame, ReferenceFrame rf = WORLD) const
+            {
+                const int at = _ensure_hessians(frame, rf, true);
+                return _observed_block(hes_dJ_[rf], at, 6 * v_tsid_.cols);
+            }
+
             // The reference's self-collision check of the solver's own model (CONTROLLER.check_model_collisions, collision_path;
             // controller.hpp:148-150, collision_check.cpp), per instance, for the controller's CURRENT state: computed on the device
             // (wbcqp_check_collisions_host) and kept with the state like the observables above, so a tick or qp_step_back() refreshes it.
@@ -736,8 +759,7 @@ namespace inria_wbc {
                         added = true;
                     }
                 }
-                if (added)
-                    for (auto& c : self->jac_at_) c = ComputedAt{}; // (the selection grew: what is kept of every convention is the old one's)
+                if (added) self->_jacobian_selection_grew();
                 const ComputedAt& kept = frame ? jac_at_[rf] : jac_com_at_;
                 if (!kept.current(source_.get(), q_tsid_, nullptr)) {
                     self->jac_com_at_ = ComputedAt{};
@@ -757,6 +779,46 @@ namespace inria_wbc {
             std::vector<std::string> jac_names_;
             MatrixXd jac_J_[3], jac_com_, jac_ag_; // J: per convention
             ComputedAt jac_at_[3], jac_com_at_;    // the state (q alone) and the source they were made for
+            // (the selection grew: what is kept of every convention, Jacobians and Hessians alike, is the old selection's)
+            void _jacobian_selection_grew()
+            {
+                for (auto& c : jac_at_) c = ComputedAt{};
+                for (auto& c : hes_H_at_) c = ComputedAt{};
+                for (auto& c : hes_dJ_at_) c = ComputedAt{};
+            }
+
+            // the kinematic Hessians (time: false) or the Jacobians' time variation (time: true) of the current state for the frames of the
+            // Jacobians' selection, fetched on demand on the pattern of _ensure_jacobians.  Returns the frame's place in the selection
+            int _ensure_hessians(const std::string& frame, int rf, bool time) const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
+                IWBC_ASSERT(rf == WORLD || rf == LOCAL || rf == LOCAL_WORLD_ALIGNED, "unknown reference frame ", rf);
+                auto self = const_cast<Controller*>(this);
+                auto it = std::find(jac_names_.begin(), jac_names_.end(), frame);
+                const int at = (int)std::distance(jac_names_.begin(), it);
+                const bool added = it == jac_names_.end();
+                if (added) {
+                    self->jac_names_.push_back(frame);
+                    self->_jacobian_selection_grew();
+                }
+                ComputedAt& kept = time ? self->hes_dJ_at_[rf] : self->hes_H_at_[rf];
+                if (!kept.current(source_.get(), q_tsid_, time ? &v_tsid_ : nullptr)) {
+                    kept = ComputedAt{};
+                    try {
+                        self->source_->hessians(q_tsid_, time ? &v_tsid_ : nullptr, jac_names_, rf, time ? nullptr : &self->hes_H_[rf],
+                                                time ? &self->hes_dJ_[rf] : nullptr);
+                    }
+                    catch (...) {
+                        if (added) self->jac_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
+                        throw;
+                    }
+                    kept.set(source_.get(), q_tsid_, time ? &v_tsid_ : nullptr);
+                }
+                return at;
+            }
+            MatrixXd hes_H_[3], hes_dJ_[3];          // per convention
+            ComputedAt hes_H_at_[3], hes_dJ_at_[3];  // the state (H: q alone) and the source they were made for
 
             std::shared_ptr<ProblemSource> source_;
             const double* tick_references_ = nullptr; // [batch][nref] read by the next tick instead of the source's stored references (the stabiliser's ref_out)

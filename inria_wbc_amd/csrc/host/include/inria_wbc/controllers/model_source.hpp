@@ -409,6 +409,21 @@ namespace inria_wbc {
                 if (wbcqp_jacobians_host(handle_, slot_, batch_, q.data.data(), nullptr, reference_frame, &out) != WBCQP_OK)
                     IWBC_ERROR("wbcqp_jacobians_host failed: ", wbcqp_last_error(handle_));
             }
+            // wbcqp_kinematic_hessians_host on the slot in use, for the Jacobians' selection of frames
+            void hessians(const MatrixXd& q, const MatrixXd* v, const std::vector<std::string>& frames, int reference_frame, MatrixXd* H, MatrixXd* dJ) override
+            {
+                IWBC_ASSERT(cur_ && handle_, "ModelSource is not bound to a solver");
+                const int n = (int)frames.size(), nv = robot_->nv();
+                IWBC_ASSERT(q.rows == batch_ && q.cols == robot_->nq(), "one state row per instance");
+                IWBC_ASSERT(!v || (v->rows == batch_ && v->cols == nv), "one velocity row per instance");
+                IWBC_ASSERT(n <= WBCQP_MAX_JACOBIAN_FRAMES, "at most ", WBCQP_MAX_JACOBIAN_FRAMES, " frames can have a Jacobian");
+                select_frames(jacobian_frames_, frames, wbcqp_set_jacobian_frames, "wbcqp_set_jacobian_frames");
+                if (H) *H = MatrixXd(batch_, 6 * nv * nv * n);
+                if (dJ) *dJ = MatrixXd(batch_, 6 * nv * n);
+                const wbcqp_hessian_outputs out = {H ? H->data.data() : nullptr, dJ ? dJ->data.data() : nullptr};
+                if (wbcqp_kinematic_hessians_host(handle_, slot_, batch_, q.data.data(), v ? v->data.data() : nullptr, reference_frame, &out) != WBCQP_OK)
+                    IWBC_ERROR("wbcqp_kinematic_hessians_host failed: ", wbcqp_last_error(handle_));
+            }
             void add_foot_mass(const MatrixXd& q, const std::string& ft_frame, const std::string& sole_frame, MatrixXd& force, MatrixXd& torque) const override
             {
                 if (!robot_->existFrame(ft_frame)) IWBC_ERROR("Frame name ", ft_frame, "is not in model"); // robot_model.cpp:173-176

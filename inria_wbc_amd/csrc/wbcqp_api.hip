@@ -123,6 +123,7 @@ int wbcqp_create(const wbcqp_desc* desc, wbcqp_handle** out)
     h->n_cu = prop.multiProcessorCount;
     if (const char* pad = std::getenv("WBCQP_DEBUG_LDS_PAD")) h->lds_pad = std::atoi(pad);
     h->debug_launch = std::getenv("WBCQP_DEBUG_LAUNCH") != nullptr;
+    if (const char* shape = std::getenv("WBCQP_HESSIAN_STORE")) h->hessian_wide = !std::strcmp(shape, "wide");
     h->no_ffcache = std::getenv("WBCQP_DEBUG_NO_FFCACHE") != nullptr;
     if (const char* ch = std::getenv("WBCQP_REFPROG_CHUNK")) h->ref_chunk = std::max(1, std::min(std::atoi(ch), 4096));
     *out = h;
@@ -803,6 +804,31 @@ int wbcqp_jacobians_host(wbcqp_handle* h, int slot, int batch, const void* q, co
                  {-1, out->dAgv, B * 6 * es, 0}};
     return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
         return launch_jacobians(h, *s, batch, u[0], u[1], reference_frame, wbcqp_jacobian_outputs{d[0], d[1], d[2], d[3], d[4]}, nullptr);
+    });
+}
+
+int wbcqp_kinematic_hessians(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, int reference_frame, const wbcqp_hessian_outputs* out,
+                             void* stream)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_hessians(h, slot, batch, q, v, reference_frame, out, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_hessians(h, *s, batch, q, v, reference_frame, *out, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_kinematic_hessians_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, int reference_frame, const wbcqp_hessian_outputs* out)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_hessians(h, slot, batch, q, v, reference_frame, out, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv, nf = (size_t)s->jacobian.n;
+    // (v goes up only where the kernel reads it)
+    Arr up[2] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, out->dJ ? const_cast<void*>(v) : nullptr, B * nv * es, 0}};
+    Arr dn[2] = {{-1, out->H, B * nf * 6 * nv * nv * es, 0}, {-1, out->dJ, B * nf * 6 * nv * es, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_hessians(h, *s, batch, u[0], u[1], reference_frame, wbcqp_hessian_outputs{d[0], d[1]}, nullptr);
     });
 }
 

@@ -196,6 +196,7 @@ struct wbcqp_handle {
     wbcqp_dense_output dense_out{};
     int lds_pad = 0; // diagnostic (env WBCQP_DEBUG_LDS_PAD): extra dynamic LDS per workgroup, to force a lower residency
     bool debug_launch = false;                                   // env WBCQP_DEBUG_LAUNCH, read once at wbcqp_create (never on the per-tick path)
+    bool hessian_wide = false;                                   // env WBCQP_HESSIAN_STORE=wide, read once at wbcqp_create: hessian_kernel's second store shape
     bool no_ffcache = false;                                     // env WBCQP_DEBUG_NO_FFCACHE: every QP eliminates its force blocks itself (what tests compare the cache with)
     bool warned_occupancy = false;                               // the one-time note of launch() when the runtime's occupancy answer is overruled
     // wbcqp_rollout: sub-batches on streams of their own (each with its own launch-order state and queue counter), the record

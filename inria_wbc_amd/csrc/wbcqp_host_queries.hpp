@@ -1,13 +1,14 @@
 // wbcqp_host_queries.hpp -- host side of the model queries on a fleet's states (wbcqp_api.hip): wbcqp_observe, wbcqp_check_collisions and
 // wbcqp_inverse_dynamics, each with the set-up call that puts its table on the slot, and wbcqp_mass_matrix, wbcqp_forward_dynamics and
-// wbcqp_spd_commands (fdyn_kernel, csrc/wbcqp_fdyn.hpp, behind rnea_kernel for the bias) and wbcqp_jacobians (jacobian_kernel,
-// csrc/wbcqp_jacobians.hpp).  Per query: ONE check_* that the device-pointer and the
+// wbcqp_spd_commands (fdyn_kernel, csrc/wbcqp_fdyn.hpp, behind rnea_kernel for the bias), wbcqp_jacobians (jacobian_kernel,
+// csrc/wbcqp_jacobians.hpp) and wbcqp_kinematic_hessians (hessian_kernel, csrc/wbcqp_hessians.hpp).  Per query: ONE check_* that the device-pointer and the
 // host-pointer entry point share (nothing is staged or launched before it has passed) and ONE launch_* of its kernel (csrc/wbcqp_observe.hpp,
 // wbcqp_collide.hpp, wbcqp_rnea.hpp), one wavefront per instance.  Host code only; included by wbcqp_api.hip alone.
 #pragma once
 #include "wbcqp_host_handle.hpp"
 #include "wbcqp_fdyn.hpp"
 #include "wbcqp_jacobians.hpp"
+#include "wbcqp_hessians.hpp"
 
 namespace {
 
@@ -17,6 +18,7 @@ static_assert(kJacobianPerBlock == kRneaPerBlock && WBCQP_MAX_JACOBIAN_FRAMES ==
               "jacobian_kernel: the same instances per workgroup, one lane per selected frame");
 static_assert(WBCQP_RF_WORLD == kRfWorld && WBCQP_RF_LOCAL == kRfLocal && WBCQP_RF_LOCAL_WORLD_ALIGNED == kRfLocalWorldAligned,
               "the header and the kernel agree on the reference frames");
+static_assert(kHessianPerBlock == kRneaPerBlock, "hessian_kernel: the same instances per workgroup");
 static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
 
 // workgroups for `batch` instances at one wavefront each
@@ -383,6 +385,53 @@ int launch_jacobians(wbcqp_handle* h, const Slot& s, int batch, const void* q, c
         const JacobianArgs<TI> a{D, static_cast<const TI*>(q), (out.drift || out.dAgv) ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out.J),
                                  static_cast<TI*>(out.Jcom), static_cast<TI*>(out.Ag), static_cast<TI*>(out.drift), static_cast<TI*>(out.dAgv), rf, batch};
         hipLaunchKernelGGL(jacobian_kernel<TI>, dim3(query_blocks(batch)), dim3(kJacobianThreads), 0, stream, a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+// ---- second-order kinematics: wbcqp_kinematic_hessians -----------------------------------------------------------------------------------------------
+int check_hessians(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, int rf, const wbcqp_hessian_outputs* out, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "hessian outputs struct is NULL");
+    if (rf != WBCQP_RF_WORLD && rf != WBCQP_RF_LOCAL && rf != WBCQP_RF_LOCAL_WORLD_ALIGNED)
+        return fail(h, WBCQP_ERR_INVALID, "unknown reference_frame (WBCQP_RF_WORLD, WBCQP_RF_LOCAL or WBCQP_RF_LOCAL_WORLD_ALIGNED)");
+    if (!out->H && !out->dJ) return fail(h, WBCQP_ERR_INVALID, "every output is NULL: nothing is asked for");
+    if (sl->jacobian.n == 0) return fail(h, WBCQP_ERR_INVALID, "H / dJ asked for, but no frames are selected (wbcqp_set_jacobian_frames)");
+    if (out->dJ && !v) return fail(h, WBCQP_ERR_INVALID, "dJ asked for, but v is NULL");
+    if (batch == 0) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    *s = sl;
+    return WBCQP_OK;
+}
+
+// H's store shape.  One k per lane (narrow) everywhere, unless the handle was created with WBCQP_HESSIAN_STORE=wide in the environment AND nv is
+// even AND H is aligned to two elements: then two consecutive k per lane in one store of twice the width.  Narrow is the faster one; wide is kept
+// so that tools/hessians_bench.py can put the two side by side (profiles/hessians/INDEX.md has the figures)
+bool hessian_wide_stores(const wbcqp_handle* h, const void* H, int nv, size_t elem)
+{
+    return h->hessian_wide && H && !(nv & 1) && reinterpret_cast<uintptr_t>(H) % (2 * elem) == 0;
+}
+
+int launch_hessians(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, int rf, const wbcqp_hessian_outputs& out, hipStream_t stream)
+{
+    const TermsDev& T = s.terms;
+    const JacobianDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, T.ipool, T.dpool, T.i_jtype, T.i_last, T.i_idxq, T.i_idxv, T.i_anc, T.i_bodyof, T.i_kof,
+                        T.d_place, T.d_inertia, s.jacobian.n, s.jacobian.body, s.jacobian.place};
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        // (v goes to the kernel only where dJ is asked for: H has the bits of the call with v)
+        const HessianArgs<TI> a{D, static_cast<const TI*>(q), out.dJ ? static_cast<const TI*>(v) : nullptr, static_cast<TI*>(out.H), static_cast<TI*>(out.dJ),
+                                rf, batch};
+        if (hessian_wide_stores(h, out.H, T.nv, sizeof(TI)))
+            hipLaunchKernelGGL((hessian_kernel<TI, true>), dim3(query_blocks(batch)), dim3(kHessianThreads), 0, stream, a);
+        else
+            hipLaunchKernelGGL((hessian_kernel<TI, false>), dim3(query_blocks(batch)), dim3(kHessianThreads), 0, stream, a);
         HIP_TRY(h, hipGetLastError());
         return WBCQP_OK;
     });
