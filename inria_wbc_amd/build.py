@@ -72,6 +72,9 @@ def build_poison(verbose: bool = False, force: bool = False) -> str:
 
 
 HOST = os.path.join(CSRC, "host")
+# the model-query programs of the facade (host/tests/<name>.cpp), in build order
+FACADE_TESTS = ("observe_facade_test", "collision_facade_test", "inverse_dynamics_facade_test", "forward_dynamics_facade_test",
+                "jacobian_facade_test", "hessian_facade_test", "torque_collision_facade_test", "stabilizer_facade_test")
 
 
 def build_host(verbose: bool = False) -> dict:
@@ -81,14 +84,8 @@ def build_host(verbose: bool = False) -> dict:
     common = ["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-Wno-return-type", *inc]
     link = ["-L", LIBDIR, "-lwbcqp", "-Wl,-rpath," + LIBDIR]
     lib = os.path.join(LIBDIR, "libinria_wbc_hip.so")
-    out = {"lib": lib, "test_facade": os.path.join(LIBDIR, "test_facade"), "qp_timer_test": os.path.join(LIBDIR, "qp_timer_test"),
-           "observe_facade_test": os.path.join(LIBDIR, "observe_facade_test"), "collision_facade_test": os.path.join(LIBDIR, "collision_facade_test"),
-           "inverse_dynamics_facade_test": os.path.join(LIBDIR, "inverse_dynamics_facade_test"),
-           "forward_dynamics_facade_test": os.path.join(LIBDIR, "forward_dynamics_facade_test"),
-           "jacobian_facade_test": os.path.join(LIBDIR, "jacobian_facade_test"),
-           "hessian_facade_test": os.path.join(LIBDIR, "hessian_facade_test"),
-           "torque_collision_facade_test": os.path.join(LIBDIR, "torque_collision_facade_test"),
-           "stabilizer_facade_test": os.path.join(LIBDIR, "stabilizer_facade_test")}
+    programs = ("test_facade", "qp_timer_test") + FACADE_TESTS
+    out = {"lib": lib, **{name: os.path.join(LIBDIR, name) for name in programs}}
     # (nothing to do when the outputs are newer than every source of the facade, the C ABI header and the library)
     deps = [LIB, os.path.join(_HERE, "..", "include", "wbcqp.h"), os.path.abspath(__file__)]
     for root, _, files in os.walk(HOST):
@@ -97,22 +94,9 @@ def build_host(verbose: bool = False) -> dict:
         oldest = min(os.path.getmtime(o) for o in out.values())
         if all(os.path.getmtime(d) <= oldest for d in deps):
             return out
-    cmds = [
-        common + ["-fPIC", "-shared", os.path.join(HOST, "src", "registry.cpp"), "-o", lib] + link,
-        common + [os.path.join(HOST, "tests", "test_facade.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["test_facade"]] + link,
-        common + [os.path.join(HOST, "tests", "qp_timer_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["qp_timer_test"]] + link,
-        common + [os.path.join(HOST, "tests", "observe_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["observe_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "collision_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["collision_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "inverse_dynamics_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o",
-                  out["inverse_dynamics_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "forward_dynamics_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o",
-                  out["forward_dynamics_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "jacobian_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["jacobian_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "hessian_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["hessian_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "torque_collision_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o",
-                  out["torque_collision_facade_test"]] + link,
-        common + [os.path.join(HOST, "tests", "stabilizer_facade_test.cpp"), os.path.join(HOST, "src", "registry.cpp"), "-o", out["stabilizer_facade_test"]] + link,
-    ]
+    registry = os.path.join(HOST, "src", "registry.cpp")
+    cmds = [common + ["-fPIC", "-shared", registry, "-o", lib] + link]
+    cmds += [common + [os.path.join(HOST, "tests", name + ".cpp"), registry, "-o", out[name]] + link for name in programs]
     for cmd in cmds:
         if verbose:
             print(" ".join(cmd), file=sys.stderr)

@@ -100,76 +100,64 @@ namespace inria_wbc {
             virtual void set_contact_se3_ref(const std::string&, const std::vector<double>&) {}  // 12 numbers, or 24 with derivatives
             virtual const double* reference_data() const { return nullptr; }                   // [batch][nref] for wbcqp_tick_host
             virtual void fill_limits(const wbcqp_layout&, TickInputs&) const {}                // constant tlb / tub
+            // What a source without a model answers to a question only a model can answer: `who` is the asker with its verb.  The askers that
+            // Controller refuses itself as well (before it looks at an argument) are named here, so that each is spelled once
+            static constexpr const char *RNEA = "rnea_double_support needs", *INERTIA = "inertia_matrix needs", *FDYN = "forward_dynamics needs",
+                                        *SPD = "compute_spd needs", *JACOBIAN = "jacobian needs"; // (the Hessians ask in the Jacobians' name)
+            static std::string no_model(const char* who)
+            {
+                return detail::cat("this problem source has no model: ", who, " a model-driven source (CONTROLLER.model)");
+            }
             // where the robots are at the states (q, v): CoM and its velocity (B x 3 each), world placement (B x 12 n: rotation row-major, translation)
             // and local velocity (B x 6 n: linear, angular) of the n named model frames -- wbcqp_observe_host.  Only a source that holds a model can tell
             virtual void observe(const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, MatrixXd&, MatrixXd&, MatrixXd&, MatrixXd&)
-            {
-                IWBC_ERROR("this problem source has no model: com_now / model_frame_pos / model_frame_vel need a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model("com_now / model_frame_pos / model_frame_vel need")); }
             // tau (B x nv) = M(q) a + nle(q, v) - sum_k J_k' w_k for the n named model frames, wrenches B x 6 n (linear, angular in each frame's own
             // axes; n <= 8) -- wbcqp_inverse_dynamics_host.  Only a source that holds a model can tell
             virtual void inverse_dynamics(const MatrixXd&, const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, const MatrixXd&, MatrixXd&)
-            {
-                IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(RNEA)); }
             // M(q), B x nv*nv (row-major per instance, both triangles) -- wbcqp_mass_matrix_host.  Only a source that holds a model can tell
             virtual void mass_matrix(const MatrixXd&, MatrixXd&)
-            {
-                IWBC_ERROR("this problem source has no model: inertia_matrix needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(INERTIA)); }
             // a (B x nv) with (M(q) + diag(damping)) a = tau - nle(q, v) + sum_k J_k' w_k: tau B x nv (all dofs), the n named frames and their
             // wrenches as for inverse_dynamics, damping nv entries or none; info (B): 0, or k + 1 for a pivot that is not > 0 --
             // wbcqp_forward_dynamics_host.  Only a source that holds a model can tell
             virtual void forward_dynamics(const MatrixXd&, const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, const MatrixXd&,
                                           const std::vector<double>&, MatrixXd&, VectorXi&)
-            {
-                IWBC_ERROR("this problem source has no model: forward_dynamics needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(FDYN)); }
             // the reference's compute_spd (robot_dart/cmd.hpp:10-38) for every instance: commands B x nv from q, dq, the targets of the actuated
             // joints (the last na columns of targetpos), dt, kp, kd -- wbcqp_spd_commands_host.  Only a source that holds a model can tell
             virtual void spd_commands(const MatrixXd&, const MatrixXd&, const MatrixXd&, double, double, double, MatrixXd&)
-            {
-                IWBC_ERROR("this problem source has no model: compute_spd needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(SPD)); }
             // Frame Jacobians, the CoM Jacobian and the centroidal momentum matrix at the states q -- wbcqp_jacobians_host.  J (null: not asked for):
             // B x n*6*nv for the n named frames in the convention reference_frame (pinocchio's values: 0 WORLD, 1 LOCAL, 2 LOCAL_WORLD_ALIGNED),
             // each frame's 6 x nv block row-major; Jcom: B x 3*nv; Ag: B x 6*nv.  Only a source that holds a model can tell
             virtual void jacobians(const MatrixXd&, const std::vector<std::string>&, int, MatrixXd*, MatrixXd&, MatrixXd&)
-            {
-                IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(JACOBIAN)); }
             // The kinematic Hessians dJ/dq and the Jacobians' time variation at the states q (and v, for dJ) -- wbcqp_kinematic_hessians_host.  H (null:
             // not asked for): B x n*6*nv*nv for the n named frames in the convention reference_frame, each frame's [6][nv][nv] block as it is; dJ
             // (null: not asked for; needs v): B x n*6*nv.  Only a source that holds a model can tell
             virtual void hessians(const MatrixXd&, const MatrixXd*, const std::vector<std::string>&, int, MatrixXd*, MatrixXd*)
-            {
-                IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(JACOBIAN)); }
             // the foot's own mass added to a measured wrench (robot_model.cpp:171-186 of the reference), per instance, at the states q: force -= m g
             // with m the mass of the body that carries ft_frame, torque += (ankle - sole) x force with the world positions of that body's joint
             // frame and of sole_frame.  Only a source that holds a model can tell
             virtual void add_foot_mass(const MatrixXd&, const std::string&, const std::string&, MatrixXd&, MatrixXd&) const
-            {
-                IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model(RNEA)); }
             // One tick of the stabiliser (wbcqp_stabilize_host) on the source's stored references: com, acom and the two ankle frames are observed at
             // (q, v); wrench is B x 12 (lf_force, lf_torque, rf_force, rf_torque); feet_forces_prev: B x 24, the previous solution's point forces of
             // contact_lfoot then contact_rfoot, or null.  state: [B][wbcqp_stabilizer_state_bytes] bytes, sized and zeroed here when it does not fit.
             // ref_out [B][nref] is what the tick reads instead of the stored references, which are not touched.  Only a source with a model can
             virtual void stabilize(const StabilizerParams&, const MatrixXd&, const MatrixXd&, const MatrixXd&, const double*, std::vector<unsigned char>&,
                                    std::vector<double>&, VectorXi&, MatrixXd&)
-            {
-                IWBC_ERROR("this problem source has no model: the stabilizer needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model("the stabilizer needs")); }
             // whether the source holds a kinematic model (what observe() and check_collisions() need)
             virtual bool has_model() const { return false; }
             // self-collision of the sphere model in the collision file `file` (the reference's members: {member: {link: [[x, y, z, d], ...]}}) at
             // the states q: colliding (B: 1 / 0), first_pair (2 B: table indices of the pair the reference's loops meet first, -1 -1 without a hit)
             // and, per table entry, its (member, place inside the member) -- wbcqp_check_collisions_host.  Only a source that holds a model can tell
             virtual void check_collisions(const MatrixXd&, const std::string&, VectorXi&, VectorXi&, std::vector<std::pair<std::string, int>>&)
-            {
-                IWBC_ERROR("this problem source has no model: check_model_collisions needs a model-driven source (CONTROLLER.model)");
-            }
+            { IWBC_ERROR(no_model("check_model_collisions needs")); }
         };
 
         // "computed at this (source, q, v)": an answer a controller keeps WITH the state and the source it was made for, so whatever moves the
@@ -182,6 +170,28 @@ namespace inria_wbc {
                 return source && source == s && q.rows == qn.rows && q.data == qn.data && (!vn || v.data == vn->data);
             }
             void set(const ProblemSource* s, const MatrixXd& qn, const MatrixXd* vn) { source = s; q = qn; if (vn) v = *vn; }
+        };
+
+        // The model frames a controller has been asked about so far, in the order they joined: what goes to the source with every fetch
+        struct FrameSelection {
+            std::vector<std::string> names;
+            // fetch(joined) runs with `frame` in the selection -- joined: it was asked for the first time and has just been appended -- and a
+            // frame whose fetch throws (the model does not have it) does not stay.  Returns the frame's place
+            template <typename Fetch>
+            int with(const std::string& frame, Fetch&& fetch)
+            {
+                const int at = (int)std::distance(names.begin(), std::find(names.begin(), names.end(), frame));
+                const bool joined = at == (int)names.size();
+                if (joined) names.push_back(frame);
+                try {
+                    fetch(joined);
+                }
+                catch (...) {
+                    if (joined) names.pop_back();
+                    throw;
+                }
+                return at;
+            }
         };
 
         class Controller {
@@ -330,8 +340,7 @@ namespace inria_wbc {
             // the CoM as the problem source reports it (a model-driven source: the CoM at q0, filled once; com_now() below is the live one)
             void com(MatrixXd& pos, MatrixXd& vel) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                source_->com(pos, vel);
+                _source().com(pos, vel);
             }
             // Where the robots are NOW -- at the controller's current state (q_tsid(), dq(): after the last tick's integration), computed on the
             // device by wbcqp_observe_host when somebody asks and kept until the next tick: the batched counterparts of the reference's com() and
@@ -355,9 +364,7 @@ namespace inria_wbc {
             MatrixXd rnea_double_support(const SensorData& sensor_data, bool add_foot_mass, const std::string& left_ft_frame, const std::string& right_ft_frame,
                                          const std::string& left_sole_frame, const std::string& right_sole_frame) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (!source_->has_model())
-                    IWBC_ERROR("this problem source has no model: rnea_double_support needs a model-driven source (CONTROLLER.model)");
+                ProblemSource& source = _model_source(ProblemSource::RNEA);
                 if ((sensor_data.find("lf_force") == sensor_data.end()) || (sensor_data.find("rf_force") == sensor_data.end()) ||
                     (sensor_data.find("lf_torque") == sensor_data.end()) || (sensor_data.find("rf_torque") == sensor_data.end()))
                     throw IWBC_EXCEPTION("when FT is missing in fext_map"); // robot_model.cpp:161-163
@@ -373,8 +380,8 @@ namespace inria_wbc {
                 MatrixXd force[2] = {per_instance("lf_force"), per_instance("rf_force")}, torque[2] = {per_instance("lf_torque"), per_instance("rf_torque")};
                 std::vector<std::string> frames = {left_ft_frame, right_ft_frame};
                 if (add_foot_mass) {
-                    source_->add_foot_mass(q_tsid_, left_ft_frame, left_sole_frame, force[0], torque[0]);
-                    source_->add_foot_mass(q_tsid_, right_ft_frame, right_sole_frame, force[1], torque[1]);
+                    source.add_foot_mass(q_tsid_, left_ft_frame, left_sole_frame, force[0], torque[0]);
+                    source.add_foot_mass(q_tsid_, right_ft_frame, right_sole_frame, force[1], torque[1]);
                     frames = {left_sole_frame, right_sole_frame};
                 }
                 MatrixXd w(B, 12), a(B, nv), tau;
@@ -385,7 +392,7 @@ namespace inria_wbc {
                             w(i, 6 * k + 3 + d) = torque[k](i, d);
                         }
                 if (a_tsid_.rows == B && a_tsid_.cols == nv) a = a_tsid_; // (before the first tick: no acceleration yet)
-                source_->inverse_dynamics(q_tsid_, v_tsid_, a, frames, w, tau);
+                source.inverse_dynamics(q_tsid_, v_tsid_, a, frames, w, tau);
                 return tau;
             }
 
@@ -394,35 +401,25 @@ namespace inria_wbc {
             // state like com_now(): a tick, qp_step_back() or a new problem source makes the next call fetch again.
             const MatrixXd& inertia_matrix() const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: inertia_matrix needs a model-driven source (CONTROLLER.model)");
-                if (!mass_at_.current(source_.get(), q_tsid_, nullptr)) {
-                    auto self = const_cast<Controller*>(this);
-                    self->mass_at_ = ComputedAt{};
-                    self->source_->mass_matrix(q_tsid_, self->mass_);
-                    self->mass_at_.set(source_.get(), q_tsid_, nullptr);
-                }
+                ProblemSource& source = _model_source(ProblemSource::INERTIA);
+                _keep(mass_at_, nullptr, [&] { source.mass_matrix(q_tsid_, mass_); });
                 return mass_;
             }
             // The accelerations joint torques produce at the controller's current q_tsid(), dq(false): tau B x nv (all dofs; a floating base's six
             // first), no wrenches, no damping -- wbcqp_forward_dynamics_host.  info (B): 0, or k + 1 where the k-th pivot was not > 0.
             MatrixXd forward_dynamics(const MatrixXd& tau, VectorXi* info = nullptr) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: forward_dynamics needs a model-driven source (CONTROLLER.model)");
                 MatrixXd a;
                 VectorXi flags;
-                source_->forward_dynamics(q_tsid_, v_tsid_, tau, {}, MatrixXd(), {}, a, flags);
+                _model_source(ProblemSource::FDYN).forward_dynamics(q_tsid_, v_tsid_, tau, {}, MatrixXd(), {}, a, flags);
                 if (info) *info = flags;
                 return a;
             }
             // compute_spd of inria_wbc/robots/cmd.hpp goes through here: the states are the caller's (a simulator's), not the controller's
             MatrixXd spd_commands(const MatrixXd& q, const MatrixXd& dq, const MatrixXd& targetpos, double dt, double kp, double kd) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: compute_spd needs a model-driven source (CONTROLLER.model)");
                 MatrixXd commands;
-                source_->spd_commands(q, dq, targetpos, dt, kp, kd, commands);
+                _model_source(ProblemSource::SPD).spd_commands(q, dq, targetpos, dt, kp, kd, commands);
                 return commands;
             }
 
@@ -491,7 +488,7 @@ namespace inria_wbc {
             {
                 IWBC_ASSERT(src, "Invalid problem source");
                 if (check_model_collisions_ && !src->has_model())
-                    IWBC_ERROR("check_model_collisions is set, but this problem source has no model: the check needs a model-driven source (CONTROLLER.model)");
+                    IWBC_ERROR("check_model_collisions is set, but ", ProblemSource::no_model("the check needs"));
                 send_cmd_.clear();
                 col_at_ = ComputedAt{};
                 source_ = src;
@@ -650,27 +647,45 @@ namespace inria_wbc {
             MatrixXd _cmd(const MatrixXd& m, bool filter_mimics) const { return filter_mimics ? filter_cmd(m) : m; }
             bool _latched() const { return check_model_collisions_ && !send_cmd_.empty(); } // (before the first tick: the solver's state, as without the check)
 
-            // the collision answer of the current state, kept with the state and the source it was made for (the pattern of _ensure_observed)
+            // the source, or the words for there being none; with `who` asking (ProblemSource::no_model): a source that holds a model
+            ProblemSource& _source() const
+            {
+                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
+                return *source_;
+            }
+            ProblemSource& _model_source(const char* who) const
+            {
+                if (!_source().has_model()) IWBC_ERROR(ProblemSource::no_model(who));
+                return *source_;
+            }
+            // The rule of ComputedAt, once: an answer that is not current for (source_, q_tsid_, v) is fetched and marked.  The mark is cleared
+            // before the fetch, so a fetch that throws leaves nothing kept.  What is kept this way is mutable: the accessors that ask are const
+            template <typename Fetch>
+            void _keep(ComputedAt& kept, const MatrixXd* v, Fetch&& fetch) const
+            {
+                if (kept.current(source_.get(), q_tsid_, v)) return;
+                kept = ComputedAt{};
+                fetch();
+                kept.set(source_.get(), q_tsid_, v);
+            }
+
+            // the collision answer of the current state
             void _ensure_collisions() const
             {
-                auto self = const_cast<Controller*>(this);
                 if (!check_model_collisions_) {
-                    self->col_flags_.assign(batch_, 0);
+                    col_flags_.assign(batch_, 0);
                     return;
                 }
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (col_at_.current(source_.get(), q_tsid_, nullptr)) return;
-                self->col_at_ = ComputedAt{};
-                self->source_->check_collisions(q_tsid_, collision_file_, self->col_flags_, self->col_pairs_, self->col_names_);
-                self->col_at_.set(source_.get(), q_tsid_, nullptr);
+                ProblemSource& source = _source();
+                _keep(col_at_, nullptr, [&] { source.check_collisions(q_tsid_, collision_file_, col_flags_, col_pairs_, col_names_); });
             }
             bool check_model_collisions_ = false;
             std::string collision_file_;
             std::vector<int> send_cmd_; // per instance; empty until the first tick with the check on
             MatrixXd q_sent_, dq_sent_, ddq_sent_, tau_sent_;
-            VectorXi col_flags_, col_pairs_;
-            std::vector<std::pair<std::string, int>> col_names_;
-            ComputedAt col_at_; // the state (q alone) and the source the answer above was made for
+            mutable VectorXi col_flags_, col_pairs_;
+            mutable std::vector<std::pair<std::string, int>> col_names_;
+            mutable ComputedAt col_at_; // the state (q alone) and the source the answer above was made for
 
             bool verbose_ = false;
             double t_ = 0.0, dt_ = 0.001;
@@ -693,9 +708,8 @@ namespace inria_wbc {
             void _ensure_rows() const
             {
                 if (rows_valid_ || !source_ || in_.batch == 0) return;
-                auto self = const_cast<Controller*>(this);
-                self->source_->compute(t_ - dt_, last_q_, last_v_, _stack(), _layout(), self->in_);
-                self->rows_valid_ = true;
+                source_->compute(t_ - dt_, last_q_, last_v_, _stack(), _layout(), in_);
+                rows_valid_ = true;
             }
 
             // the observables of the current state, fetched on demand like the rows above: one wbcqp_observe_host per tick at the most (a frame
@@ -704,30 +718,14 @@ namespace inria_wbc {
             // Returns the frame's place in the selection (-1: none asked)
             int _ensure_observed(const std::string* frame) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                auto self = const_cast<Controller*>(this);
-                int at = -1;
-                bool added = false;
-                if (frame) {
-                    auto it = std::find(obs_names_.begin(), obs_names_.end(), *frame);
-                    at = (int)std::distance(obs_names_.begin(), it);
-                    if (it == obs_names_.end()) {
-                        self->obs_names_.push_back(*frame);
-                        added = true;
-                    }
-                }
-                if (added || !obs_at_.current(source_.get(), q_tsid_, &v_tsid_)) {
-                    self->obs_at_ = ComputedAt{};
-                    try {
-                        self->source_->observe(q_tsid_, v_tsid_, obs_names_, self->obs_com_, self->obs_vcom_, self->obs_place_, self->obs_vel_);
-                    }
-                    catch (...) {
-                        if (added) self->obs_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
-                        throw;
-                    }
-                    self->obs_at_.set(source_.get(), q_tsid_, &v_tsid_);
-                }
-                return at;
+                ProblemSource& source = _source();
+                auto fetch = [&](bool joined) {
+                    if (joined) obs_at_ = ComputedAt{};
+                    _keep(obs_at_, &v_tsid_, [&] { source.observe(q_tsid_, v_tsid_, obs_names_.names, obs_com_, obs_vcom_, obs_place_, obs_vel_); });
+                };
+                if (frame) return obs_names_.with(*frame, fetch);
+                fetch(false);
+                return -1;
             }
             static MatrixXd _observed_block(const MatrixXd& all, int at, int width)
             {
@@ -735,52 +733,41 @@ namespace inria_wbc {
                 for (int i = 0; i < all.rows; ++i) std::copy(all.row(i) + (size_t)at * width, all.row(i) + (size_t)(at + 1) * width, out.row(i));
                 return out;
             }
-            std::vector<std::string> obs_names_;
-            MatrixXd obs_com_, obs_vcom_, obs_place_, obs_vel_;
-            ComputedAt obs_at_; // the state and the source the four above were made for
-            MatrixXd mass_;
-            ComputedAt mass_at_; // the state (q alone) and the source mass_ was made for
+            mutable FrameSelection obs_names_;
+            mutable MatrixXd obs_com_, obs_vcom_, obs_place_, obs_vel_;
+            mutable ComputedAt obs_at_; // the state and the source the four above were made for
+            mutable MatrixXd mass_;
+            mutable ComputedAt mass_at_; // the state (q alone) and the source mass_ was made for
 
+            // who answers for Jacobians and Hessians in the convention rf
+            ProblemSource& _jacobian_source(int rf) const
+            {
+                ProblemSource& source = _model_source(ProblemSource::JACOBIAN);
+                IWBC_ASSERT(rf == WORLD || rf == LOCAL || rf == LOCAL_WORLD_ALIGNED, "unknown reference frame ", rf);
+                return source;
+            }
             // the Jacobians of the current state, fetched on demand on the pattern of _ensure_observed: J per convention for the frames asked for
             // so far, Jcom and Ag with whichever call comes first at a state.  Returns the frame's place in the selection (-1: none asked)
             int _ensure_jacobians(const std::string* frame, int rf) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
-                IWBC_ASSERT(rf == WORLD || rf == LOCAL || rf == LOCAL_WORLD_ALIGNED, "unknown reference frame ", rf);
-                auto self = const_cast<Controller*>(this);
-                int at = -1;
-                bool added = false;
-                if (frame) {
-                    auto it = std::find(jac_names_.begin(), jac_names_.end(), *frame);
-                    at = (int)std::distance(jac_names_.begin(), it);
-                    if (it == jac_names_.end()) {
-                        self->jac_names_.push_back(*frame);
-                        added = true;
-                    }
-                }
-                if (added) self->_jacobian_selection_grew();
-                const ComputedAt& kept = frame ? jac_at_[rf] : jac_com_at_;
-                if (!kept.current(source_.get(), q_tsid_, nullptr)) {
-                    self->jac_com_at_ = ComputedAt{};
-                    if (frame) self->jac_at_[rf] = ComputedAt{};
-                    try {
-                        self->source_->jacobians(q_tsid_, jac_names_, rf, frame ? &self->jac_J_[rf] : nullptr, self->jac_com_, self->jac_ag_);
-                    }
-                    catch (...) {
-                        if (added) self->jac_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
-                        throw;
-                    }
-                    self->jac_com_at_.set(source_.get(), q_tsid_, nullptr);
-                    if (frame) self->jac_at_[rf].set(source_.get(), q_tsid_, nullptr);
-                }
-                return at;
+                ProblemSource& source = _jacobian_source(rf);
+                auto fetch = [&](bool joined) {
+                    if (joined) _jacobian_selection_grew();
+                    _keep(frame ? jac_at_[rf] : jac_com_at_, nullptr, [&] {
+                        jac_com_at_ = ComputedAt{};
+                        source.jacobians(q_tsid_, jac_names_.names, rf, frame ? &jac_J_[rf] : nullptr, jac_com_, jac_ag_);
+                        jac_com_at_.set(source_.get(), q_tsid_, nullptr); // (Jcom and Ag come with every call)
+                    });
+                };
+                if (frame) return jac_names_.with(*frame, fetch);
+                fetch(false);
+                return -1;
             }
-            std::vector<std::string> jac_names_;
-            MatrixXd jac_J_[3], jac_com_, jac_ag_; // J: per convention
-            ComputedAt jac_at_[3], jac_com_at_;    // the state (q alone) and the source they were made for
+            mutable FrameSelection jac_names_;
+            mutable MatrixXd jac_J_[3], jac_com_, jac_ag_; // J: per convention
+            mutable ComputedAt jac_at_[3], jac_com_at_;    // the state (q alone) and the source they were made for
             // (the selection grew: what is kept of every convention, Jacobians and Hessians alike, is the old selection's)
-            void _jacobian_selection_grew()
+            void _jacobian_selection_grew() const
             {
                 for (auto& c : jac_at_) c = ComputedAt{};
                 for (auto& c : hes_H_at_) c = ComputedAt{};
@@ -791,40 +778,23 @@ namespace inria_wbc {
             // Jacobians' selection, fetched on demand on the pattern of _ensure_jacobians.  Returns the frame's place in the selection
             int _ensure_hessians(const std::string& frame, int rf, bool time) const
             {
-                IWBC_ASSERT(source_, "no problem source set (set_problem_source)");
-                if (!source_->has_model()) IWBC_ERROR("this problem source has no model: jacobian needs a model-driven source (CONTROLLER.model)");
-                IWBC_ASSERT(rf == WORLD || rf == LOCAL || rf == LOCAL_WORLD_ALIGNED, "unknown reference frame ", rf);
-                auto self = const_cast<Controller*>(this);
-                auto it = std::find(jac_names_.begin(), jac_names_.end(), frame);
-                const int at = (int)std::distance(jac_names_.begin(), it);
-                const bool added = it == jac_names_.end();
-                if (added) {
-                    self->jac_names_.push_back(frame);
-                    self->_jacobian_selection_grew();
-                }
-                ComputedAt& kept = time ? self->hes_dJ_at_[rf] : self->hes_H_at_[rf];
-                if (!kept.current(source_.get(), q_tsid_, time ? &v_tsid_ : nullptr)) {
-                    kept = ComputedAt{};
-                    try {
-                        self->source_->hessians(q_tsid_, time ? &v_tsid_ : nullptr, jac_names_, rf, time ? nullptr : &self->hes_H_[rf],
-                                                time ? &self->hes_dJ_[rf] : nullptr);
-                    }
-                    catch (...) {
-                        if (added) self->jac_names_.pop_back(); // (a frame the model does not have does not stay in the selection)
-                        throw;
-                    }
-                    kept.set(source_.get(), q_tsid_, time ? &v_tsid_ : nullptr);
-                }
-                return at;
+                ProblemSource& source = _jacobian_source(rf);
+                const MatrixXd* v = time ? &v_tsid_ : nullptr;
+                return jac_names_.with(frame, [&](bool joined) {
+                    if (joined) _jacobian_selection_grew();
+                    _keep(time ? hes_dJ_at_[rf] : hes_H_at_[rf], v, [&] {
+                        source.hessians(q_tsid_, v, jac_names_.names, rf, time ? nullptr : &hes_H_[rf], time ? &hes_dJ_[rf] : nullptr);
+                    });
+                });
             }
-            MatrixXd hes_H_[3], hes_dJ_[3];          // per convention
-            ComputedAt hes_H_at_[3], hes_dJ_at_[3];  // the state (H: q alone) and the source they were made for
+            mutable MatrixXd hes_H_[3], hes_dJ_[3];          // per convention
+            mutable ComputedAt hes_H_at_[3], hes_dJ_at_[3];  // the state (H: q alone) and the source they were made for
 
             std::shared_ptr<ProblemSource> source_;
             const double* tick_references_ = nullptr; // [batch][nref] read by the next tick instead of the source's stored references (the stabiliser's ref_out)
-            TickInputs in_;
+            mutable TickInputs in_; // (mutable with rows_valid_: _ensure_rows() fetches the rows for a const cost())
             MatrixXd last_q_, last_v_;
-            bool rows_valid_ = false;
+            mutable bool rows_valid_ = false;
             wbcqp_handle* handle_ = nullptr; // the reference's solver_ (controller.hpp:224)
         };
 

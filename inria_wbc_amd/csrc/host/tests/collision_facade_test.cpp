@@ -48,6 +48,7 @@ int main(int argc, char** argv)
         const double roll = std::atof(argv[7]);
         yaml::Node b_config = IWBC_CHECK(yaml::LoadFile(argv[2]));
         std::shared_ptr<controllers::Controller> ctl[2] = {make_controller(argv[1], B, argv[3]), make_controller(argv[1], B)};
+        std::shared_ptr<CountingSource> counting[2];
         std::vector<Tick> rec[2];
         std::vector<std::vector<int>> flags;
         MatrixXd q_start, zero_v;
@@ -55,6 +56,7 @@ int main(int argc, char** argv)
             auto pt = std::dynamic_pointer_cast<controllers::PosTracker>(ctl[c]);
             IWBC_ASSERT(pt && pt->robot(), "the controller must be a PosTracker with a model");
             IWBC_ASSERT(ctl[c]->check_model_collisions() == (c == 0), "CONTROLLER.check_model_collisions was not read");
+            counting[c] = count_device_calls(ctl[c], argv[1]);
             auto behavior = behaviors::Factory::instance().create(IWBC_CHECK(b_config["BEHAVIOR"]["name"].as<std::string>()), ctl[c], b_config);
             q_start = ctl[c]->q_tsid();
             zero_v = MatrixXd(B, ctl[c]->dq(false).cols);
@@ -119,6 +121,8 @@ int main(int argc, char** argv)
             f.write(reinterpret_cast<const char*>(&v), sizeof(double));
         }
         std::cout << "instances: " << B << std::endl;
+        std::cout << "device calls: " << counting[0]->calls() << std::endl;
+        std::cout << "device calls without the check: " << counting[1]->calls() << std::endl;
         std::cout << "hit seen after tick: " << hit << std::endl;
         std::cout << "others never collide: " << others_free << std::endl;
         std::cout << "commands frozen from the tick after the hit: " << frozen << std::endl;

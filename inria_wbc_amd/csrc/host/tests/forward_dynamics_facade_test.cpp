@@ -33,6 +33,7 @@ int main(int argc, char** argv)
         auto controller = make_controller(argv[1], std::atoi(argv[4]));
         auto pt = std::dynamic_pointer_cast<controllers::PosTracker>(controller);
         IWBC_ASSERT(pt && pt->robot(), "the controller must be a PosTracker with a model");
+        auto counting = count_device_calls(controller, argv[1]);
         yaml::Node b_config = IWBC_CHECK(yaml::LoadFile(argv[2]));
         auto behavior = behaviors::Factory::instance().create(IWBC_CHECK(b_config["BEHAVIOR"]["name"].as<std::string>()), controller, b_config);
         const int n_ticks = std::atoi(argv[3]);
@@ -80,6 +81,7 @@ int main(int argc, char** argv)
         put(q); put(dq); put(M); put(target); put(cmd); put(tau); put(a);
         std::cout.precision(4);
         std::cout << "instances: " << B << std::endl;
+        std::cout << "device calls: " << counting->calls() << std::endl;
         std::cout << "kept: " << kept << " refreshed after qp_step_back: " << refreshed << std::endl;
         std::cout << "max |M - M'|: " << asym << std::endl;
         std::cout << "min M(j, j): " << diag_min << std::endl;

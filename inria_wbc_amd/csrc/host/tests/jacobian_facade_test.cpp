@@ -32,6 +32,7 @@ int main(int argc, char** argv)
         auto controller = make_controller(argv[1], std::atoi(argv[4]));
         auto pt = std::dynamic_pointer_cast<controllers::PosTracker>(controller);
         IWBC_ASSERT(pt && pt->robot(), "the controller must be a PosTracker with a model");
+        auto counting = count_device_calls(controller, argv[1]);
         yaml::Node b_config = IWBC_CHECK(yaml::LoadFile(argv[2]));
         auto behavior = behaviors::Factory::instance().create(IWBC_CHECK(b_config["BEHAVIOR"]["name"].as<std::string>()), controller, b_config);
         const int n_ticks = std::atoi(argv[3]);
@@ -77,6 +78,7 @@ int main(int argc, char** argv)
         put(q); put(Jw); put(Jl); put(Ja); put(J2); put(Jcom); put(Ag);
         std::cout.precision(6);
         std::cout << "instances: " << B << std::endl;
+        std::cout << "device calls: " << counting->calls() << std::endl;
         std::cout << "world is the default: " << world_is_default << std::endl;
         std::cout << "kept: " << kept << " refreshed after qp_step_back: " << refreshed << std::endl;
         std::cout << "a second frame leaves the first: " << first_stays << std::endl;

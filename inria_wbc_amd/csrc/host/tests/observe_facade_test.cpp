@@ -7,18 +7,6 @@
 //       a controller on a FileSource must refuse the three accessors (it has no model)
 #include "model_query_facade.hpp"
 
-// the controller's own kind of source, counting the trips to the device the accessors cause
-struct CountingSource : controllers::ModelSource {
-    using controllers::ModelSource::ModelSource;
-    int calls = 0;
-    void observe(const controllers::MatrixXd& q, const controllers::MatrixXd& v, const std::vector<std::string>& frames, controllers::MatrixXd& com,
-                 controllers::MatrixXd& vcom, controllers::MatrixXd& place, controllers::MatrixXd& vel) override
-    {
-        ++calls;
-        controllers::ModelSource::observe(q, v, frames, com, vcom, place, vel);
-    }
-};
-
 static int file_source_mode(char** argv)
 {
     auto controller = make_controller(argv[2], 0);
@@ -80,11 +68,11 @@ int main(int argc, char** argv)
         }
         // asked again within the tick: no further trip to the device (so far: com_now, then one per frame that joined the selection); a
         // frame the model does not have is refused without spoiling the selection
-        const int n_frames = argc - 6, calls_first = counting->calls;
+        const int n_frames = argc - 6, calls_first = counting->observe_calls;
         controllers::MatrixXd cn2, vn2;
         controller->com_now(cn2, vn2);
         for (int a = 6; a < argc; ++a) { controller->model_frame_pos(argv[a]); controller->model_frame_vel(argv[a]); }
-        const bool cached = calls_first == 1 + n_frames && counting->calls == calls_first && cn2.data == cn.data;
+        const bool cached = calls_first == 1 + n_frames && counting->observe_calls == calls_first && cn2.data == cn.data;
         bool unknown_refused = false;
         try { controller->model_frame_pos("no_such_frame"); } catch (std::exception&) { unknown_refused = true; }
         const bool still_works = controller->model_frame_pos(argv[6]).cols == 12;
@@ -92,7 +80,7 @@ int main(int argc, char** argv)
         behavior->update(controllers::SensorData{});
         controllers::MatrixXd c_after, v_after, c_back, v_back;
         controller->com_now(c_after, v_after);
-        const int calls_tick = counting->calls;
+        const int calls_tick = counting->observe_calls;
         controller->qp_step_back();
         controller->com_now(c_back, v_back);
         const auto P_back = controller->model_frame_pos(argv[6]);
@@ -107,7 +95,7 @@ int main(int argc, char** argv)
                 stepped = std::max(stepped, std::fabs(c_back(i, d) - c_after(i, d)));
             }
         }
-        const bool refetched = counting->calls == calls_tick + 1;
+        const bool refetched = counting->observe_calls == calls_tick + 1;
         // a controller put back to its start (a new problem source: _reset) answers for q0 again
         auto fresh = make_source<CountingSource>(*pt, argv[1]);
         controller->set_problem_source(fresh);
@@ -116,7 +104,7 @@ int main(int argc, char** argv)
         double dreset = 0.0;
         for (int i = 0; i < B; ++i)
             for (int d = 0; d < 3; ++d) dreset = std::max(dreset, std::fabs(c_reset(i, d) - c0(i, d)));
-        const bool same = cached && refetched && fresh->calls == 1;
+        const bool same = cached && refetched && fresh->observe_calls == 1;
         std::cout.precision(3);
         std::cout << "instances: " << B << std::endl;
         std::cout << "max |com_now - com()|: " << moved << std::endl;
@@ -125,8 +113,8 @@ int main(int argc, char** argv)
         std::cout << "max |com_now, model_frame_pos after qp_step_back - RobotWrapper at the restored q|: " << dback << std::endl;
         std::cout << "max |com_now after qp_step_back - com_now before it|: " << stepped << std::endl;
         std::cout << "max |com_now after a new problem source - com()|: " << dreset << std::endl;
-        std::cout << "device calls: " << calls_first << " for com_now and " << n_frames << " new frames, " << counting->calls - calls_tick
-                  << " after the step back, " << fresh->calls << " on the new source" << std::endl;
+        std::cout << "device calls: " << calls_first << " for com_now and " << n_frames << " new frames, " << counting->observe_calls - calls_tick
+                  << " after the step back, " << fresh->observe_calls << " on the new source" << std::endl;
         std::cout << "cached: " << same << " unknown frame refused: " << unknown_refused << " then still answering: " << still_works << std::endl;
         return (moved > 1e-9 && dcom <= 1e-10 && dpos <= 1e-10 && dback <= 1e-10 && stepped > 1e-9 && dreset <= 1e-10 && same && unknown_refused && still_works) ? 0 : 1;
     }

@@ -36,6 +36,10 @@ def test_one_of_eight_robots_collides_and_stops_sending(host_build, tmp_path):
                 "without the check q() is q_solver() and nothing collides", "send_cmd is 0 for k alone", "step back to the start frees everybody",
                 "step back with another instance driven names it alone"):
         assert lines[key] == "1", (key, r.stdout)
+    # trips to the device, counted in the problem source: the latch's check after each of the 6 ticks (is_model_colliding and collision_index
+    # after it: kept) and one after each of the two steps back; a controller without the check makes none
+    assert lines["device calls"] == "observe 0, check_collisions 8, mass_matrix 0, jacobians 0, hessians 0", r.stdout
+    assert lines["device calls without the check"] == "observe 0, check_collisions 0, mass_matrix 0, jacobians 0, hessians 0", r.stdout
     # the final state and flags against the numpy statement; the names against pair_names
     m = mdl.talos_like()
     t = collision.sphere_table(m, FIXTURE)

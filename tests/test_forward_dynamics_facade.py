@@ -30,6 +30,8 @@ def test_inertia_matrix_and_compute_spd_after_move_com(host_build, tmp_path):
     lines = dict(ln.split(": ", 1) for ln in r.stdout.splitlines() if ": " in ln)
     assert lines["instances"] == str(B)
     assert lines["kept"] == "1 refreshed after qp_step_back: 1", r.stdout
+    # trips to the device, counted in the problem source: inertia_matrix() asked three times at one state (1) and once after the step back (1)
+    assert lines["device calls"] == "observe 0, check_collisions 0, mass_matrix 2, jacobians 0, hessians 0", r.stdout
     assert float(lines["max |M - M'|"]) == 0.0 and float(lines["min M(j, j)"]) > 0.0
     assert float(lines["max |commands| on the base rows"]) == 0.0 and float(lines["max |commands| on the actuated rows"]) > 1.0
     assert lines["commands for nv-wide targets equal"] == "1"

@@ -31,6 +31,11 @@ def test_hessians_after_move_com(host_build, tmp_path):
     assert lines["instances"] == str(B)
     assert lines["world is the default"] == "1" and lines["refreshed after qp_step_back"] == "1", r.stdout
     assert lines["a second frame leaves the first"] == "1" and lines["an unknown frame is refused"] == "1"
+    # trips to the device, counted in the problem source.  Hessians: H of the first frame in three conventions (3; WORLD again: kept), dJ in
+    # three (3), the second frame's H and dJ in LOCAL (2; it joins and drops every kept J, H and dJ), the first frame's H and dJ in WORLD again
+    # (2; LOCAL's H came with the second), the unknown frame's refused call (1; it drops everything again) and H in WORLD after it (1), H and dJ
+    # in WORLD after the step back (2).  Jacobians: the first frame in LOCAL before the second frame joins and after (2)
+    assert lines["device calls"] == "observe 0, check_collisions 0, mass_matrix 0, jacobians 2, hessians 14", r.stdout
     assert float(lines["max |H v - dJ|"]) <= 1e-10 * max(1.0, float(lines["max |dJ|"])) and float(lines["max |dJ|"]) > 0.0
     m, st, tm = mq.talos_case()
     nv = m.nv

@@ -32,6 +32,10 @@ def test_jacobians_after_move_com(host_build, tmp_path):
     assert lines["world is the default"] == "1"
     assert lines["kept"] == "1 refreshed after qp_step_back: 1", r.stdout
     assert lines["a second frame leaves the first"] == "1" and lines["an unknown frame is refused"] == "1"
+    # trips to the device, counted in the problem source: the first frame in three conventions (3; WORLD again, Jcom and Ag twice: kept), the
+    # second frame in LOCAL (1; it drops every kept J), the first in WORLD again (1; LOCAL came with the second), the unknown frame's refused
+    # call (1; it drops every kept J and Jcom) and WORLD after it (1), WORLD after the step back (1; Ag comes with it)
+    assert lines["device calls"] == "observe 0, check_collisions 0, mass_matrix 0, jacobians 8, hessians 0", r.stdout
     assert float(lines["max |angular rows, aligned - world|"]) == 0.0
     m, st, tm = mq.talos_case()
     mass = float(m.inertia[:, 0].sum())

@@ -35,6 +35,7 @@ def test_com_now_and_model_frames_after_move_com(host_build, tmp_path):
     # asked twice in a tick: one trip to the device (counted in the problem source); after qp_step_back and after a new problem source the
     # accessors answer for the state the controller then holds
     assert lines["cached"] == "1 unknown frame refused: 1 then still answering: 1", r.stdout
+    assert lines["device calls"] == "%d for com_now and %d new frames, 1 after the step back, 1 on the new source" % (1 + len(FRAMES), len(FRAMES)), r.stdout
     assert float(lines["max |com_now, model_frame_pos after qp_step_back - RobotWrapper at the restored q|"]) <= 1e-10
     assert float(lines["max |com_now after qp_step_back - com_now before it|"]) > 1e-9
     assert float(lines["max |com_now after a new problem source - com()|"]) <= 1e-10
