@@ -855,7 +855,9 @@ int wbcqp_jacobians_host(wbcqp_handle* handle, int slot, int batch, const void* 
  *   WBCQP_RF_WORLD                k <= j: J_k x_m J_j                 otherwise: +0.0
  *   WBCQP_RF_LOCAL                k <= j: +0.0                        otherwise: J_j x_m J_k
  *   WBCQP_RF_LOCAL_WORLD_ALIGNED  k <= j: (w_k x l_j, w_k x w_j)      otherwise: (w_j x l_k, +0.0)
- * and +0.0 everywhere else.  Every such +0.0, and the entries k = j that are a vector's product with itself, are +0.0 bit for bit.
+ * and +0.0 everywhere else.  Every such +0.0, and the entries k = j that are a vector's product with itself, are +0.0 bit for bit; so are the
+ * free-flyer's translation and rotation along one axis of the base (dofs i and i + 3) against one another, the same vector twice: all six rows in
+ * WBCQP_RF_WORLD, the linear rows in WBCQP_RF_LOCAL_WORLD_ALIGNED (the base's axis does not move when the base turns about it).
  * dJ v is the frame's spatial acceleration at zero joint accelerations: in LOCAL_WORLD_ALIGNED it equals wbcqp_jacobians' drift, in LOCAL
  * drift = dJ v + (w_f x l_f, 0) with (l_f, w_f) = J v.
  * q [batch][nq]; v [batch][nv], or NULL when dJ is not asked for (v is not read then, and H has the bits of the call with v).  The arrays of a

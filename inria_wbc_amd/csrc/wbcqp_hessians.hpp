@@ -10,7 +10,10 @@
 //     WORLD                 k <= j: J_k x_m J_j                  otherwise: +0.0
 //     LOCAL                 k <= j: +0.0                         otherwise: J_j x_m J_k
 //     LOCAL_WORLD_ALIGNED   k <= j: (w_k x l_j, w_k x w_j)       otherwise: (w_j x l_k, +0.0)
-// and +0.0 everywhere else; every +0.0 is written as a zero, never left to a cross product that cancels (k = j included).  The dofs that move a
+// and +0.0 everywhere else; every +0.0 is written as a zero, never left to a cross product that cancels (k = j included).  So are the free-flyer's
+// TWINS, its translation and its rotation along one axis e of the base (dofs i and i + 3): both columns are made of the one vector R e, the product is
+// that vector's with itself (WORLD: all six rows, either order; LOCAL_WORLD_ALIGNED: the linear rows of j the translation, k the rotation) -- the
+// base's axis does not move when the base turns about it.  The dofs that move a
 // frame lie on one chain, so among them k <= j is bodyof(k) <= bodyof(j) (bodies are numbered with parents ahead of children).
 // dJ comes in O(1) per column from the bodies' spatial velocities V (world axes, about the world's origin), with D_j = V(frame's body) - V(bodyof(j))
 // the motion of what lies between dof j's body and the frame:
@@ -60,8 +63,9 @@ struct alignas(2 * sizeof(TI)) HessianPair {
 #ifdef __HIPCC__
 
 // H[.][0..6)[j][k] from column k = (lk, wk) and column j = (lj, wj) in the convention rf.  both: j and k move the frame's body; pre: k <= j;
-// diag: k == j.  Whatever the table of this file's head has as +0.0 comes out as a written zero
-__device__ __forceinline__ void hessian_entry(int rf, bool both, bool pre, bool diag, V3 lk, V3 wk, V3 lj, V3 wj, double* o)
+// diag: k == j; twin: k != j, the free-flyer's translation and rotation along one axis.  Whatever the table of this file's head has as +0.0 comes
+// out as a written zero
+__device__ __forceinline__ void hessian_entry(int rf, bool both, bool pre, bool diag, bool twin, V3 lk, V3 wk, V3 lj, V3 wj, double* o)
 {
     // LOCAL, and LOCAL_WORLD_ALIGNED under j: column j acts on column k; otherwise column k on column j
     const bool swap = rf == kRfLocal || (rf == kRfLocalWorldAligned && !pre);
@@ -69,11 +73,17 @@ __device__ __forceinline__ void hessian_entry(int rf, bool both, bool pre, bool 
     V3 lin = cross(aw, bl);
     const V3 ang = cross(aw, bw);
     if (rf != kRfLocalWorldAligned) lin = lin + cross(al, bw);
-    const bool above = pre && !diag;
-    const bool nzl = both && (rf == kRfWorld ? above : rf == kRfLocal ? !pre : true);
+    const bool above = pre && !diag && !twin;
+    const bool nzl = both && (rf == kRfWorld ? above : rf == kRfLocal ? !pre : !twin);
     const bool nza = both && (rf == kRfLocal ? !pre : above);
     o[0] = nzl ? lin.x : 0.0; o[1] = nzl ? lin.y : 0.0; o[2] = nzl ? lin.z : 0.0;
     o[3] = nza ? ang.x : 0.0; o[4] = nza ? ang.y : 0.0; o[5] = nza ? ang.z : 0.0;
+}
+
+// Two different dofs of one body are the free-flyer's (every other joint has one): twins where they lie three apart, v = (linear, angular)
+__device__ __forceinline__ bool hessian_twin(int bk, int bj, int k, int j)
+{
+    return bk == bj && (k - j == 3 || j - k == 3);
 }
 
 // Wide: H's stores.  false (what every call gets by itself: the faster one, profiles/hessians/INDEX.md): one k per lane.  true: two consecutive k
@@ -281,7 +291,7 @@ __global__ __launch_bounds__(kHessianThreads) void hessian_kernel(const HessianA
                     const int bjj = __builtin_amdgcn_readlane(bj, j);
                     const V3 lj = {bcast_lane(lin.x, j), bcast_lane(lin.y, j), bcast_lane(lin.z, j)};
                     const V3 wj = {bcast_lane(ang.x, j), bcast_lane(ang.y, j), bcast_lane(ang.z, j)};
-                    hessian_entry(rf, sup, bj <= bjj, lane == j, lin, ang, lj, wj, e);
+                    hessian_entry(rf, sup, bj <= bjj, lane == j, hessian_twin(bj, bjj, lane, j), lin, ang, lj, wj, e);
                 }
                 if (dof) {
 #pragma unroll
@@ -306,8 +316,8 @@ __global__ __launch_bounds__(kHessianThreads) void hessian_kernel(const HessianA
                     const int bjj = __builtin_amdgcn_readlane(bj, j);
                     const V3 lj = {bcast_lane(lin.x, j), bcast_lane(lin.y, j), bcast_lane(lin.z, j)};
                     const V3 wj = {bcast_lane(ang.x, j), bcast_lane(ang.y, j), bcast_lane(ang.z, j)};
-                    hessian_entry(rf, pairl && sup0, b0 <= bjj, k0 == j, l0, w0, lj, wj, e0);
-                    hessian_entry(rf, pairl && sup1, b1 <= bjj, k1 == j, l1, w1, lj, wj, e1);
+                    hessian_entry(rf, pairl && sup0, b0 <= bjj, k0 == j, hessian_twin(b0, bjj, k0, j), l0, w0, lj, wj, e0);
+                    hessian_entry(rf, pairl && sup1, b1 <= bjj, k1 == j, hessian_twin(b1, bjj, k1, j), l1, w1, lj, wj, e1);
                 }
                 if (pairl) {
 #pragma unroll

@@ -11,7 +11,9 @@ product (l1, w1) x_m (l2, w2) = (w1 x l2 + l1 x w2, w1 x w2).  Where both j and 
     LOCAL                 k <= j: +0.0                         otherwise: J_j x_m J_k
     LOCAL_WORLD_ALIGNED   k <= j: (w_k x l_j, w_k x w_j)       otherwise: (w_j x l_k, +0.0)
 
-and +0.0 everywhere else.  d/dq_k is the derivative along dof k in the tangent space, d/de at 0 of J(q (+) e e_k) with the SE(3) integration of
+and +0.0 everywhere else -- and for the free-flyer's TWINS, its translation and its rotation along one axis e of the base (dofs i and i + 3): both
+columns are made of the one vector R e, whose product with itself is written as +0.0 like the diagonal's (WORLD: all six rows, either order;
+LOCAL_WORLD_ALIGNED: the linear rows; the angular ones are a product with the translation's w = 0).  d/dq_k is the derivative along dof k in the tangent space, d/de at 0 of J(q (+) e e_k) with the SE(3) integration of
 the library: tests/test_hessians_host.py holds the table to central differences of jacobians.py.  dJ is formed from partial sums of v_k J_k
 along the chain, never from H.  Host code for tests and tools: the hot path is the HIP kernel.
 """
@@ -45,19 +47,26 @@ def moves(model: Model, frames: Sequence[int]) -> np.ndarray:
     return supports(model)[dof_bodies(model)[None, :], model.frame_body[frames][:, None]]
 
 
+def twins(model: Model) -> np.ndarray:
+    """[nv, nv] bool: the free-flyer's translation and rotation along one axis of the base.  Two different dofs that are each <= the other are the
+    free-flyer's (every other joint has one dof), v = (linear, angular): twins lie three apart."""
+    pre, d = precedes(model), np.arange(model.nv)
+    return pre & pre.T & (np.abs(d[:, None] - d[None, :]) == 3)
+
+
 def structure_masks(model: Model, frames: Sequence[int], reference_frame: int):
     """(lin, ang): [n_frames, nv, nv] bool, True where the table above has a cross product in H's linear and angular rows at (f, j, k); every
-    other element of H is +0.0.  The diagonal k = j is +0.0 too wherever the product is of a vector with itself."""
+    other element of H is +0.0.  The diagonal k = j is +0.0 too wherever the product is of a vector with itself, and so are the twins."""
     mv, pre = moves(model, frames), precedes(model)
     both = mv[:, :, None] & mv[:, None, :]
-    off = ~np.eye(model.nv, dtype=bool)
+    off = ~np.eye(model.nv, dtype=bool) & ~twins(model)
     if reference_frame == WORLD:
         lin = both & pre[None] & off[None]
         return lin, lin
     if reference_frame == LOCAL:
         lin = both & ~pre[None]
         return lin, lin
-    return both, both & pre[None] & off[None]
+    return both & ~twins(model)[None], both & pre[None] & off[None]
 
 
 def _cross(a: np.ndarray, b: np.ndarray) -> np.ndarray:

@@ -36,15 +36,33 @@ bodies of |Y_b about the origin|, entry by entry) |S_j| for M, the same with the
 one common origin and moves it to the point: a rotation's lever is then two, origin to joint and origin to point, each with its magnitude.  They are
 what a zero lever (local scale 0, an exact zero for a body-local recursion) and the rates cost a common-origin formulation (tests/test_gpu_rbd_exact.py).
 
+THE SECOND-ORDER KINEMATICS (what wbcqp_kinematic_hessians computes; fixtures of their own, <case>.hessians.npz, for hessian_frames(case)):
+  * H_world, H_local, H_lwa [states, frames, 6, nv, nv]: H[f, r, j, k] is the central difference (step STEP again) along dof k in the tangent space
+    of the frame's Jacobian entry J[f, r, j] in that convention, J being the central difference of the placement map above, formed anew at either
+    displaced configuration -- a nested difference: it rounds at 1e-80 / 1e-40 and is off by 1e-40, check_steps_hessians() halves either step;
+  * dJ_world, dJ_local, dJ_lwa [states, frames, 6, nv]: the same difference of J along the curve q (+) t v (a = 0), on its own -- H is not contracted;
+  * no table of cross products is used.  `scale` of an H entry is the motion cross product (l1, w1) x_m (l2, w2) = (w1 x l2 + l1 x w2, w1 x w2) of the
+    two columns' J_<c>.scale with every term of every component added; in LOCAL_WORLD_ALIGNED the linear rows have one term, not two: l_j = w_j x
+    (frame - joint j), a dof k of j's body or above it turns all of it (w_k x l_j), one under it moves the frame's origin alone (w_j x l_k);
+    `scale_world`: the same of the columns' scale_world.  dJ.scale = sum_k H.scale[..., j, k] |v_k|; dJ.scale_world is what
+    csrc/wbcqp_hessians.hpp sums, (|V|(frame's body) + |V|(bodyof(j))) x_m |S_j| about the world's origin, |V|(b) = sum over the chain to b of
+    |S_k| |v_k|, moved to the frame and turned with SR_frame' for LOCAL_WORLD_ALIGNED and LOCAL: the difference V(frame) - V(body) counts both;
+  * the STRUCTURAL ZEROS of H are decided from the values (dependence()): scale and scale_world are 0 where the exact value is under ZERO_REL of
+    its magnitude sum in every state of the case and in generic(case), a second model of generic geometry at a generic state -- there J[f, r, j]
+    does not depend on q_k at all.  The decision is made with exact_rotations: it is a statement about rigid bodies.  The fixture's value is 0 there
+    (with the tables' own rotations it is 1e-16 of the magnitude sum).  tests/test_rbd_exact_host.py asserts that inria_wbc_amd/hessians.py's
+    structure_masks says the same.
+
 The identities the statement is held to (tests/test_rbd_exact_host.py): M symmetric, (Ag of the first derivatives) v = the bodies' momenta on the curve,
 and v' nle(q, v, g = 0) = v' M_dot v / 2 -- the last with the tables' rotations orthogonalised in mpmath (exact_rotations), because it is an identity of
-rigid bodies and the tables' own rotations are orthogonal to 1e-16 only.
+rigid bodies and the tables' own rotations are orthogonal to 1e-16 only.  The second-order quantities: second_order_identities().
 
 Cases: the smallest at which the tree kernels can go wrong (CASES).  Their statements are committed under tests/golden/rbd_exact/ as compressed
-.npz: `python -m tests.rbd_exact --write` makes them.
+.npz: `python -m tests.rbd_exact --write` makes them, <case>.npz and <case>.hessians.npz.
 """
 from __future__ import annotations
 
+import copy
 import functools
 import os
 import sys
@@ -55,8 +73,9 @@ import mpmath as mp
 import numpy as np
 
 from inria_wbc_amd import model as mdl
-from tests.rbd_exact_cases import (CASES, EPS, FULL_ONLY, GOLDEN, K_ORACLE, NO_ORIGIN, ORIGINS, QUANTITIES, SMALL, TOTALS,  # noqa: F401
-                                   load, model, path, ratios, states, worst_ratio, wrench_frames)
+from tests.rbd_exact_cases import (CASES, CONVENTIONS, EPS, FULL_ONLY, GOLDEN, HESSIANS, K_ORACLE, NO_ORIGIN, ORIGINS, QUANTITIES,  # noqa: F401
+                                   RATES, SECOND_ORDER, SMALL, TOTALS, hessian_frames, hessians_path, load, load_hessians, model, path, ratios,
+                                   states, worst_ratio, wrench_frames)
 
 DPS = 80
 STEP = "1e-20"
@@ -314,11 +333,14 @@ def statement(m, q, v, a, wframes: Sequence[int], wrench, step: str = STEP, **kw
 
 
 def _statement(m, q, v, a, wframes: Sequence[int], wrench, step: str = STEP, want_M_only: bool = False, gravity: bool = True, shift=None,
-               raw: bool = False, exact_rotations: bool = False, origin: Optional[str] = None) -> Dict[str, np.ndarray]:
+               raw: bool = False, exact_rotations: bool = False, origin: Optional[str] = None, hessian_frames: Optional[Sequence[int]] = None,
+               step2: str = STEP, values: bool = True) -> Dict[str, np.ndarray]:
     """Every quantity of QUANTITIES for one state as float64 arrays: out[name], out[name + ".scale"] and, for TOTALS, out[name + ".scale_total"].
     wrench [len(wframes), 6]: linear, angular in the frames' own axes.  shift: evaluate at time `shift` of the curve that leaves q with the constant
     velocity v.  exact_rotations: the tables' rotations replaced by the nearest orthogonal matrices and the quaternion by the unit one, in mpmath
-    (what the identities of rigid bodies presume; the tables' own are orthogonal to 1e-16).  raw: also out[name + ".lo"], what rounding to float64 left of every value, and out["_mp"], M and nle as mpmath numbers."""
+    (what the identities of rigid bodies presume; the tables' own are orthogonal to 1e-16).  raw: also out[name + ".lo"], what rounding to float64 left of every value, and out["_mp"], M, nle, the frame Jacobians and the drifts as mpmath numbers.
+    hessian_frames: return _second_order's arrays for those frames instead (step2: the step of the difference of the Jacobian; values False: the
+    magnitude sums alone), as soon as the Jacobians and their scales stand."""
     mp.mp.dps = DPS
     T = _tables(m, exact_rotations)
     nb, nv, nf = T.nb, T.nv, T.nf
@@ -480,6 +502,9 @@ def _statement(m, q, v, a, wframes: Sequence[int], wrench, step: str = STEP, wan
                     Jval[name][f, i, j], Jscl[name][f, i, j] = val[i], scl[i]
     for k in Jval:
         put(k, Jval[k], Jscl[k])
+        keep[k] = Jval[k]
+    if hessian_frames is not None:
+        return _second_order(T, x0, loc0, vv, h, mp.mpf(step2), list(hessian_frames), Jscl, Sp, SZ, SRf, Spf, values)
     # Jcom, Ag
     Ag = [[zero] * nv for _ in range(6)]
     SAg = [[zero] * nv for _ in range(6)]
@@ -565,6 +590,7 @@ def _statement(m, q, v, a, wframes: Sequence[int], wrench, step: str = STEP, wan
     put("velocity", vel, svel)
     put("drift_local", dl, sdl)
     put("drift_lwa", dw, sdw)
+    keep["drift_local"], keep["drift_lwa"], keep["sdrift_local"], keep["sdrift_lwa"] = dl, dw, sdl, sdw
 
     def bodies(curve, acc_abs, grav):
         """Per body: (m c_dot, its scale, momentum rate (force, moment about the body's CoM), their scales, w, I_w w and scales)."""
@@ -640,6 +666,159 @@ def _statement(m, q, v, a, wframes: Sequence[int], wrench, step: str = STEP, wan
     return out
 
 
+def _compose(A, B):
+    """The placement A followed by B, each (R, p); None is the identity."""
+    if A is None or B is None:
+        return B if A is None else A
+    return _mm(A[0], B[0]), _add(_mv(A[0], B[1]), A[1])
+
+
+def _second_order(T, x0, loc0, vv, h, h2, frames, Jscl, Sp, SZ, SRf, Spf, values):
+    """The second-order kinematics of the frames `frames` for one state, as arrays of mpmath numbers: H_<c> [F, 6, nv, nv] and dJ_<c> [F, 6, nv]
+    (values: asked for), H_<c>.mag, the magnitude sums of H before the structural zeros are decided, and dJ_<c>.mag_world; c of CONVENTIONS.
+    h is the step of the Jacobian's own difference, h2 the step of the difference of the Jacobian.  Jscl: the Jacobians' scales of the pass
+    (the local ones, or those of a common origin)."""
+    nv, nF, zero = T.nv, len(frames), mp.mpf(0)
+    av = [abs(x) for x in vv]
+    zeros = [zero] * nv
+    out = {}
+    for c in CONVENTIONS:
+        out["H_%s.mag" % c] = np.full((nF, 6, nv, nv), zero, dtype=object)
+        out["dJ_%s.mag_world" % c] = np.full((nF, 6, nv), zero, dtype=object)
+        if values:
+            out["H_" + c], out["dJ_" + c] = np.full((nF, 6, nv, nv), zero, dtype=object), np.full((nF, 6, nv), zero, dtype=object)
+
+    def about_origin(k):
+        """|S_k|: the magnitudes of dof k's world column about the world's origin, (linear, angular)."""
+        a, kind, _ = T.dofs[k]
+        return (SZ[k], _zero3()) if kind in ("fl", "p") else (_cmag(Sp[a], SZ[k]), SZ[k])
+
+    def path_sum(body):
+        """|V|(body) = sum over the chain to the body of |S_k| |v_k|."""
+        lin, ang = _zero3(), _zero3()
+        for k in T.sup[body]:
+            sl, sw = about_origin(k)
+            lin, ang = _add(lin, _sc(av[k], sl)), _add(ang, _sc(av[k], sw))
+        return lin, ang
+
+    for fi, f in enumerate(frames):
+        b = T.fbody[f]
+        dofs = T.sup[b]
+        # ---- magnitudes: H from the two columns' scales, the motion cross product with every term of every component added ------------------
+        cols = {c: {j: [Jscl["J_" + c][f, r, j] for r in range(6)] for j in dofs} for c in CONVENTIONS}
+        for j in dofs:
+            for k in dofs:
+                for c in ("world", "local"):
+                    cj, ck = cols[c][j], cols[c][k]
+                    s = _add(_cmag(ck[3:], cj[:3]), _cmag(ck[:3], cj[3:])) + _cmag(ck[3:], cj[3:])
+                    for r in range(6):
+                        out["H_%s.mag" % c][fi, r, j, k] = s[r]
+                # world axes at the frame's origin: l_j = w_j x (frame - joint j).  A dof k of j's body or above it turns the whole of it,
+                # w_k x l_j; one under it moves the frame's origin alone, w_j x l_k; the angular rows are w_k x w_j either way, if anything
+                cj, ck = cols["lwa"][j], cols["lwa"][k]
+                s = (_cmag(ck[3:], cj[:3]) if T.dofs[k][0] <= T.dofs[j][0] else _cmag(cj[3:], ck[:3])) + _cmag(ck[3:], cj[3:])
+                for r in range(6):
+                    out["H_lwa.mag"][fi, r, j, k] = s[r]
+        # ---- dJ as an algorithm about the world's origin sums it: (|V|(frame's body) + |V|(bodyof(j))) x_m |S_j|, moved to the frame -----------
+        Vf = path_sum(b)
+        for j in dofs:
+            Vj = path_sum(T.dofs[j][0])
+            Wl, Ww = _add(Vf[0], Vj[0]), _add(Vf[1], Vj[1])
+            sl, sw = about_origin(j)
+            Yl, Yw = _add(_cmag(Ww, sl), _cmag(Wl, sw)), _cmag(Ww, sw)
+            at_frame = _add(Yl, _cmag(Yw, Spf[f]))
+            for c, s in (("world", Yl + Yw), ("lwa", at_frame + Yw), ("local", _mtv(SRf[f], at_frame) + _mtv(SRf[f], Yw))):
+                for r in range(6):
+                    out["dJ_%s.mag_world" % c][fi, r, j] = s[r]
+        if not values:
+            continue
+        # ---- values: differences of the frame's Jacobian, itself the difference of the placement map --------------------------------------------
+        chain = []
+        a = b
+        while a >= 0:
+            chain.append(a)
+            a = T.parent[a]
+        chain.reverse()
+        d = len(chain)
+        pos = {a: i for i, a in enumerate(chain)}
+        seg = [[None] * (d + 1) for _ in range(d + 1)]  # seg[i][j]: the chain's bodies i .. j - 1 as they stand, composed
+        for i in range(d):
+            acc = None
+            for i2 in range(i, d):
+                acc = _compose(acc, loc0[chain[i2]])
+                seg[i][i2 + 1] = acc
+
+        def placed(mods):
+            """The frame's body in the world with the local placements `mods` (place on the chain -> (R, p)) in place of those as they stand."""
+            acc, at = None, 0
+            for pz in sorted(mods):
+                acc = _compose(_compose(acc, seg[at][pz]), mods[pz])
+                at = pz + 1
+            return _compose(acc, seg[at][d])
+
+        plain = {}  # dof j moved alone, either way: its local placement, and that composed with the chain above it and with the chain under it
+
+        def alone(j, e):
+            if (j, e) not in plain:
+                bj, kind, kk = T.dofs[j]
+                L = T.local(bj, _moved(T, x0[bj], bj, kind, kk, e))
+                plain[(j, e)] = (L, _compose(seg[0][pos[bj]], L), _compose(L, seg[pos[bj] + 1][d]))
+            return plain[(j, e)]
+
+        def columns(over, mods, centre, j, one=None):
+            """Column j of the frame's Jacobian in the three conventions where the coordinates `over` (body -> coordinate; mods: their local
+            placements) replace those of the state: the module's central difference of the placement map along dof j, formed there.
+            one: where a single body is moved, its place on the chain and its local placement composed with the chain above and under it
+            (the same products as placed(), the shared ones formed once)."""
+            bj, kind, kk = T.dofs[j]
+            side = []
+            for e in (h, -h):
+                if bj in over:
+                    there = dict(mods)
+                    there[pos[bj]] = T.local(bj, _moved(T, over[bj], bj, kind, kk, e))
+                    side.append(placed(there))
+                elif one is not None:
+                    (pk, above, under), pj = one, pos[bj]
+                    side.append(_compose(_compose(above, seg[pk + 1][pj]), alone(j, e)[2]) if pj > pk else
+                                _compose(_compose(alone(j, e)[1], seg[pj + 1][pk]), under))
+                else:
+                    there = dict(mods)
+                    there[pos[bj]] = alone(j, e)[0]
+                    side.append(placed(there))
+            (Ra, pa), (Rb, pb) = side
+            Rc, pc = centre
+            dp, dR = _sc(1 / (2 * h), _sub(pa, pb)), _msc(1 / (2 * h), _msub(Ra, Rb))
+            lin, ang = _add(dp, _mv(dR, T.fp[f])), _vee(_mmt(dR, Rc))
+            Rf, pf = _mm(Rc, T.fR[f]), _add(_mv(Rc, T.fp[f]), pc)
+            return {"lwa": lin + ang, "local": _mtv(Rf, lin) + _mtv(Rf, ang), "world": _add(lin, _cross(pf, ang)) + ang}
+
+        for k in dofs:
+            bk, kind, kk = T.dofs[k]
+            side = []
+            for e in (h2, -h2):
+                xk = _moved(T, x0[bk], bk, kind, kk, e)
+                Lk, pk = T.local(bk, xk), pos[bk]
+                over, mods = {bk: xk}, {pk: Lk}
+                one = (pk, _compose(seg[0][pk], Lk), _compose(Lk, seg[pk + 1][d]))
+                centre = _compose(one[1], seg[pk + 1][d])
+                side.append({j: columns(over, mods, centre, j, one) for j in dofs})
+            for j in dofs:
+                for c in CONVENTIONS:
+                    for r in range(6):
+                        out["H_" + c][fi, r, j, k] = (side[0][j][c][r] - side[1][j][c][r]) / (2 * h2)
+        side = []
+        for t in (h2, -h2):
+            over = {a: _on_curve(T, x0[a], a, vv, zeros, t) for a in chain}
+            mods = {pos[a]: T.local(a, over[a]) for a in chain}
+            centre = placed(mods)
+            side.append({j: columns(over, mods, centre, j) for j in dofs})
+        for j in dofs:
+            for c in CONVENTIONS:
+                for r in range(6):
+                    out["dJ_" + c][fi, r, j] = (side[0][j][c][r] - side[1][j][c][r]) / (2 * h2)
+    return out
+
+
 def _orthogonal(R):
     """The orthogonal matrix nearest R (Newton's iteration for the polar factor)."""
     A = mp.matrix(R)
@@ -680,15 +859,174 @@ def computed(name) -> Dict[str, np.ndarray]:
     return compute(name)
 
 
-def check_steps(name) -> float:
-    """Halving the step moves no value by more than 1e-25 of its scale; returns the largest move over scale."""
-    a, b = compute(name, STEP, raw=True), compute(name, "5e-21", raw=True)
+def _moves(a, b, quantities) -> float:
     worst = 0.0
-    for k in QUANTITIES:
+    for k in quantities:
         s = a[k + ".scale"]
         with np.errstate(divide="ignore", invalid="ignore"):
             mv = np.where(s > 0, np.abs((a[k] - b[k]) + (a[k + ".lo"] - b[k + ".lo"])) / s, 0.0)
         worst = max(worst, float(mv.max()) if mv.size else 0.0)
+    return worst
+
+
+def check_steps(name) -> float:
+    """Halving the step moves no value by more than 1e-25 of its scale; returns the largest move over scale."""
+    worst = _moves(compute(name, STEP, raw=True), compute(name, "5e-21", raw=True), QUANTITIES)
+    assert worst <= 1e-25, (name, worst)
+    return worst
+
+
+# ---- the second-order kinematics of a case: H = dJ/dq and dJ/dt ------------------------------------------------------------------------------
+def second_order(m, q, v, frames, step: str = STEP, step2: str = STEP, **kw):
+    """_second_order for one state (the statement's first part runs ahead of it: placements, scales, the Jacobians)."""
+    return _statement(m, q, v, np.zeros(m.nv), [], None, step, hessian_frames=frames, step2=step2, **kw)
+
+
+def _floats(a):
+    return np.vectorize(float, otypes=[np.float64])(a)
+
+
+def generic(name):
+    """A second model and state for deciding the structural zeros: the case's tree with generic geometry, at a generic q and v.  Every frame is
+    off its body's origin and every link off its parent's by a generic vector, every placement's rotation is off the table's by a generic one
+    (exact_rotations takes the nearest orthogonal matrix).  What is zero there is zero because the Jacobian's entry does not depend on q_k; a
+    frame ON its joint's origin, parallel axes, an axis through the base's origin give zeros of the values that no dependence explains."""
+    m = copy.deepcopy(model(name))
+    rng = np.random.default_rng(19_000 + list(CASES).index(name))
+    sign = lambda shape: rng.choice([-1.0, 1.0], shape)  # noqa: E731
+    m.frame_placement[:, 9:] = rng.uniform(0.1, 0.4, (m.nframe, 3)) * sign((m.nframe, 3))
+    m.placement[:, 9:] = rng.uniform(0.1, 0.4, (m.nbody, 3)) * sign((m.nbody, 3))
+    m.frame_placement[:, :9] += rng.uniform(0.05, 0.2, (m.nframe, 9)) * sign((m.nframe, 9))
+    m.placement[:, :9] += rng.uniform(0.05, 0.2, (m.nbody, 9)) * sign((m.nbody, 9))
+    q = m.q0.copy()
+    q[m.nq - m.na:] += rng.uniform(-1.0, 1.0, m.na)
+    if m.floating_base:
+        q[0:3] = rng.uniform(0.5, 1.5, 3)
+        u = rng.standard_normal(4)
+        q[3:7] = u / np.linalg.norm(u)
+    return m, q, rng.uniform(0.5, 1.5, m.nv) * sign(m.nv)
+
+
+@functools.lru_cache(maxsize=None)
+def dependence(name) -> Dict[str, np.ndarray]:
+    """H_<c> -> [frames, 6, nv, nv] bool: True where the Jacobian's entry (f, r, j) depends on q_k.  Decided from the values alone: False where
+    the exact value is under ZERO_REL of its magnitude sum in every state of the case and in generic(name).  It is a statement about RIGID bodies,
+    so the tables' rotations are orthogonalised (exact_rotations, as for the energy identity): with the tables' own, orthogonal to 1e-16, such an
+    entry holds 1e-16 of its magnitude sum -- the relative placements between the two dofs do not quite drop out of R' R."""
+    s, frames = states(name), hessian_frames(name)
+    gm, gq, gv = generic(name)
+    passes = [second_order(model(name), s["q"][i], s["v"][i], frames, exact_rotations=True) for i in range(s["q"].shape[0])]
+    passes.append(second_order(gm, gq, gv, frames, exact_rotations=True))
+    out = {}
+    for k in HESSIANS:
+        seen = [(_floats(abs(r[k])), _floats(r[k + ".mag"])) for r in passes]
+        out[k] = np.any([(val > ZERO_REL * mag) & (mag > 0) for val, mag in seen], axis=0)
+        for val, mag in seen:  # decided with room: nothing lies between 1e-35 of its magnitude sum and ZERO_REL of it
+            assert not ((val > 1e-35 * mag) & (val <= ZERO_REL * mag)).any(), (name, k)
+    return out
+
+
+def compute_hessians(name, step: str = STEP, step2: str = STEP, raw: bool = False) -> Dict[str, np.ndarray]:
+    """The six second-order quantities of every state of a case, stacked, each with `scale` and `scale_world`; in.hessian_frames beside them.
+    raw: with what rounding left of every value (name + ".lo")."""
+    m, s, frames = model(name), states(name), hessian_frames(name)
+    n = s["q"].shape[0]
+    per = [second_order(m, s["q"][i], s["v"][i], frames, step, step2) for i in range(n)]
+    world = [second_order(m, s["q"][i], s["v"][i], frames, step, step2, origin="world", values=False) for i in range(n)]
+    dep = dependence(name)
+    out: Dict[str, np.ndarray] = {}
+
+    def put(k, val, scale, scale_world, tiny):
+        """Values outside the scale: zeros.  tiny: what the tables' rotations leave there, over the magnitude sum."""
+        (hi, lo) = _hi_lo(val)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            floor = 1e-30 * max(1.0, float(tiny.max()))  # (a difference of an exact zero is the differences' own rounding)
+            assert (np.abs(hi[scale == 0.0]) <= 1e-14 * tiny[scale == 0.0] + floor).all(), (name, k, "a structural zero has a value")
+            assert (np.abs(hi) <= scale * (1 + 1e-12))[scale > 0.0].all(), (name, k, "a value is larger than its magnitude sum")
+        assert (scale_world >= scale).all() or k in RATES, (name, k)
+        out[k], out[k + ".scale"], out[k + ".scale_world"] = np.where(scale > 0.0, hi, 0.0), scale, scale_world
+        if raw:
+            out[k + ".lo"] = np.where(scale > 0.0, lo, 0.0)
+
+    av = np.abs(s["v"])
+    for c in CONVENTIONS:
+        H, dJ = "H_" + c, "dJ_" + c
+        mag = np.stack([_floats(r[H + ".mag"]) for r in per])
+        mag_world = np.stack([_floats(r[H + ".mag"]) for r in world])
+        scale = np.where(dep[H][None], mag, 0.0)
+        put(H, np.stack([r[H] for r in per]), scale, np.where(dep[H][None], mag_world, 0.0), mag_world)
+        rate = np.zeros(scale.shape[:-1])
+        for k in range(m.nv):  # (one dof after the other: the same sum on every machine)
+            rate = rate + scale[..., k] * av[:, None, None, None, k]
+        rate_world = np.stack([_floats(r[dJ + ".mag_world"]) for r in per])
+        put(dJ, np.stack([r[dJ] for r in per]), rate, rate_world, rate_world)
+    out["in.hessian_frames"] = np.array(frames, dtype=np.int32)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def computed_hessians(name) -> Dict[str, np.ndarray]:
+    return compute_hessians(name)
+
+
+def second_order_identities(name, i: int = 0) -> Dict[str, float]:
+    """What ties the second-order quantities of state i to one another and to the first part of the statement, in mpmath, each as the largest
+    |defect| over the magnitude sum of what it compares:
+      * sum_k H[..., k] v_k = dJ in each convention (dJ is differenced along the curve, H along one dof at a time);
+      * dJ_lwa v = drift_lwa, the frames' classical acceleration at a = 0 of the statement's first part;
+      * dJ_local v + (w_f x l_f, 0) = drift_local, (l_f, w_f) = J_local v;
+      * in WORLD, H[j][k] - H[k][j] = J_k x_m J_j where dof k's body is above dof j's, the bracket of the two columns from J_world; and TWICE
+        that between two dofs of the free-flyer, each of which is <= the other (the base's own axes turn with it: d_k J_j = J_k x_m J_j both ways).
+    The first two hold for the tables as they are.  The last two are identities of RIGID bodies (R' R_dot is a cross product only where R is
+    orthogonal) and are formed with exact_rotations, as the energy identity is."""
+    m, s, frames = model(name), states(name), hessian_frames(name)
+    q, v = s["q"][i], s["v"][i]
+    vv = [_f(x) for x in v]
+    av = [abs(x) for x in vv]
+    nv, zero = m.nv, mp.mpf(0)
+    tiny = mp.mpf(10) ** -35  # (a difference of an exact zero is the differences' own rounding)
+    first = {x: _statement(m, q, v, np.zeros(nv), [], None, raw=True, exact_rotations=x)["_mp"] for x in (False, True)}
+    second = {x: second_order(m, q, v, frames, exact_rotations=x) for x in (False, True)}
+    worst, dofs = {}, _tables(m).dofs
+
+    def hold(what, defect, scale):
+        assert scale > 0 or abs(defect) <= tiny, (name, what)
+        worst[what] = max(worst.get(what, 0.0), float(abs(defect) / scale) if scale > 0 else 0.0)
+
+    for fi, f in enumerate(frames):
+        for c in CONVENTIONS:
+            H, Hs, dJ = second[False]["H_" + c][fi], second[False]["H_%s.mag" % c][fi], second[False]["dJ_" + c][fi]
+            for r in range(6):
+                for j in range(nv):
+                    hold("H v = dJ, " + c, sum((H[r, j, k] * vv[k] for k in range(nv)), zero) - dJ[r, j],
+                         sum((Hs[r, j, k] * av[k] for k in range(nv)), zero))
+        dJ = second[False]["dJ_lwa"][fi]
+        for r in range(6):
+            hold("dJ_lwa v = drift_lwa", sum((dJ[r, j] * vv[j] for j in range(nv)), zero) - first[False]["drift_lwa"][f][r],
+                 first[False]["sdrift_lwa"][f][r])
+        dJ, J = second[True]["dJ_local"][fi], first[True]["J_local"][f]
+        vf = [sum((J[r, j] * vv[j] for j in range(nv)), zero) for r in range(6)]
+        wl, swl = _cross(vf[3:], vf[:3]) + _zero3(), _cmag(_vabs(vf[3:]), _vabs(vf[:3])) + _zero3()
+        for r in range(6):
+            hold("dJ_local v + (w x l, 0) = drift_local", sum((dJ[r, j] * vv[j] for j in range(nv)), zero) + wl[r] - first[True]["drift_local"][f][r],
+                 first[True]["sdrift_local"][f][r] + swl[r])
+        H, Hs, J = second[True]["H_world"][fi], second[True]["H_world.mag"][fi], first[True]["J_world"][f]
+        for j in range(nv):
+            for k in range(j):
+                ck, cj = list(J[:, k]), list(J[:, j])
+                bracket = _add(_cross(ck[3:], cj[:3]), _cross(ck[:3], cj[3:])) + _cross(ck[3:], cj[3:])
+                twice = dofs[k][0] == dofs[j][0]
+                for r in range(6):
+                    hold("H_world[j][k] - H_world[k][j] = %sJ_k x_m J_j" % ("2 " if twice else ""),
+                         H[r, j, k] - H[r, k, j] - (2 if twice else 1) * bracket[r], Hs[r, j, k])
+    return worst
+
+
+def check_steps_hessians(name) -> float:
+    """check_steps for the second-order quantities: either step halved, the Jacobian's own and that of the difference of the Jacobian."""
+    a = compute_hessians(name, raw=True)
+    worst = max(_moves(a, compute_hessians(name, "5e-21", STEP, raw=True), SECOND_ORDER),
+                _moves(a, compute_hessians(name, STEP, "5e-21", raw=True), SECOND_ORDER))
     assert worst <= 1e-25, (name, worst)
     return worst
 
@@ -716,6 +1054,9 @@ def write(names: Optional[Sequence[str]] = None) -> None:
         t0 = time.time()
         np.savez_compressed(path(name), **{k: a for k, a in compute(name).items() if k not in CHECKS})  # values and scales only
         print("%-28s %6.1f s  %8d bytes" % (name, time.time() - t0, os.path.getsize(path(name))))
+        t0 = time.time()
+        np.savez_compressed(hessians_path(name), **compute_hessians(name))
+        print("%-28s %6.1f s  %8d bytes (second order)" % (name, time.time() - t0, os.path.getsize(hessians_path(name))))
 
 
 if __name__ == "__main__":

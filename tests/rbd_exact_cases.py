@@ -18,6 +18,10 @@ QUANTITIES = ("placement", "com", "J_world", "J_local", "J_lwa", "Jcom", "Ag", "
               "dAgv", "nle", "tau_a", "tau_aw")
 ORIGINS = ("world", "base")
 NO_ORIGIN = ("placement", "com", "nle", "tau_a", "tau_aw")  # computed directly, or held to scale_total: no scale_world / scale_base
+CONVENTIONS = ("world", "local", "lwa")  # wbcqp_reference_frame, as the Jacobians' names spell them
+HESSIANS = tuple("H_" + c for c in CONVENTIONS)   # [states, frames, 6, nv, nv]: d J[f, r, j] / d q_k
+RATES = tuple("dJ_" + c for c in CONVENTIONS)     # [states, frames, 6, nv]: d/dt of J along the curve that leaves q with the velocity v
+SECOND_ORDER = HESSIANS + RATES                   # fixtures of their own (<case>.hessians.npz), with scale and scale_world
 
 # K_ORACLE[quantity]: the worst ratio |x - value| / (eps scale) of the C oracle (rbd.rbd_terms, rbd.rnea) and of the numpy statements (observe,
 # jacobians, dynamics, forward_dynamics.mass_matrix) over all seven cases.  Measured 2026-10-20 with
@@ -27,7 +31,11 @@ K_ORACLE = {
     "placement": 1.19, "com": 1.83, "J_world": 95.9, "J_local": 4.74, "J_lwa": 95.9, "Jcom": 100.0, "Ag": 101.0, "M": 8.95, "velocity": 0.913,
     "vcom": 1.25, "Agv": 2.84, "drift_local": 0.575, "drift_lwa": 1.90, "acom": 0.696, "dAgv": 0.803, "nle": 1.80, "tau_a": 1.54, "tau_aw": 0.543,
 }
-assert set(K_ORACLE) == set(QUANTITIES)
+# The six second-order quantities: the worst ratio of inria_wbc_amd/hessians.py alone -- NO C oracle exists for them -- over all seven cases, H
+# against `scale`, dJ against `scale_world` (tests/test_gpu_rbd_exact.py says why).  Measured 2026-10-21 with the same command (37.6, 0.251, 10.5,
+# 0.996, 0.811, 0.996 on the line "K_ORACLE measured"), written rounded UP in the third digit.  Every one is under 256.
+K_ORACLE.update({"H_world": 37.7, "H_local": 0.252, "H_lwa": 10.6, "dJ_world": 0.997, "dJ_local": 0.812, "dJ_lwa": 0.997})
+assert set(K_ORACLE) == set(QUANTITIES) | set(SECOND_ORDER)
 
 
 # ---- cases -----------------------------------------------------------------------------------------------------------------------------------
@@ -94,6 +102,15 @@ def wrench_frames(name) -> List[int]:
     return _talos_wrench_frames(m) if name == "talos" else [2, 3, 1]  # two frames on one body, one on a leaf
 
 
+def hessian_frames(name) -> List[int]:
+    """The frames of the second-order quantities: every frame of the small cases (the root, a leaf and two frames on one body among them); Talos:
+    the wrench frames and one on the other arm; the 59-body tree: the root, the last body and two on one body."""
+    m = model(name)
+    if name == "talos":
+        return _talos_wrench_frames(m) + [m.frame("gripper_right_joint")]
+    return [0, 1, 2, 3] if name == "tree_59_floating" else list(range(m.nframe))
+
+
 @functools.lru_cache(maxsize=None)
 def states(name) -> Dict[str, np.ndarray]:
     """q within 0.5 of q0, v and a of order 1, a random unit quaternion as float64 rounds it, the base 1 to 3 m from the origin; wrenches of
@@ -115,9 +132,19 @@ def path(name):
     return os.path.join(GOLDEN, name + ".npz")
 
 
+def hessians_path(name):
+    return os.path.join(GOLDEN, name + ".hessians.npz")
+
+
 @functools.lru_cache(maxsize=None)
 def load(name) -> Dict[str, np.ndarray]:
     with np.load(path(name)) as z:
+        return {k: z[k] for k in z.files}
+
+
+@functools.lru_cache(maxsize=None)
+def load_hessians(name) -> Dict[str, np.ndarray]:
+    with np.load(hessians_path(name)) as z:
         return {k: z[k] for k in z.files}
 
 

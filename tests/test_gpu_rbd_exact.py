@@ -1,5 +1,6 @@
 """The tree kernels' rigid-body terms against the exact statement of tests/rbd_exact.py, ENTRY BY ENTRY: wbcqp_mass_matrix, wbcqp_jacobians,
-wbcqp_observe / wbcqp_observe_acom, wbcqp_inverse_dynamics and the rows kernel (wbcqp_problem_data: M, h, the contact Jacobians, the momentum).
+wbcqp_observe / wbcqp_observe_acom, wbcqp_inverse_dynamics, wbcqp_kinematic_hessians and the rows kernel (wbcqp_problem_data: M, h, the contact
+Jacobians, the momentum).
 
 The statement's values and scales are the committed fixtures (tests/golden/rbd_exact/): no mpmath runs here.  The bar of every entry is
     |x - value| <= REF_MULTIPLE K_ORACLE[quantity] eps scale,        a structural zero (scale 0): an exact zero,
@@ -20,6 +21,17 @@ sums with every rotation's lever split at the common origin the kernel forms its
     ov = R vJ + p x ow, hl = m ov + ow x hc): every term carries the origin's lever, and the scale is `scale_world` throughout.
 The multiple does not move and every entry is judged; the ratio against the local scale is printed.  The norm-wise bars of the other test_gpu_*.py
 modules stand as they are, next to these.
+
+wbcqp_kinematic_hessians (the fixtures <case>.hessians.npz: H = dJ/dq and dJ/dt in the three conventions) falls under the same two rules, read from
+csrc/wbcqp_hessians.hpp:
+  * H is a motion cross product of two columns that the kernel forms about the world's origin and moves to the frame ("2. lanes = dofs: lane j's
+    world column S_j = (v_j, w_j) about the world's origin", "4. ... lane j forms column j in the convention asked for"): a ZERO LEVER column is two
+    levers that cancel to rounding.  H is held to the local scale where it is not 0, to `scale_world` (the same cross product of the columns'
+    `scale_world`) where a zero lever leaves the local one 0, to an exact 0 where both are -- the zeros of the header's table, which the statement
+    decides from its own values (tests/rbd_exact.py, dependence);
+  * dJ is a RATE: "dJ comes in O(1) per column from the bodies' spatial velocities V (world axes, about the world's origin), with
+    D_j = V(frame's body) - V(bodyof(j))".  Both path sums hold the whole common ancestry, dof j's own term among it, which the difference and
+    S_j x_m S_j cancel to rounding only: `scale_world`, (|V|(frame's body) + |V|(bodyof(j))) x_m |S_j| moved to the frame, throughout.
 One launch per entry point (and Jacobian convention) and case, batch = the case's states."""
 import numpy as np
 import pytest
@@ -119,6 +131,20 @@ def test_inverse_dynamics(handle, name):
     got = {"nle": handle.inverse_dynamics_host(3, q, v), "tau_a": handle.inverse_dynamics_host(3, q, v, a),
            "tau_aw": handle.inverse_dynamics_host(3, q, v, a, wrench=w)}
     _judge("inverse_dynamics", name, [(k, got[k], C[k], C[k + ".scale_total"], C[k + ".scale"]) for k in ("nle", "tau_a", "tau_aw")])
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_kinematic_hessians(handle, name):
+    m, C = _set(handle, name)
+    S = X.load_hessians(name)
+    handle.set_jacobian_frames(3, [int(f) for f in S["in.hessian_frames"]])
+    q, v = C["in.q"], C["in.v"]
+    checks = []
+    for rf, c in ((capi.RF_WORLD, "world"), (capi.RF_LOCAL, "local"), (capi.RF_LOCAL_WORLD_ALIGNED, "lwa")):
+        got = handle.kinematic_hessians_host(3, q, v, rf)
+        checks.append(("H_" + c, got["H"], S["H_" + c], *_local(S, "H_" + c, "world")))
+        checks.append(("dJ_" + c, got["dJ"], S["dJ_" + c], *_rate(S, "dJ_" + c)))
+    _judge("kinematic_hessians", name, checks)
 
 
 def _stack(name, m):
