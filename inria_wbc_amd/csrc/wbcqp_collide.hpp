@@ -163,9 +163,7 @@ __global__ __launch_bounds__(kObserveThreads) void collide_kernel(const CollideA
             o[3] = __hiloint2double(S.tag[sl], __float_as_int(S.half[sl]));
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
 
     // ---- pair loop: lane = sphere i, j the same for the whole wave (a broadcast read) -------------------------------------------------
     if (args.colliding || args.first_pair || args.n_pairs || args.clearance) {

@@ -21,7 +21,7 @@
 //      not) ends the instance: info = k + 1 (LAPACK's potrf), the output row all NaN; no other instance notices.
 //   3. L y = b, L' a = y with lanes = rows (the running right-hand side stays in a register), then the epilogue.
 // Phases 2 and 3 round every product and every sum once (no contraction into fused multiply-adds).
-// LDS traffic inside the wave is ordered by the release fence / wave_barrier / acquire fence triple of stab_wave_sync and terms_kernel.
+// LDS traffic inside the wave is ordered by the wave_sync() of wbcqp_prims.hpp (release fence / wave_barrier / acquire fence), as in terms_kernel.
 #pragma once
 
 #include "wbcqp_rnea.hpp"
@@ -49,13 +49,6 @@ struct FdynArgs {
 };
 
 #ifdef __HIPCC__
-
-__device__ __forceinline__ void fdyn_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 template <typename TI, bool SPD>
 __global__ __launch_bounds__(kFdynThreads) void fdyn_kernel(const FdynArgs<TI> args)
@@ -236,7 +229,7 @@ __global__ __launch_bounds__(kFdynThreads) void fdyn_kernel(const FdynArgs<TI> a
             A[lane * ld + i] = mij;
         }
     }
-    fdyn_wave_sync();
+    wave_sync();
     if (args.M) {
         TI* gM = args.M + (size_t)inst * nv * nv;
         for (int r = 0; r < nv; ++r)
@@ -247,7 +240,7 @@ __global__ __launch_bounds__(kFdynThreads) void fdyn_kernel(const FdynArgs<TI> a
     {
 #pragma clang fp contract(off)
         if (dof) A[lane * ld + lane] = A[lane * ld + lane] + damp;
-        fdyn_wave_sync();
+        wave_sync();
         int failed = 0;
         const double* Ai = A + cj * ld;
         for (int k = 0; k < nv; ++k) {
@@ -261,7 +254,7 @@ __global__ __launch_bounds__(kFdynThreads) void fdyn_kernel(const FdynArgs<TI> a
             }
             const double r = sqrt(d);
             if (dof && lane >= k) A[lane * ld + k] = (lane == k) ? r : s / r;
-            fdyn_wave_sync();
+            wave_sync();
         }
         TI* gout = args.out + (size_t)inst * nv;
         TI* gqdd = (SPD && args.qddot) ? args.qddot + (size_t)inst * nv : nullptr;

@@ -239,9 +239,7 @@ __global__ __launch_bounds__(kObserveThreads) void observe_kernel(const ObserveA
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     // ---- lanes = output elements: element e of the instance's block from lane e % 64 ----------------------------------------------
     if (args.placement) {
         TI* out = args.placement + (size_t)inst * nf * 12;

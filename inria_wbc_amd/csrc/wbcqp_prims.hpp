@@ -25,6 +25,16 @@ __device__ __forceinline__ void bsync()
     __syncthreads();
 }
 
+// The hand-off inside ONE wave: lanes that wrote LDS (or memory) in one role read each other's values in the next.  Release fence,
+// s_wave_barrier (no instruction: it only keeps the compiler from moving code across), acquire fence -- no s_barrier, other waves
+// are not waited for.
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <int CTRL>
 __device__ __forceinline__ double dpp_mov(double v)
 {

@@ -141,13 +141,6 @@ __device__ inline double stab_normal_force(const double* n, const double* f12)
 
 __device__ inline bool stab_far(double x, double y) { return fabs(x) >= 10.0 && fabs(y) >= 10.0; }
 
-__device__ inline void stab_wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // block of patch element i (0 .. 128) and the block's first patch element
 __device__ inline int stab_block_of(int i) { return i < 9 ? 0 : 1 + (i - 9) / 24; }
 __device__ inline int stab_base_of(int b) { return b == 0 ? 0 : 9 + 24 * (b - 1); }
@@ -295,7 +288,7 @@ __global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabKe
     const double sample = ch == 0 ? craw[0] : ch == 1 ? craw[1] : ch == 2 ? lraw[0] : ch == 3 ? lraw[1] : ch == 4 ? rraw[0] : ch == 5 ? rraw[1] : ch == 6 ? lf[2] : rf[2];
     const bool push = fi == 0 ? has_b : fi == 1 ? has_l : fi == 2 ? has_r : fi == 3 ? load_l : load_r;
     const bool reset = (fi == 1 && !has_l) || (fi == 2 && !has_r);
-    stab_wave_sync(); // the ring and the patch are whole: from here on lane c touches column c of the ring alone
+    wave_sync(); // the ring and the patch are whole: from here on lane c touches column c of the ring alone
     double fv = 0.0;
     if (push && mine) {
         ring[head * kStabChannels + lane] = sample;
@@ -433,7 +426,7 @@ __global__ __launch_bounds__(kObserveThreads) void stabilize_kernel(const StabKe
             for (int k = 0; k < 9; ++k) torso[3 + k] = Rn[k];
         }
     }
-    stab_wave_sync(); // the patch is rewritten
+    wave_sync(); // the patch is rewritten
 
     // ---- 4. the outputs ---------------------------------------------------------------------------------------------------------------------
     if (args.ref_out) {

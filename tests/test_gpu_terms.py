@@ -8,6 +8,7 @@ import pytest
 
 from inria_wbc_amd import capi, structure
 from inria_wbc_amd import model as mdl
+from tests import sc_pair_cases
 from tests.util import assert_parity, device_outputs, host_outputs
 
 pytestmark = pytest.mark.gpu
@@ -70,10 +71,11 @@ def _cases():
                 node["joint"] = "f%d" % int(node["name"][-1])
         return m, st, mdl.build_taskmap(m, st, stack, dt=2e-3)
 
-    return {"talos": talos, "talos_torque_cop": talos_torque_cop, "talos_posture_mask": talos_posture_mask, "talos_single_support": talos_ss, "icub": icub, "franka": franka, "tree_fb": tree(21, 30, True), "tree_fixed": tree(22, 19, False), "tree_big": tree(23, 62, False), "tree_three_contacts": three_limbs}
+    return {"talos": talos, "talos_torque_cop": talos_torque_cop, "talos_posture_mask": talos_posture_mask, "talos_single_support": talos_ss, "icub": icub, "franka": franka, "tree_fb": tree(21, 30, True), "tree_fixed": tree(22, 19, False), "tree_big": tree(23, 62, False), "tree_three_contacts": three_limbs, "tree_65_pairs": sc_pair_cases.tree_65_pairs}
 
 
 CASES = _cases()
+BATCH = {"tree_65_pairs": sc_pair_cases.BATCH}  # every other case: 48 states
 
 
 @pytest.fixture(scope="module")
@@ -106,7 +108,7 @@ def test_problem_data_parity(handle, rbd, name):
     handle.set_structure(3, st)
     handle.set_model(3, m, tm)
     big = dict(q_noise=0.3, v_noise=0.5, ref_noise=0.2) if name.startswith("tree") else {}
-    s = mdl.sample_states(m, tm, 48, 31_000, **big)
+    s = mdl.sample_states(m, tm, BATCH.get(name, 48), 31_000, **big)
     dev = handle.problem_data_host(3, s["q"], s["v"], s["ref"])
     ora = rbd.task_rows(m, tm, st, s["q"], s["v"], s["ref"], n_threads=8)
     _compare(dev, ora)

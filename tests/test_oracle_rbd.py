@@ -281,6 +281,33 @@ def test_rows_golden(rbd, tag):
             assert np.abs(a - z[k]).max() <= 1e-12 * max(1.0, np.abs(z[k]).max()), k
 
 
+def test_pair_64_of_the_65_pair_case_is_active(rbd):
+    """tests/test_gpu_terms.py's case tree_65_pairs is there for the SECOND pass of the rows kernel's pair loop (64 pairs per pass).  It
+    reaches it only if the map holds 65 pairs over 18 distinct frames and pair 64 -- the last avoided frame of the last task -- is active:
+    its gradient moves the oracle's row of that task.  The oracle is asked twice, with and without that one pair; the row and its right-hand
+    side must differ by far more than the parity test's tolerance (1e-10 of an array's scale: the bar here is 1e-6, ten thousand times that) in at
+    least one of the three states the GPU test draws."""
+    import copy
+    from tests import sc_pair_cases
+    m, st, tm = sc_pair_cases.tree_65_pairs()
+    sc = [b for b in tm.blocks if b.kind == mdl.T_SELFCOLLISION]
+    assert m.nbody == 12 and not m.floating_base and len(sc) == 5 and [len(b.avoided) for b in sc] == [13] * 5
+    assert len({f for b in sc for f in [b.frame] + [a for a, _ in b.avoided]}) == 18
+    assert tm.blocks[-1] is sc[-1]  # pairs are numbered block by block: pair 64 is this block's last avoided frame
+    draw = dict(sc_pair_cases.STATES)
+    s = mdl.sample_states(m, tm, sc_pair_cases.BATCH, draw.pop("seed"), **draw)  # as test_problem_data_parity draws them
+    full = rbd.task_rows(m, tm, st, s["q"], s["v"], s["ref"])
+    less = copy.deepcopy(tm)
+    less.blocks[-1].avoided.pop()
+    without = rbd.task_rows(m, less, st, s["q"], s["v"], s["ref"])
+    row = st.n_dense - 1
+    dA = np.abs(full["A"].reshape(-1, st.n_dense, m.nv)[:, row] - without["A"].reshape(-1, st.n_dense, m.nv)[:, row]).max(axis=1)
+    db = np.abs(full["b1"][:, row] - without["b1"][:, row])
+    print("pair 64: |dA| per state", dA, " |db1|", db, " scales", np.abs(full["A"]).max(), np.abs(full["b1"]).max())
+    assert dA.max() > 1e-6 * max(1.0, np.abs(full["A"]).max())
+    assert db.max() > 1e-6 * max(1.0, np.abs(full["b1"]).max())
+
+
 def test_sample_states_do_not_depend_on_the_sharding():
     """Instance i of a stream depends on seed + i only: a rank that owns [lo, hi) draws exactly its slice."""
     m, st, tm = _talos_setup()

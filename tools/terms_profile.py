@@ -9,8 +9,14 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-NAMES = ["load state", "joint transform", "tree sweep", "inertia+scan", "task laws", "sc pairs", "posture/com/mom rhs", "S,F,h",
-         "M rows", "Jacobian rows", "com/mom/sc rows", "bounds+b1 store"]
+# what stamp i of csrc/wbcqp_terms.hpp brackets, by slot.  Slots 4 and 5 are the whole phases 1-2 of waves 1 and 2 (they run beside wave 0's
+# slots 1, 2, 3, 9); every other slot is wave 0's.  Wave 3 (posture, force references, joint bounds, two thirds of the Jacobian rows) has no stamp.
+NAMES = ["load state, barrier 0", "w0 joint_transform", "w0 sweep, path sums, kin", "w0 barrier 1, inertias, scan", "w1 tables, barrier 1, law_wave",
+         "w2 selfcollision_wave", "w0 wait at barrier 2", "totals, momentum out, S/F read", "mass_rows", "w0 column_S_F_h", "block_rows",
+         "last barrier, b1/bc store"]
+# Slots 3 and 9 changed meaning when the body was cut into functions: 3 used to run to the end of S/F/h and 9 bracketed nothing, so their figures are
+# not comparable with profiles taken before profiles/rows_body/; the other ten bracket what they always did.
+ORDER = [0, 1, 2, 3, 9, 4, 5, 6, 7, 8, 10, 11]  # wave 0 in time order, the two helper waves beside its phase 2
 
 
 def main():
@@ -58,8 +64,8 @@ def main():
     t = dbg.cpu().numpy().astype(np.float64)[:, :12]
     mean = t.mean(axis=0)
     print("batch %d: mean cycles per instance %.0f" % (B, mean.sum()))
-    for i, nm in enumerate(NAMES):
-        print("  %-22s %9.0f  %5.1f %%" % (nm, mean[i], 100 * mean[i] / mean.sum()))
+    for i in ORDER:
+        print("  %2d %-32s %9.0f  %5.1f %%" % (i, NAMES[i], mean[i], 100 * mean[i] / mean.sum()))
     h.close()
 
 
