@@ -67,8 +67,9 @@ extern "C" {
  *        accelerations joint torques produce, and the reference's stable-PD torque commands, on the device); wbcqp_reference_frame,
  *        wbcqp_jacobian_outputs, wbcqp_set_jacobian_frames, wbcqp_jacobians and wbcqp_jacobians_host (frame Jacobians, the CoM Jacobian, the
  *        centroidal momentum matrix and their drift terms, on the device); wbcqp_hessian_outputs, wbcqp_kinematic_hessians and
- *        wbcqp_kinematic_hessians_host (the frames' kinematic Hessians dJ/dq and the Jacobians' time variation, on the device).  151 therefore
- *        names more than one set of declarations: every one of them
+ *        wbcqp_kinematic_hessians_host (the frames' kinematic Hessians dJ/dq and the Jacobians' time variation, on the device);
+ *        wbcqp_id_derivative_outputs, wbcqp_inverse_dynamics_derivatives and wbcqp_inverse_dynamics_derivatives_host (dtau/dq and dtau/dv of the
+ *        inverse dynamics, on the device).  151 therefore names more than one set of declarations: every one of them
  *        contains the one before it unchanged (nothing was removed or resized), so a caller checks for a symbol, not for the number
  *   150  launch-order state per (handle, stream), active_mask written by every kernel, torque / cop task rows
  *        (wbcqp_structure.n_acteq, cop_*), posture mask
@@ -874,6 +875,39 @@ int wbcqp_kinematic_hessians(wbcqp_handle* handle, int slot, int batch, const vo
 /* Same with HOST pointers: stage through device buffers owned by the handle, block until done. */
 int wbcqp_kinematic_hessians_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, int reference_frame,
                                   const wbcqp_hessian_outputs* out);
+
+/* ---- How a fleet's joint torques change with the state: the derivatives of the inverse dynamics, dtau/dq and dtau/dv ----
+ * The linearisation of tau = M(q) a + nle(q, v) - sum_k J_k(q)' w_k (wbcqp_inverse_dynamics) in q and in v -- pinocchio's
+ * computeRNEADerivatives -- for a whole fleet: what MPC, DDP or iLQR on a recorded roll-out, a gain or stability analysis of the stable-PD law, the
+ * sensitivity of the torque-collision detector's model torque to encoder error and the gravity stiffness dg/dq (v = a = NULL) need; with
+ * wbcqp_mass_matrix, the forward dynamics' derivatives da/dq = -M^-1 dtau/dq.  One wavefront per instance (id_derivatives_kernel,
+ * csrc/wbcqp_idderiv.hpp), no atomics, every sum in a fixed order, an instance's result depends on its own rows alone: the same bits from run to
+ * run and at whatever index or batch size the rows arrive.  The slot needs a model.
+ *
+ * The inputs are exactly those of wbcqp_inverse_dynamics: q [batch][nq]; v [batch][nv] or NULL (zero); a: rows lda >= nv apart, or NULL (zero), so
+ * that a tick's or a trace's x passes as it lies; wrench [batch][n_frames][6] or NULL, acting at the frames of wbcqp_set_wrench_frames, linear
+ * then angular in each frame's OWN axes -- and held fixed in those axes while q varies.  Each member of wbcqp_id_derivative_outputs may be NULL;
+ * what is given is written whole, nothing else is touched, and asking for one costs none of the other's stores:
+ *   dtau_dq  [batch][nv][nv]  dtau_dq[b][i][j] = d tau_i / d q_j, j fastest.  d/dq_j is the derivative along dof j in the tangent space, d/de at
+ *                             e = 0 of tau(q (+) e e_j) with the SE(3) integration of wbcqp_integrate: the convention of wbcqp_kinematic_hessians.
+ *   dtau_dv  [batch][nv][nv]  dtau_dv[b][i][j] = d tau_i / d v_j.  Needs v.
+ * d tau / d a is M(q): wbcqp_mass_matrix gives it; it is no output here.
+ * Exact +0.0, bit for bit: every entry whose two dofs lie on unrelated branches (M's pattern, in both matrices); columns 0..2 of dtau_dq on a
+ * floating base (nothing depends on where the base is); and, with v NULL, every velocity term of dtau_dq (that sweep is not run).
+ * The closed forms are at the head of csrc/wbcqp_idderiv.hpp and in DESIGN 4.22.  Offsets are 64-bit.  F32 handles read float, compute in double
+ * and write float.
+ * Refused with WBCQP_ERR_INVALID before anything is launched (nothing is written): a slot without a model, batch < 0, outputs NULL or both members
+ * NULL, dtau_dv without v, lda < nv with a given, wrench given while no frames are selected, q NULL (batch > 0).  batch == 0: WBCQP_OK, nothing
+ * launched. */
+typedef struct {
+    void *dtau_dq, *dtau_dv;
+} wbcqp_id_derivative_outputs;
+/* DEVICE pointers of the handle's dtype, asynchronous on `stream`, ordered like wbcqp_observe. */
+int wbcqp_inverse_dynamics_derivatives(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* a, int lda,
+                                       const void* wrench, const wbcqp_id_derivative_outputs* out, void* stream);
+/* Same with HOST pointers: stage through device buffers owned by the handle, block until done. */
+int wbcqp_inverse_dynamics_derivatives_host(wbcqp_handle* handle, int slot, int batch, const void* q, const void* v, const void* a, int lda,
+                                            const void* wrench, const wbcqp_id_derivative_outputs* out);
 
 /* ---- Did a robot hit something: model torques against measured torques over a stream of ticks ----
  * The reference's inria_wbc::safety::TorqueCollisionDetection (src/safety/torque_collision_detection.cpp) with the filters of

@@ -74,7 +74,7 @@ def build_poison(verbose: bool = False, force: bool = False) -> str:
 HOST = os.path.join(CSRC, "host")
 # the model-query programs of the facade (host/tests/<name>.cpp), in build order
 FACADE_TESTS = ("observe_facade_test", "collision_facade_test", "inverse_dynamics_facade_test", "forward_dynamics_facade_test",
-                "jacobian_facade_test", "hessian_facade_test", "torque_collision_facade_test", "stabilizer_facade_test")
+                "jacobian_facade_test", "hessian_facade_test", "id_derivatives_facade_test", "torque_collision_facade_test", "stabilizer_facade_test")
 
 
 def build_host(verbose: bool = False) -> dict:
@@ -146,7 +146,7 @@ def check_resources(usage: dict) -> None:
         raise RuntimeError("kernel-resource remarks not understood: %d solve_queue_kernel entries among %d kernels -- the build's register checks would "
                            "pass vacuously; refuse to ship" % (len(solve), len(usage)))
     for name, u in usage.items():
-        if ("solve_kernel" in name or "solve_queue_kernel" in name or "terms_kernel" in name or "integrate_kernel" in name or "task_costs_kernel" in name or "observe_kernel" in name or "collide_kernel" in name or "rnea_kernel" in name or "fdyn_kernel" in name or "jacobian_kernel" in name or "hessian_kernel" in name or "torque_monitor_kernel" in name) and (u.get("AGPRs", 0) != 0 or u.get("ScratchSize [bytes/lane]", 0) != 0 or u.get("VGPRs Spill", 0) != 0):
+        if ("solve_kernel" in name or "solve_queue_kernel" in name or "terms_kernel" in name or "integrate_kernel" in name or "task_costs_kernel" in name or "observe_kernel" in name or "collide_kernel" in name or "rnea_kernel" in name or "fdyn_kernel" in name or "jacobian_kernel" in name or "hessian_kernel" in name or "id_derivatives_kernel" in name or "torque_monitor_kernel" in name) and (u.get("AGPRs", 0) != 0 or u.get("ScratchSize [bytes/lane]", 0) != 0 or u.get("VGPRs Spill", 0) != 0):
             raise RuntimeError("%s: AGPRs %s, scratch %s B/lane, VGPR spills %s -- refuse to ship (see the comment in build.py)" %
                                (name, u.get("AGPRs"), u.get("ScratchSize [bytes/lane]"), u.get("VGPRs Spill")))
         # two workgroups per CU is what the queue kernels are sized and measured for (four waves each, one per SIMD: two waves per SIMD)

@@ -39,6 +39,7 @@ EXPORTS = ("wbcqp_version", "wbcqp_last_error", "wbcqp_create", "wbcqp_destroy",
            "wbcqp_spd_commands", "wbcqp_spd_commands_host",
            "wbcqp_set_jacobian_frames", "wbcqp_jacobians", "wbcqp_jacobians_host",
            "wbcqp_kinematic_hessians", "wbcqp_kinematic_hessians_host",
+           "wbcqp_inverse_dynamics_derivatives", "wbcqp_inverse_dynamics_derivatives_host",
            "wbcqp_torque_monitor_state_bytes", "wbcqp_detect_torque_collisions", "wbcqp_detect_torque_collisions_host",
            "wbcqp_stabilizer_state_bytes", "wbcqp_stabilize", "wbcqp_stabilize_host",
            "wbcqp_set_force_references", "wbcqp_stabilize_zmp", "wbcqp_stabilize_zmp_host")
@@ -53,6 +54,9 @@ JACOBIAN_OUTPUTS = ("J", "Jcom", "Ag", "drift", "dAgv")  # what wbcqp_jacobians 
 # tests/test_capi_binding.py fixes the number of structures THIS module defines (31) and checks their layouts, and existing tests stay as they
 # are; CHessianOutputs' layout is checked against the header in tests/test_hessians_host.py with the same function.
 from .hessians import OUTPUTS as HESSIAN_OUTPUTS, CHessianOutputs  # noqa: E402
+# what wbcqp_inverse_dynamics_derivatives writes (wbcqp_id_derivative_outputs; per instance nv x nv each): defined beside the call's numpy statement
+# for the same reason; the layout is checked against the header in tests/test_id_derivatives_host.py.
+from .id_derivatives import OUTPUTS as ID_DERIVATIVE_OUTPUTS, CIdDerivativeOutputs  # noqa: E402
 RF_WORLD, RF_LOCAL, RF_LOCAL_WORLD_ALIGNED = 0, 1, 2  # wbcqp_reference_frame: pinocchio's values
 COLLISIONS = ("colliding", "first_pair", "n_pairs", "clearance", "centres")  # what wbcqp_check_collisions writes (wbcqp_collisions)
 TRACE_FIELDS = ("q", "v", "x", "tau", "status", "iters", "objective", "cost")  # what a roll-out can keep per recorded tick (wbcqp_trace)
@@ -314,6 +318,7 @@ SIGNATURES = {
     "wbcqp_set_jacobian_frames": _sig(_vp, _int, _int, c_i32_p),
     "wbcqp_jacobians": _sig(_vp, _int, _int, _vp, _vp, _int, _p(CJacobianOutputs), _vp),
     "wbcqp_kinematic_hessians": _sig(_vp, _int, _int, _vp, _vp, _int, _p(CHessianOutputs), _vp),
+    "wbcqp_inverse_dynamics_derivatives": _sig(_vp, _int, _int, _vp, _vp, _vp, _int, _vp, _p(CIdDerivativeOutputs), _vp),
     "wbcqp_torque_monitor_state_bytes": _sig(_p(CTorqueMonitor), restype=C.c_int64),
     "wbcqp_detect_torque_collisions": _sig(_vp, _p(CTorqueMonitor), _int, _int, _vp, _int, _vp, _vp, _p(CTorqueChecks), _vp),
     "wbcqp_stabilizer_state_bytes": _sig(_p(CStabilizer), restype=C.c_int64),
@@ -323,7 +328,7 @@ SIGNATURES = {
 # the _host forms that are the device signature without the stream
 for _name in ("wbcqp_solve_batch", "wbcqp_integrate", "wbcqp_problem_data", "wbcqp_tick", "wbcqp_observe", "wbcqp_observe_acom",
               "wbcqp_check_collisions", "wbcqp_inverse_dynamics", "wbcqp_mass_matrix", "wbcqp_forward_dynamics", "wbcqp_spd_commands",
-              "wbcqp_jacobians", "wbcqp_kinematic_hessians", "wbcqp_detect_torque_collisions", "wbcqp_stabilize", "wbcqp_stabilize_zmp"):
+              "wbcqp_jacobians", "wbcqp_kinematic_hessians", "wbcqp_inverse_dynamics_derivatives", "wbcqp_detect_torque_collisions", "wbcqp_stabilize", "wbcqp_stabilize_zmp"):
     SIGNATURES[_name + "_host"] = (SIGNATURES[_name][0], SIGNATURES[_name][1][:-1])
 
 
@@ -729,6 +734,34 @@ class Handle:
         self._check(self.lib.wbcqp_inverse_dynamics_host(self._h, slot, B, q.ctypes.data, dat(v), dat(a), int(a.shape[-1]) if a is not None else 0,
                                                          dat(wrench), tau.ctypes.data))
         return tau
+
+    def inverse_dynamics_derivatives(self, slot: int, batch: int, q, v=None, a=None, lda: int = 0, wrench=None, dtau_dq=None, dtau_dv=None,
+                                     stream: int = 0):
+        """dtau/dq and dtau/dv of the inverse dynamics of `batch` states on device tensors (wbcqp_inverse_dynamics_derivatives); the inputs are
+        inverse_dynamics': q [batch, nq]; v [batch, nv] or None (zero); a or None (zero): row i starts lda elements after row i - 1 (lda = 0:
+        a.shape[-1]); wrench [batch, n_frames, 6] or None.  Outputs, each optional: dtau_dq, dtau_dv [batch, nv, nv] ([b, i, j] = d tau_i / d q_j,
+        d tau_i / d v_j; dtau_dv needs v)."""
+        if a is not None and lda == 0:
+            lda = int(a.shape[-1])
+        ptr = dev_ptr_given
+        out = CIdDerivativeOutputs(ptr(dtau_dq), ptr(dtau_dv))
+        self._check(self.lib.wbcqp_inverse_dynamics_derivatives(self._h, slot, int(batch), ptr(q), ptr(v), ptr(a), int(lda), ptr(wrench),
+                                                                C.byref(out), C.c_void_p(stream)))
+
+    def inverse_dynamics_derivatives_host(self, slot: int, q: np.ndarray, v: Optional[np.ndarray] = None, a: Optional[np.ndarray] = None,
+                                          wrench: Optional[np.ndarray] = None, which: Optional[Sequence[str]] = None) -> Dict[str, np.ndarray]:
+        """wbcqp_inverse_dynamics_derivatives_host: a dict of the outputs named in `which` (of ID_DERIVATIVE_OUTPUTS), each [B, nv, nv].  which
+        None: dtau_dq and, with v, dtau_dv.  a [B, lda] with lda >= nv: its first nv columns are the accelerations."""
+        q, v, a, wrench = self._host(q, v, a, wrench)
+        B, nv, f = q.shape[0], self._nv(slot), self.np_dtype
+        if which is None:
+            which = ["dtau_dq"] + (["dtau_dv"] if v is not None else [])
+        res, ptrs = host_outputs({k: ((B, nv, nv), f) for k in ID_DERIVATIVE_OUTPUTS}, which)
+        out = CIdDerivativeOutputs(*ptrs)
+        dat = host_ptr
+        self._check(self.lib.wbcqp_inverse_dynamics_derivatives_host(self._h, slot, B, q.ctypes.data, dat(v), dat(a),
+                                                                     int(a.shape[-1]) if a is not None else 0, dat(wrench), C.byref(out)))
+        return res
 
     def mass_matrix(self, slot: int, batch: int, q, M, stream: int = 0):
         """M(q) of `batch` states on device tensors (wbcqp_mass_matrix): q [batch, nq], M [batch, nv, nv], both triangles."""

@@ -116,6 +116,12 @@ namespace inria_wbc {
             // axes; n <= 8) -- wbcqp_inverse_dynamics_host.  Only a source that holds a model can tell
             virtual void inverse_dynamics(const MatrixXd&, const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, const MatrixXd&, MatrixXd&)
             { IWBC_ERROR(no_model(RNEA)); }
+            // dtau/dq and dtau/dv of the inverse dynamics at (q, v, a), each B x nv*nv (row-major per instance: [i][j] = d tau_i / d q_j, d tau_i /
+            // d v_j; d/dq_j in the tangent space), for the n named model frames and their wrenches as for inverse_dynamics --
+            // wbcqp_inverse_dynamics_derivatives_host.  Only a source that holds a model can tell
+            virtual void inverse_dynamics_derivatives(const MatrixXd&, const MatrixXd&, const MatrixXd&, const std::vector<std::string>&, const MatrixXd&,
+                                                      MatrixXd&, MatrixXd&)
+            { IWBC_ERROR(no_model(RNEA)); }
             // M(q), B x nv*nv (row-major per instance, both triangles) -- wbcqp_mass_matrix_host.  Only a source that holds a model can tell
             virtual void mass_matrix(const MatrixXd&, MatrixXd&)
             { IWBC_ERROR(no_model(INERTIA)); }
@@ -414,6 +420,24 @@ namespace inria_wbc {
                 _model_source(ProblemSource::FDYN).forward_dynamics(q_tsid_, v_tsid_, tau, {}, MatrixXd(), {}, a, flags);
                 if (info) *info = flags;
                 return a;
+            }
+            // The linearisation of the inverse dynamics tau = M(q) a + nle(q, v) (pinocchio's computeRNEADerivatives) for every instance at the
+            // controller's current q_tsid(), dq(false) and the accelerations a (B x nv, or wider: the first nv columns), no wrenches: dtau_dq and
+            // dtau_dv, each B x nv*nv with instance i's matrix row-major in row i ([r][c] = d tau_r / d q_c along dof c in the tangent space,
+            // d tau_r / d v_c); d tau / d a is inertia_matrix().  Computed on the device (wbcqp_inverse_dynamics_derivatives_host) when somebody
+            // asks and kept with the state and with `a` like inertia_matrix(): the same question again costs no second call.
+            struct IdDerivatives {
+                MatrixXd dtau_dq, dtau_dv;
+            };
+            const IdDerivatives& inverse_dynamics_derivatives(const MatrixXd& a) const
+            {
+                ProblemSource& source = _model_source(ProblemSource::RNEA);
+                if (idd_a_.rows != a.rows || idd_a_.data != a.data) idd_at_ = ComputedAt{}; // (another a: another answer)
+                _keep(idd_at_, &v_tsid_, [&] {
+                    source.inverse_dynamics_derivatives(q_tsid_, v_tsid_, a, {}, MatrixXd(), idd_.dtau_dq, idd_.dtau_dv);
+                    idd_a_ = a;
+                });
+                return idd_;
             }
             // compute_spd of inria_wbc/robots/cmd.hpp goes through here: the states are the caller's (a simulator's), not the controller's
             MatrixXd spd_commands(const MatrixXd& q, const MatrixXd& dq, const MatrixXd& targetpos, double dt, double kp, double kd) const
@@ -738,6 +762,9 @@ namespace inria_wbc {
             mutable ComputedAt obs_at_; // the state and the source the four above were made for
             mutable MatrixXd mass_;
             mutable ComputedAt mass_at_; // the state (q alone) and the source mass_ was made for
+            mutable IdDerivatives idd_;
+            mutable MatrixXd idd_a_;
+            mutable ComputedAt idd_at_; // the state and the source idd_ was made for; idd_a_: the accelerations
 
             // who answers for Jacobians and Hessians in the convention rf
             ProblemSource& _jacobian_source(int rf) const

@@ -215,6 +215,19 @@ namespace inria_wbc {
                 check(wbcqp_inverse_dynamics_host(handle_, slot_, batch_, q.data.data(), v.data.data(), a.data.data(), a.cols, w, tau.data.data()),
                       "wbcqp_inverse_dynamics_host");
             }
+            // wbcqp_inverse_dynamics_derivatives_host on the slot in use; the wrench frames are inverse_dynamics' selection
+            void inverse_dynamics_derivatives(const MatrixXd& q, const MatrixXd& v, const MatrixXd& a, const std::vector<std::string>& frames,
+                                              const MatrixXd& wrenches, MatrixXd& dtau_dq, MatrixXd& dtau_dv) override
+            {
+                bound(q, &v, &a);
+                const double* w = select_wrenches(frames, wrenches);
+                const int nv = robot_->nv();
+                dtau_dq = MatrixXd(batch_, nv * nv);
+                dtau_dv = MatrixXd(batch_, nv * nv);
+                const wbcqp_id_derivative_outputs out = {dtau_dq.data.data(), dtau_dv.data.data()};
+                check(wbcqp_inverse_dynamics_derivatives_host(handle_, slot_, batch_, q.data.data(), v.data.data(), a.data.data(), a.cols, w, &out),
+                      "wbcqp_inverse_dynamics_derivatives_host");
+            }
             // wbcqp_mass_matrix_host on the slot in use
             void mass_matrix(const MatrixXd& q, MatrixXd& M) override
             {

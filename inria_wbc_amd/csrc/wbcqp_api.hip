@@ -832,6 +832,33 @@ int wbcqp_kinematic_hessians_host(wbcqp_handle* h, int slot, int batch, const vo
     });
 }
 
+int wbcqp_inverse_dynamics_derivatives(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
+                                       const wbcqp_id_derivative_outputs* out, void* stream)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_inverse_dynamics_derivatives(h, slot, batch, q, v, a, lda, wrench, out, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    return launch_inverse_dynamics_derivatives(h, *s, batch, q, v, a, lda, wrench, *out, static_cast<hipStream_t>(stream));
+}
+
+int wbcqp_inverse_dynamics_derivatives_host(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
+                                            const wbcqp_id_derivative_outputs* out)
+{
+    const Slot* s = nullptr;
+    WB_TRY(check_inverse_dynamics_derivatives(h, slot, batch, q, v, a, lda, wrench, out, &s));
+    if (!s) return WBCQP_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    const size_t es = elem_size(h), B = (size_t)batch, nv = (size_t)s->terms.nv;
+    // (a: rows lda apart, the last one nv long -- nothing behind it is the caller's to give)
+    Arr up[4] = {{-1, const_cast<void*>(q), B * s->terms.nq * es, 0}, {-1, const_cast<void*>(v), B * nv * es, 0},
+                 {-1, const_cast<void*>(a), ((B - 1) * (size_t)(a ? lda : 0) + nv) * es, 0}, {-1, const_cast<void*>(wrench), B * s->wrench.n * 6 * es, 0}};
+    Arr dn[2] = {{-1, out->dtau_dq, B * nv * nv * es, 0}, {-1, out->dtau_dv, B * nv * nv * es, 0}};
+    return staged_call(h, up, dn, [&](void* const* u, void* const* d) {
+        return launch_inverse_dynamics_derivatives(h, *s, batch, u[0], u[1], u[2], lda, u[3], wbcqp_id_derivative_outputs{d[0], d[1]}, nullptr);
+    });
+}
+
 int64_t wbcqp_torque_monitor_state_bytes(const wbcqp_torque_monitor* monitor)
 {
     return monitor_flaw(monitor) ? 0 : (int64_t)monitor_state_bytes(monitor->n_joints, monitor->filter, monitor->window);

@@ -1,7 +1,8 @@
 // wbcqp_host_queries.hpp -- host side of the model queries on a fleet's states (wbcqp_api.hip): wbcqp_observe, wbcqp_check_collisions and
 // wbcqp_inverse_dynamics, each with the set-up call that puts its table on the slot, and wbcqp_mass_matrix, wbcqp_forward_dynamics and
 // wbcqp_spd_commands (fdyn_kernel, csrc/wbcqp_fdyn.hpp, behind rnea_kernel for the bias), wbcqp_jacobians (jacobian_kernel,
-// csrc/wbcqp_jacobians.hpp) and wbcqp_kinematic_hessians (hessian_kernel, csrc/wbcqp_hessians.hpp).  Per query: ONE check_* that the device-pointer and the
+// csrc/wbcqp_jacobians.hpp), wbcqp_kinematic_hessians (hessian_kernel, csrc/wbcqp_hessians.hpp) and wbcqp_inverse_dynamics_derivatives
+// (id_derivatives_kernel, csrc/wbcqp_idderiv.hpp).  Per query: ONE check_* that the device-pointer and the
 // host-pointer entry point share (nothing is staged or launched before it has passed) and ONE launch_* of its kernel (csrc/wbcqp_observe.hpp,
 // wbcqp_collide.hpp, wbcqp_rnea.hpp), one wavefront per instance.  Host code only; included by wbcqp_api.hip alone.
 #pragma once
@@ -9,6 +10,7 @@
 #include "wbcqp_fdyn.hpp"
 #include "wbcqp_jacobians.hpp"
 #include "wbcqp_hessians.hpp"
+#include "wbcqp_idderiv.hpp"
 
 namespace {
 
@@ -19,6 +21,7 @@ static_assert(kJacobianPerBlock == kRneaPerBlock && WBCQP_MAX_JACOBIAN_FRAMES ==
 static_assert(WBCQP_RF_WORLD == kRfWorld && WBCQP_RF_LOCAL == kRfLocal && WBCQP_RF_LOCAL_WORLD_ALIGNED == kRfLocalWorldAligned,
               "the header and the kernel agree on the reference frames");
 static_assert(kHessianPerBlock == kRneaPerBlock, "hessian_kernel: the same instances per workgroup");
+static_assert(kIdDerivPerBlock == kRneaPerBlock, "id_derivatives_kernel: the same instances per workgroup");
 static_assert(WBCQP_MAX_WRENCH_FRAMES == kMaxWrenchFrames, "the header and the kernel agree on the number of wrench frames");
 
 // workgroups for `batch` instances at one wavefront each
@@ -432,6 +435,42 @@ int launch_hessians(wbcqp_handle* h, const Slot& s, int batch, const void* q, co
             hipLaunchKernelGGL((hessian_kernel<TI, true>), dim3(query_blocks(batch)), dim3(kHessianThreads), 0, stream, a);
         else
             hipLaunchKernelGGL((hessian_kernel<TI, false>), dim3(query_blocks(batch)), dim3(kHessianThreads), 0, stream, a);
+        HIP_TRY(h, hipGetLastError());
+        return WBCQP_OK;
+    });
+}
+
+// ---- the inverse dynamics' derivatives: wbcqp_inverse_dynamics_derivatives ------------------------------------------------------------------------------
+int check_inverse_dynamics_derivatives(wbcqp_handle* h, int slot, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
+                                       const wbcqp_id_derivative_outputs* out, const Slot** s)
+{
+    *s = nullptr;
+    if (!h) return WBCQP_ERR_INVALID;
+    const Slot* sl = slot_with_model(h, slot);
+    if (!sl) return WBCQP_ERR_INVALID;
+    if (batch < 0) return fail(h, WBCQP_ERR_INVALID, "negative batch");
+    if (!out) return fail(h, WBCQP_ERR_INVALID, "inverse dynamics derivative outputs struct is NULL");
+    if (!out->dtau_dq && !out->dtau_dv) return fail(h, WBCQP_ERR_INVALID, "every output is NULL: nothing is asked for");
+    if (out->dtau_dv && !v) return fail(h, WBCQP_ERR_INVALID, "dtau_dv asked for, but v is NULL");
+    if (a && lda < sl->terms.nv) return fail(h, WBCQP_ERR_INVALID, "lda must be at least nv");
+    if (wrench && sl->wrench.n == 0) return fail(h, WBCQP_ERR_INVALID, "wrench given, but no frames are selected (wbcqp_set_wrench_frames)");
+    if (batch == 0) return WBCQP_OK;
+    if (!q) return fail(h, WBCQP_ERR_INVALID, "q is NULL");
+    *s = sl;
+    return WBCQP_OK;
+}
+
+int launch_inverse_dynamics_derivatives(wbcqp_handle* h, const Slot& s, int batch, const void* q, const void* v, const void* a, int lda, const void* wrench,
+                                        const wbcqp_id_derivative_outputs& out, hipStream_t stream)
+{
+    const TermsDev& T = s.terms;
+    const RneaDev D{T.nb, T.nq, T.nv, T.floating_base, T.nrounds, {T.g[0], T.g[1], T.g[2]}, T.ipool, T.dpool, T.i_jtype, T.i_last, T.i_idxq, T.i_idxv, T.i_anc,
+                    T.i_bodyof, T.i_kof, T.d_place, T.d_inertia, wrench ? s.wrench.n : 0, s.wrench.body, s.wrench.place};
+    return with_dtype(h, [&](auto tag) -> int {
+        using TI = WB_TI(tag);
+        const IdDerivArgs<TI> args{D, static_cast<const TI*>(q), static_cast<const TI*>(v), static_cast<const TI*>(a), static_cast<const TI*>(wrench),
+                                   static_cast<TI*>(out.dtau_dq), static_cast<TI*>(out.dtau_dv), a ? lda : 0, batch};
+        hipLaunchKernelGGL(id_derivatives_kernel<TI>, dim3(query_blocks(batch)), dim3(kIdDerivThreads), 0, stream, args);
         HIP_TRY(h, hipGetLastError());
         return WBCQP_OK;
     });
